@@ -124,6 +124,16 @@ def cpu_model():
     return "unknown"
 
 
+def dump_outputs(path, preds, detections):
+    """What a caller of the timed step receives: every decoder layer's class scores and boxes of this rank's sample
+    ([layers, 1, queries, ...]) and the gathered fixed-shape detections ([world, 1, 300, 11]), as float32 .npy files (under 1 MB
+    at f8).  The inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("all_cls_scores", preds["all_cls_scores"]), ("all_bbox_preds", preds["all_bbox_preds"]),
+                    ("detections", detections)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def launch_ranks(args):
     """Parent of a multi-GPU run: N fresh child processes (one rank per GPU, RCCL) through torch.distributed.run, started
     BEFORE this process makes any HIP call; the parent only waits and passes the children's exit status on (the reference's
@@ -333,6 +343,8 @@ def main():
                     help="storage of the two hoisted BEV value streams (internal tensors of the path): the reference's fp32 maps (the "
                          "product default and the headline) or the opt-in int16 block storage written by their producers' epilogues")
     ap.add_argument("--blas", default="", help="torch.backends.cuda.preferred_blas_library override (experiment)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--plumbing-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -346,6 +358,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     if args.plumbing_only:
         return plumbing_only(args, rank, world)
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps}: at least one timed step is needed")
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
     use_pg = world > 1 or args.force_collective
@@ -393,7 +407,7 @@ def main():
             fresh = [dict(m) for m in metas]                # new sample -> metas are staged (H2D) again
             preds = head(list(pyramid), lss, radar, fresh)
             det = head.get_detections_fixed(preds)          # [1,300,11]
-            return dp.all_gather_detections(det, force_collective=args.force_collective)   # [world,1,300,11]
+            return preds, dp.all_gather_detections(det, force_collective=args.force_collective)   # [world,1,300,11]
 
     captured, capture_error = None, None
     if not args.no_graph:
@@ -427,10 +441,10 @@ def main():
             cap, st, m_i = lanes[turn[0] % len(lanes)]
             turn[0] += 1
             with torch.cuda.stream(st):
-                _, det = cap.replay(img_metas=m_i)
-                return dp.all_gather_detections(det, force_collective=args.force_collective)
-        _, det = captured.replay(img_metas=metas)
-        return dp.all_gather_detections(det, force_collective=args.force_collective)
+                preds, det = cap.replay(img_metas=m_i)
+                return preds, dp.all_gather_detections(det, force_collective=args.force_collective)
+        preds, det = captured.replay(img_metas=metas)
+        return preds, dp.all_gather_detections(det, force_collective=args.force_collective)
 
     def fence():
         torch.cuda.synchronize()
@@ -453,6 +467,9 @@ def main():
     host_elapsed = time.perf_counter() - t0     # the host has enqueued every step (it runs ahead of the GPU unless it is the limiter)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: a captured plan's outputs are its graph's buffers, rewritten by its next replay
+        dump_outputs(args.dump_outputs, *out)
     single = lanes_match = None
     if captured is not None:
         if not lanes:
@@ -513,7 +530,7 @@ def main():
         dist.all_gather(allr, mine)
         per_rank_ms = [1e3 * float(t.item()) / args.steps for t in allr]
         elapsed = max(float(t.item()) for t in allr)      # max over ranks
-        merged = dp.merge_interleaved(out, world)           # one sample per rank per step, dataset order
+        merged = dp.merge_interleaved(out[1], world)        # one sample per rank per step, dataset order
         assert tuple(merged.shape) == (world, 300, 11)
     # the dominant kernel: the stand-alone sampling kernel (rac_sampling4d_fwd); with decoder_layer.fuse_sampling_mixing = True
     # (RAC_FUSE_SAMPLING_MIXING=1: measured and rejected in round 4) the sampling runs inside the mixing kernel

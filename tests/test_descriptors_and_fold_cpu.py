@@ -8,6 +8,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 import torch
 import torch.nn.functional as F
@@ -41,14 +42,13 @@ def _c_layout(struct, fields):
             f'  printf("%zu\\n", sizeof({struct}));']
     prog += [f'  printf("%zu\\n", offsetof({struct}, {f}));' for f in fields]
     prog += ["  return 0;", "}"]
-    src = os.path.join("/tmp", f"rac_layout_{struct}_{os.getpid()}.c")
-    exe = src[:-2]
-    with open(src, "w") as fh:
-        fh.write("\n".join(prog))
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()
-    os.remove(src)
-    os.remove(exe)
+    with tempfile.TemporaryDirectory() as tmp:
+        src = os.path.join(tmp, f"rac_layout_{struct}.c")
+        exe = src[:-2]
+        with open(src, "w") as fh:
+            fh.write("\n".join(prog))
+        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()
     return int(out[0]), [int(v) for v in out[1:]]
 
 

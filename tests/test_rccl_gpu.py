@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -16,11 +17,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["captured", "eager"])
-def test_bench_step_with_forced_rccl_all_gather(graph):
+def test_bench_step_with_forced_rccl_all_gather(graph, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-           "--no-stress", "--force-collective"] + ([] if graph else ["--no-graph"])
+           "--no-stress", "--force-collective", "--dump-outputs", str(tmp_path)] + ([] if graph else ["--no-graph"])
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -28,3 +29,10 @@ def test_bench_step_with_forced_rccl_all_gather(graph):
     assert c["backend"] == "nccl" and c["world"] == 1 and c["forced_at_world_1"] is True
     assert c["gathered_shape"] == [1, 1, 300, 11] and c["own_slot_equals_local"] is True
     assert line["value"] > 0 and line["n_gpus"] == 1
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    # --dump-outputs: the last timed step's outputs, float32, finite, in the shapes a caller receives
+    shapes = {"all_cls_scores": (6, 1, 900, 10), "all_bbox_preds": (6, 1, 900, 10), "detections": (1, 1, 300, 11)}
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in shapes)
+    for name, shape in shapes.items():
+        a = np.load(os.path.join(tmp_path, name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), (name, a.dtype, a.shape)

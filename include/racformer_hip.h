@@ -22,6 +22,8 @@
  *   rac_sampling4d_fwd<- RaCFormerSampling.inner_forward + sampling_4d + msmv op, fused
  *                        models/racformer_transformer.py:361-419, models/sparsebev_sampling.py:28-134
  *   rac_msmv_bwd / rac_msda_bwd <- the two operators' backward entry points (row f4)
+ *   rac_msmv_v2_fwd / rac_msmv_v2_bwd <- msmv_sampling_v2 (torch only in the reference: msmv_sampling_pytorch_v2,
+ *                        models/csrc/wrapper.py:41-76), called by sampling_4d(aggregate=False), models/sparsebev_sampling.py:122-134
  *   rac_bev_pool_v2_fwd/_bwd <- bev_pool_v2_ext (models/csrc/bev_pool_v2/src/bev_pool.cpp:40-111), row f2
  *   rac_add_ln_fwd    <- residual add + nn.LayerNorm (+ReLU) groups, models/racformer_transformer.py:170-258
  *   rac_layer_boundary_fwd <- rac_refine_fwd + rac_box_prep_fwd + rac_pe_head_fwd of consecutive layers, one launch
@@ -54,7 +56,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 8
+#define RAC_ABI_VERSION 9
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -86,6 +88,22 @@ const char *rac_last_error(void);
 int rac_msmv_fwd(const void *const *feats, const int32_t *hw, int L, const float *loc,
                  const float *w, float *out, int S, int N, int Q, int P, int C, int dtype,
                  int out_layout, int T, int G, void *stream);
+
+/* Feature layouts of rac_msmv_v2_fwd / rac_msmv_v2_bwd. */
+enum {
+    RAC_FEAT_CL = 0, /* [S,N,H,W,C] channel-last -- the package's pyramid (rac_regroup_fwd), what rac_msmv_fwd takes  */
+    RAC_FEAT_CF = 1  /* [S,C,N,H,W] channel-first -- what the reference's torch path hands grid_sample (fp32 only)  */
+};
+
+/* Hard-level multi-scale multi-view sampling (msmv_sampling_v2), forward: the level with the largest weight alone.
+ *   feats[l] : device ptr, layout `feat_layout`, dtype `dtype` (RAC_BF16: channel-last only)
+ *   hw, loc, w, out, T, G: as rac_msmv_fwd (w is only read to pick the level)
+ * out[s,q,c,p] = bilinear0(feats[l*][s, round(view*(N-1))], u*(W_l*-1), v*(H_l*-1)), NOT multiplied by the weight, where
+ *   l* = argmax_l w[s,q,p,l] as torch.argmax: ties to the first index, a NaN counts as maximal (the first NaN wins),
+ *        an all -inf row gives 0.  Only level l*'s four taps are read. */
+int rac_msmv_v2_fwd(const void *const *feats, const int32_t *hw, int L, const float *loc, const float *w, float *out,
+                    int S, int N, int Q, int P, int C, int dtype, int feat_layout, int out_layout, int T, int G,
+                    void *stream);
 
 /* Multi-scale deformable attention, forward (Deformable-DETR semantics, align_corners=False).
  *   value  : device, [bs, keys, heads, dim], dtype `dtype`
@@ -435,6 +453,13 @@ int rac_decode_fwd(const float *cls_scores, const float *bbox_preds, float *out,
 int rac_msmv_bwd(const float *grad_out, const void *const *feats, const int32_t *hw, int L, const float *loc,
                  const float *w, void *const *grad_feats, float *grad_loc, float *grad_w, int S, int N, int Q,
                  int P, int C, void *stream);
+/* Backward of rac_msmv_v2_fwd (fp32 features, either layout; grad_out [S,Q,C,P]).  grad_feats[l] like feats[l] and
+ * ZERO-FILLED by the caller: only level l* of each point receives its scatter (float atomics, last bits may vary from run to
+ * run).  grad_loc [S,Q,P,3] overwritten, one writer per element (deterministic): (u, v) = (W_l*-1 | H_l*-1) *
+ * sum_c grad_out[c] * d bilinear / d(w | h), view component 0 (as rac_msmv_bwd).  The weights get no gradient (argmax). */
+int rac_msmv_v2_bwd(const float *grad_out, const void *const *feats, const int32_t *hw, int L, const float *loc,
+                    const float *w, void *const *grad_feats, float *grad_loc, int S, int N, int Q, int P, int C,
+                    int feat_layout, void *stream);
 int rac_msda_bwd(const float *grad_out, const float *value, const int64_t *shapes, const int64_t *starts,
                  const float *loc, const float *attn, float *grad_value, float *grad_loc, float *grad_attn,
                  int bs, int keys, int heads, int dim, int Q, int L, int P, void *stream);

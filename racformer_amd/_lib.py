@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RACFORMER_HIP_LIB") or os.path.join(_HERE, "csrc", "libracformer_hip.so")
 RAC_F32, RAC_BF16, RAC_I16 = 0, 1, 2
 OUT_SQCP, OUT_BQGTPC = 0, 1
+FEAT_CL, FEAT_CF = 0, 1
 MIX_F32, MIX_F16X3 = 0, 1
 _lib = None
 
@@ -28,6 +29,8 @@ SIGNATURES = {
     "rac_box_prep_fwd": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rac_sampling4d_fwd": (_i, [_vp, _vp, _i] + [_vp] * 11 + [_i] * 3 + [_i] * 8 + [_vp, _vp] + [_f] * 4 + [_i, _i, _vp]),
     "rac_msmv_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "rac_msmv_v2_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
+    "rac_msmv_v2_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "rac_msda_bwd": (_i, [_vp] * 9 + [_i] * 7 + [_vp]),
     "rac_bev_pool_v2_fwd": (_i, [_vp] * 8 + [_i, _i, _vp]),
     "rac_bev_pool_v2_bwd": (_i, [_vp] * 10 + [_i, _i, _vp]),

@@ -34,7 +34,7 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act
                     pe_head, refine_fused, row_gemm,
                     row_seg, rowgemm_launch, sampling4d_fused, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
 from .msda import msda_forward
-from .msmv import msmv_forward
+from .msmv import msmv_forward, msmv_v2_forward
 
 try:  # registry decorators are applied only if mmdet happens to be importable
     from mmdet.models.utils.builder import TRANSFORMER as _TRANSFORMER
@@ -295,9 +295,10 @@ def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, im
     """sparsebev_sampling.py:28-134 on the HIP msmv operator.
     sample_points [B,Q,T,G,P,3]; mlvl_feats[l] [B*T*G,N,H,W,C] channel-last; scale_weights
     [B,Q,G,T,P,L]; lidar2img [B,T*N,4,4] -> [B,Q,G,T*P,C].  Projection, validity, first-valid-view
-    selection and the (b,g,t)-vs-(b,t,g) weight slot order (:113-120) are as in the reference."""
-    if not aggregate:
-        raise NotImplementedError("sampling_4d(aggregate=False) is not on the inference path")
+    selection and the (b,g,t)-vs-(b,t,g) weight slot order (:113-120) are as in the reference.
+    ``aggregate=False`` (:125-134): every point is sampled on its argmax-weight level only (msmv_sampling_v2, rac_msmv_v2_fwd)
+    and the result is (final [B,Q,G,T*P,C], homo[:,0] [B,N,Q,G*P,1] -- the first frame's raw camera depth, before the eps
+    clamp --, i_view[:,0] [B,Q,G*P,1] int64 -- the camera sampled, the imposed one under ``view_in``)."""
     B, Q, T, G, P, _ = sample_points.shape
     N = lidar2img.shape[1] // T
     m = lidar2img.view(B, T, N, 1, 1, 4, 4)
@@ -322,6 +323,9 @@ def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, im
         loc_tap.append(own.view(B, T, Q, G, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(B * T * G, Q, P, 3))
     L = scale_weights.shape[-1]
     w = scale_weights.reshape(B, Q, G, T, P, L).permute(0, 2, 3, 1, 4, 5).reshape(B * G * T, Q, P, L).contiguous()
+    if not aggregate:
+        final = msmv_v2_forward(mlvl_feats, loc, w, out_layout=_lib.OUT_BQGTPC, num_frames=T, num_groups=G)
+        return final, homo[:, 0, ..., None], i_view[:, 0, 0, ..., None]
     return msmv_forward(mlvl_feats, loc, w, out_layout=_lib.OUT_BQGTPC, num_frames=T, num_groups=G)
 
 

@@ -116,6 +116,27 @@ def _clib():
     return _CLIB
 
 
+def _round_half_away(x):
+    """round half away from zero, as C ``round`` / ``roundf`` (the reference's and the kernels' view pick,
+    msmv_sampling_forward.cu:110); ``torch.round`` rounds half to even."""
+    t = torch.trunc(x)
+    return torch.where((x - t).abs() >= 0.5, t + torch.sign(x), t)   # x - trunc(x) is exact: no tie is made by rounding
+
+
+def _coord(x, scale, shift, f32_coords):
+    """``x * scale - shift``: the sampling coordinate of a normalised location.  With ``f32_coords`` and a wider
+    input the value is formed in float32, as the kernels and the reference form it (one rounding per operation), and
+    then promoted; the derivative stays ``scale`` in the input's precision.  A float64 reference then picks the same
+    taps, guard and view as the kernel even where a float32 product rounds onto an integer."""
+    y = x * scale - shift if shift else x * scale
+    if f32_coords and x.dtype != torch.float32:
+        y32 = x.detach().float() * scale
+        if shift:
+            y32 = y32 - shift
+        y = y + (y32.to(y.dtype) - y.detach())
+    return y
+
+
 def _bilinear_taps(fmap, h_im, w_im):
     """fmap [H,W,C] (any leading index handled by caller); h_im,w_im [K] float32.
     4-tap bilinear with per-tap bounds checks (msmv_sampling_forward.cu:27-73)."""
@@ -136,19 +157,20 @@ def _bilinear_taps(fmap, h_im, w_im):
             + (lh * hw)[:, None] * tap(h_high, w_low) + (lh * lw)[:, None] * tap(h_high, w_high))
 
 
-def msmv_gather_torch(feats_cl, loc, w):
+def msmv_gather_torch(feats_cl, loc, w, f32_coords=False):
     """Pure-torch kernel-semantics msmv (small cases).  feats_cl[l]: [S,N,H,W,C]; loc [S,Q,P,3];
-    w [S,Q,P,L] -> [S,Q,C,P].  Follows msmv_sampling_forward.cu:105-162."""
+    w [S,Q,P,L] -> [S,Q,C,P], in the operands' dtype.  Follows msmv_sampling_forward.cu:105-162.
+    ``f32_coords``: see ``_coord``."""
     S, N = feats_cl[0].shape[:2]
     C = feats_cl[0].shape[-1]
     _, Q, P, _ = loc.shape
-    view = torch.round(loc[..., 2] * (N - 1)).long().reshape(-1)
+    view = _round_half_away(_coord(loc[..., 2].detach(), N - 1, 0, f32_coords)).long().reshape(-1)
     sidx = torch.arange(S)[:, None, None].expand(S, Q, P).reshape(-1)
     u, v = loc[..., 0].reshape(-1), loc[..., 1].reshape(-1)
-    out = torch.zeros(S * Q * P, C)
+    out = torch.zeros(S * Q * P, C, dtype=torch.promote_types(feats_cl[0].dtype, loc.dtype))
     for l, f in enumerate(feats_cl):
         H, W = f.shape[2:4]
-        h_im, w_im = v * (H - 1), u * (W - 1)
+        h_im, w_im = _coord(v, H - 1, 0, f32_coords), _coord(u, W - 1, 0, f32_coords)
         guard = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
         flat = f.reshape(S * N, H, W, C)
         base = sidx * N + view
@@ -196,11 +218,12 @@ def msmv_gather(feats_cl, loc, w, force_torch=False):
     return out
 
 
-def msda_torch(value, shapes, starts, loc, attn):
-    """Pure-torch MSDA with Deformable-DETR kernel semantics (align_corners=False)."""
+def msda_torch(value, shapes, starts, loc, attn, f32_coords=False):
+    """Pure-torch MSDA with Deformable-DETR kernel semantics (align_corners=False), in the operands' dtype.
+    ``f32_coords``: see ``_coord``."""
     bs, keys, heads, dim = value.shape
     _, Q, _, L, P, _ = loc.shape
-    out = torch.zeros(bs, Q, heads, dim)
+    out = torch.zeros(bs, Q, heads, dim, dtype=torch.promote_types(value.dtype, loc.dtype))
     for b in range(bs):
         for h in range(heads):
             for l in range(L):
@@ -209,7 +232,7 @@ def msda_torch(value, shapes, starts, loc, attn):
                 fmap = value[b, st:st + H * W, h].reshape(H, W, dim)
                 x = loc[b, :, h, l, :, 0].reshape(-1)
                 y = loc[b, :, h, l, :, 1].reshape(-1)
-                h_im, w_im = y * H - 0.5, x * W - 0.5
+                h_im, w_im = _coord(y, H, 0.5, f32_coords), _coord(x, W, 0.5, f32_coords)
                 guard = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
                 val = _bilinear_taps(fmap, h_im, w_im) * guard[:, None].float()
                 val = val * attn[b, :, h, l].reshape(-1)[:, None]

@@ -54,9 +54,11 @@ __global__ __launch_bounds__(256) void msda_bwd_d64_kernel(const MsdaBwdArgs a)
     const int H = a.H[l], W = a.W[l];
     const float h_im = y * (float)H - 0.5f, w_im = x * (float)W - 0.5f;
     const bool in = act && h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-    const float hf = floorf(h_im), wf = floorf(w_im);
+    // outside the guard the footprint is pinned to (0, 0): a NaN / inf coordinate would make the tap weights NaN, and
+    // NaN times the zero taps would reach grad_attn / grad_loc
+    const float hf = in ? floorf(h_im) : 0.f, wf = in ? floorf(w_im) : 0.f;
     const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-    const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
+    const float lh = in ? h_im - hf : 0.f, lw = in ? w_im - wf : 0.f, hh = 1.f - lh, hw = 1.f - lw;
     const int stride = a.heads * 64;
     const size_t map = (((size_t)b * a.keys + a.start[l]) * a.heads + h) * 64 + lane16;
     const float *base = a.value + map;

@@ -69,9 +69,11 @@ __global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const MsmvBwdArgs a)
         const int H = a.H[l], W = a.W[l];
         const float h_im = lv * (float)(H - 1), w_im = lu * (float)(W - 1);
         const bool in = act && h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-        const float hf = floorf(h_im), wf = floorf(w_im);
+        // outside the guard the footprint is pinned to (0, 0): a NaN / inf coordinate would make the tap weights NaN, and
+        // NaN times the zero taps would reach grad_loc through the location sums
+        const float hf = in ? floorf(h_im) : 0.f, wf = in ? floorf(w_im) : 0.f;
         const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-        const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
+        const float lh = in ? h_im - hf : 0.f, lw = in ? w_im - wf : 0.f, hh = 1.f - lh, hw = 1.f - lw;
         const size_t map = ((size_t)s * a.N + view) * H * W * 64 + lane16;
         const float *base = (const float *)a.feat[l] + map;
         float *gbase = a.gfeat[l] + map;

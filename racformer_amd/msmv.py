@@ -114,14 +114,15 @@ class MSMVSamplingC23456(_MSMVBase):
 
 
 def msmv_sampling(mlvl_feats, sampling_locations, scale_weights):
-    """wrapper.py:145-153.  Any level count 1..8 is served by the HIP operator."""
+    """wrapper.py:145-153.  Any level count 1..8 is served by the HIP operator, forward and backward (the reference's
+    other level counts take its differentiable torch path)."""
     if len(mlvl_feats) == 2:
         return MSMVSamplingC45.apply(*mlvl_feats, sampling_locations, scale_weights)
     if len(mlvl_feats) == 4:
         return MSMVSamplingC2345.apply(*mlvl_feats, sampling_locations, scale_weights)
     if len(mlvl_feats) == 5:
         return MSMVSamplingC23456.apply(*mlvl_feats, sampling_locations, scale_weights)
-    return msmv_forward(mlvl_feats, sampling_locations, scale_weights)
+    return _MSMVBase.apply(*mlvl_feats, sampling_locations, scale_weights)
 
 
 # ------------------------------------------------------------------------------------------ v2: hard level

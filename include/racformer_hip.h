@@ -22,6 +22,7 @@
  *   rac_sampling4d_fwd<- RaCFormerSampling.inner_forward + sampling_4d + msmv op, fused
  *                        models/racformer_transformer.py:361-419, models/sparsebev_sampling.py:28-134
  *   rac_msmv_bwd / rac_msda_bwd <- the two operators' backward entry points (row f4)
+ *   rac_msmv_bwd_ex / rac_msmv_v2_bwd_ex <- the same backwards reading the gradient in sampling_4d's [B,Q,G,T*P,C] layout
  *   rac_msmv_v2_fwd / rac_msmv_v2_bwd <- msmv_sampling_v2 (torch only in the reference: msmv_sampling_pytorch_v2,
  *                        models/csrc/wrapper.py:41-76), called by sampling_4d(aggregate=False), models/sparsebev_sampling.py:122-134
  *   rac_bev_pool_v2_fwd/_bwd <- bev_pool_v2_ext (models/csrc/bev_pool_v2/src/bev_pool.cpp:40-111), row f2
@@ -56,7 +57,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 9
+#define RAC_ABI_VERSION 10
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -67,7 +68,7 @@ enum {
     RAC_E_UNSUPPORTED = -2,
 };
 
-/* Output layouts of rac_msmv_fwd. */
+/* Output layouts of rac_msmv_fwd / rac_msmv_v2_fwd; gradient layouts of rac_msmv_bwd_ex / rac_msmv_v2_bwd_ex. */
 enum {
     RAC_OUT_SQCP = 0,  /* [S,Q,C,P]      -- the reference op's layout (msmv_sampling.cpp:170)      */
     RAC_OUT_BQGTPC = 1 /* [B,Q,G,T*P,C]  -- what sampling_4d returns after its regroup
@@ -460,6 +461,18 @@ int rac_msmv_bwd(const float *grad_out, const void *const *feats, const int32_t 
 int rac_msmv_v2_bwd(const float *grad_out, const void *const *feats, const int32_t *hw, int L, const float *loc,
                     const float *w, void *const *grad_feats, float *grad_loc, int S, int N, int Q, int P, int C,
                     int feat_layout, void *stream);
+/* rac_msmv_bwd / rac_msmv_v2_bwd with grad_out in layout `grad_layout` (T, G as rac_msmv_fwd): RAC_OUT_SQCP [S,Q,C,P], or
+ * RAC_OUT_BQGTPC [B,Q,G,T*P,C], slot s = (b*T+t)*G+g -- the tensor rac_msmv_fwd / rac_msmv_v2_fwd write for sampling_4d, read
+ * as it lies (no permute copy; at C = 64 a point's channels are one contiguous 256-byte row).  T >= 1 and G >= 1 always;
+ * under RAC_OUT_BQGTPC S must be a multiple of T*G.  Every other argument, and every result, as the entry point without _ex:
+ * grad_loc / grad_w bit-identical between the two layouts.  rac_msmv_bwd(...) is rac_msmv_bwd_ex(grad_out, RAC_OUT_SQCP, 1, 1,
+ * ...), likewise for v2. */
+int rac_msmv_bwd_ex(const float *grad_out, int grad_layout, int T, int G, const void *const *feats, const int32_t *hw, int L,
+                    const float *loc, const float *w, void *const *grad_feats, float *grad_loc, float *grad_w, int S, int N,
+                    int Q, int P, int C, void *stream);
+int rac_msmv_v2_bwd_ex(const float *grad_out, int grad_layout, int T, int G, const void *const *feats, const int32_t *hw,
+                       int L, const float *loc, const float *w, void *const *grad_feats, float *grad_loc, int S, int N, int Q,
+                       int P, int C, int feat_layout, void *stream);
 int rac_msda_bwd(const float *grad_out, const float *value, const int64_t *shapes, const int64_t *starts,
                  const float *loc, const float *attn, float *grad_value, float *grad_loc, float *grad_attn,
                  int bs, int keys, int heads, int dim, int Q, int L, int P, void *stream);

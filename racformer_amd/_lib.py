@@ -31,6 +31,8 @@ SIGNATURES = {
     "rac_msmv_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
     "rac_msmv_v2_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
     "rac_msmv_v2_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
+    "rac_msmv_bwd_ex": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "rac_msmv_v2_bwd_ex": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "rac_msda_bwd": (_i, [_vp] * 9 + [_i] * 7 + [_vp]),
     "rac_bev_pool_v2_fwd": (_i, [_vp] * 8 + [_i, _i, _vp]),
     "rac_bev_pool_v2_bwd": (_i, [_vp] * 10 + [_i, _i, _vp]),

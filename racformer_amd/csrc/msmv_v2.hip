@@ -12,6 +12,8 @@
 // Backward (fp32): grad_feat[l*][tap] += w_tap * grad_out (float atomics into a caller-zeroed buffer);
 //   grad_loc (u, v) = (W_l*-1 | H_l*-1) * sum_c grad_out[c] * d bilinear[c] / d(w|h), one writer per point (deterministic);
 //   grad_loc view = 0 (as rac_msmv_bwd); the weights get no gradient (argmax cuts the graph in the reference too).
+//   grad_out in either output layout (rac_msmv_v2_bwd_ex): [S,Q,C,P], or [B,Q,G,T*P,C] as the forward writes it for
+//   sampling_4d, where a point's 64 channels are one contiguous row (the C = 64 kernel's lanes read floats c + 16 j of it).
 //
 // Feature layouts: RAC_FEAT_CL [S,N,H,W,C] (the package's pyramid, what the decoder hands the op) and RAC_FEAT_CF
 // [S,C,N,H,W] (what the reference's torch path takes; fp32).
@@ -29,7 +31,7 @@ struct MsmvV2Args {
     int W[RAC_MAX_LEVELS];
     const float *loc;       // [S,Q,P,3]
     const float *w;         // [S,Q,P,L]
-    const float *grad_out;  // [S,Q,C,P]           (backward)
+    const float *grad_out;  // layout by T          (backward)
     float *out;             // layout by T          (forward)
     float *gloc;            // [S,Q,P,3]           (backward)
     int L, S, N, Q, P, C;
@@ -251,11 +253,12 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_c64_kernel(const MsmvV2Args a
     const int H = lv_.H, W = lv_.W;
     V2Taps t = v2_taps(lp[0], lp[1], H, W);
     float g[4];
-    {
-        const float *go = a.grad_out + (row * 64 + lane16) * a.P + p;
+    {   // channel c of the point at go + c * cs: BQGTPC one contiguous 64-float row, SQCP P floats apart
+        const size_t cs = a.T > 0 ? 1 : (size_t)a.P;
+        const float *go = a.grad_out + v2_out_index(a, row, p, lane16);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            g[j] = act ? go[(size_t)(16 * j) * a.P] : 0.f;
+            g[j] = act ? go[(size_t)(16 * j) * cs] : 0.f;
     }
     const size_t map = ((size_t)s * a.N + view) * H * W * 64 + lane16;
     const float *base = (const float *)lv_.feat + map;
@@ -311,8 +314,10 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_generic_kernel(const MsmvV2Ar
         const float tw[4] = {t.hh * t.hw, t.hh * t.lw, t.lh * t.hw, t.lh * t.lw};
         float sh = 0.f, sw_ = 0.f;
         if (t.in) {
+            const float *go = a.grad_out + v2_out_index(a, row, p, 0);
+            const size_t gs = a.T > 0 ? 1 : (size_t)a.P;
             for (int c = 0; c < a.C; ++c) {
-                const float g = a.grad_out[(row * a.C + c) * a.P + p];
+                const float g = go[(size_t)c * gs];
                 const size_t cc = (size_t)c * st.ch;
                 float v[4];
 #pragma unroll
@@ -401,23 +406,29 @@ extern "C" int rac_msmv_v2_fwd(const void *const *feats, const int32_t *hw, int 
     return rac_launch_status("rac_msmv_v2_fwd");
 }
 
-extern "C" int rac_msmv_v2_bwd(const float *grad_out, const void *const *feats, const int32_t *hw, int L, const float *loc,
-                               const float *w, void *const *grad_feats, float *grad_loc, int S, int N, int Q, int P, int C,
-                               int feat_layout, void *stream)
+static int msmv_v2_bwd_impl(const char *what, const float *grad_out, int grad_layout, int T, int G, const void *const *feats,
+                            const int32_t *hw, int L, const float *loc, const float *w, void *const *grad_feats, float *grad_loc,
+                            int S, int N, int Q, int P, int C, int feat_layout, void *stream)
 {
-    RAC_CHECK_ARG(L >= 1 && L <= RAC_MAX_LEVELS, "rac_msmv_v2_bwd: L=%d out of [1,%d]", L, RAC_MAX_LEVELS);
-    RAC_CHECK_ARG(S >= 0 && Q >= 0 && N >= 1 && C >= 1, "rac_msmv_v2_bwd: bad sizes S=%d N=%d Q=%d C=%d", S, N, Q, C);
-    RAC_CHECK_ARG(P >= 0 && P <= RAC_MAX_POINTS, "rac_msmv_v2_bwd: num_point exceed limits (P=%d > %d)", P, RAC_MAX_POINTS);
-    RAC_CHECK_ARG(feat_layout == RAC_FEAT_CL || feat_layout == RAC_FEAT_CF, "rac_msmv_v2_bwd: feature layout %d", feat_layout);
+    RAC_CHECK_ARG(L >= 1 && L <= RAC_MAX_LEVELS, "%s: L=%d out of [1,%d]", what, L, RAC_MAX_LEVELS);
+    RAC_CHECK_ARG(S >= 0 && Q >= 0 && N >= 1 && C >= 1, "%s: bad sizes S=%d N=%d Q=%d C=%d", what, S, N, Q, C);
+    RAC_CHECK_ARG(P >= 0 && P <= RAC_MAX_POINTS, "%s: num_point exceed limits (P=%d > %d)", what, P, RAC_MAX_POINTS);
+    RAC_CHECK_ARG(feat_layout == RAC_FEAT_CL || feat_layout == RAC_FEAT_CF, "%s: feature layout %d", what, feat_layout);
+    RAC_CHECK_ARG(grad_layout == RAC_OUT_SQCP || grad_layout == RAC_OUT_BQGTPC, "%s: gradient layout %d", what, grad_layout);
+    RAC_CHECK_ARG(T >= 1 && G >= 1, "%s: T=%d G=%d must be >= 1", what, T, G);
+    if (grad_layout == RAC_OUT_BQGTPC)
+        RAC_CHECK_ARG(S % (T * G) == 0, "%s: S=%d not a multiple of T*G=%d*%d", what, S, T, G);
     if (S == 0 || Q == 0 || P == 0)
         return 0;
-    RAC_CHECK_ARG(grad_out && grad_loc, "rac_msmv_v2_bwd: null pointer");
+    RAC_CHECK_ARG(grad_out && grad_loc, "%s: null pointer", what);
     MsmvV2Args a;
-    const int rc = v2_fill_args(a, "rac_msmv_v2_bwd", feats, grad_feats, true, hw, L, loc, w, S, N, Q, P, C, feat_layout);
+    const int rc = v2_fill_args(a, what, feats, grad_feats, true, hw, L, loc, w, S, N, Q, P, C, feat_layout);
     if (rc)
         return rc;
     a.grad_out = grad_out;
     a.gloc = grad_loc;
+    a.T = grad_layout == RAC_OUT_BQGTPC ? T : 0;
+    a.G = grad_layout == RAC_OUT_BQGTPC ? G : 1;
     hipStream_t st = (hipStream_t)stream;
     const long npts = (long)S * Q * P;
     if (C == 64 && feat_layout == RAC_FEAT_CL) {
@@ -427,5 +438,21 @@ extern "C" int rac_msmv_v2_bwd(const float *grad_out, const void *const *feats, 
         const unsigned nb = (unsigned)((npts + 255) / 256 > 4096 ? 4096 : (npts + 255) / 256);
         hipLaunchKernelGGL(msmv_v2_bwd_generic_kernel, dim3(nb), dim3(256), 0, st, a);
     }
-    return rac_launch_status("rac_msmv_v2_bwd");
+    return rac_launch_status(what);
+}
+
+extern "C" int rac_msmv_v2_bwd_ex(const float *grad_out, int grad_layout, int T, int G, const void *const *feats,
+                                  const int32_t *hw, int L, const float *loc, const float *w, void *const *grad_feats,
+                                  float *grad_loc, int S, int N, int Q, int P, int C, int feat_layout, void *stream)
+{
+    return msmv_v2_bwd_impl("rac_msmv_v2_bwd_ex", grad_out, grad_layout, T, G, feats, hw, L, loc, w, grad_feats, grad_loc, S, N,
+                            Q, P, C, feat_layout, stream);
+}
+
+extern "C" int rac_msmv_v2_bwd(const float *grad_out, const void *const *feats, const int32_t *hw, int L, const float *loc,
+                               const float *w, void *const *grad_feats, float *grad_loc, int S, int N, int Q, int P, int C,
+                               int feat_layout, void *stream)
+{
+    return msmv_v2_bwd_impl("rac_msmv_v2_bwd", grad_out, RAC_OUT_SQCP, 1, 1, feats, hw, L, loc, w, grad_feats, grad_loc, S, N, Q,
+                            P, C, feat_layout, stream);
 }

@@ -59,6 +59,31 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, a
     return out
 
 
+def _msda_bwd_launch(grad_output, value, shapes, starts, loc, attn):
+    """rac_msda_bwd with the level tables already on the host -> (grad_value, grad_loc, grad_attn)"""
+    bs, keys, heads, dim = value.shape
+    _, Q, _, L, P, _ = loc.shape
+    grad_output = grad_output.contiguous().float()
+    grad_value = torch.zeros_like(value)
+    grad_loc, grad_attn = torch.empty_like(loc), torch.empty_like(attn)
+    rc = _lib.lib().rac_msda_bwd(_lib.ptr(grad_output), _lib.ptr(value), shapes, starts, _lib.ptr(loc), _lib.ptr(attn),
+                                 _lib.ptr(grad_value), _lib.ptr(grad_loc), _lib.ptr(grad_attn), bs, keys, heads, dim,
+                                 Q, L, P, _lib.stream_ptr())
+    _lib.check(rc, "rac_msda_bwd")
+    return grad_value, grad_loc, grad_attn
+
+
+def msda_backward(grad_output, value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
+    """rac_msda_bwd for the operands of an ``msda_forward`` call -> (grad_value, grad_sampling_locations,
+    grad_attention_weights).  float32 values only (the reference's backward is fp32 too)."""
+    grad_output = grad_output.contiguous()      # (autograd hands in whatever layout the consumer's backward produced)
+    _lib.require_gpu(grad_output, value, sampling_locations, attention_weights, what="ms_deform_attn backward")
+    if value.dtype != torch.float32:
+        raise RuntimeError(f"ms_deform_attn backward: float32 values only, got {value.dtype}")
+    (shapes, _), (starts, _) = _host_i64(spatial_shapes), _host_i64(level_start_index)
+    return _msda_bwd_launch(grad_output, value, shapes, starts, sampling_locations, attention_weights)
+
+
 class MultiScaleDeformableAttnFunction_fp32(torch.autograd.Function):
     """apply(value, value_spatial_shapes, value_level_start_index, sampling_locations,
     attention_weights, im2col_step) -> [bs, num_queries, embed_dims]; inputs are cast to float32
@@ -83,15 +108,7 @@ class MultiScaleDeformableAttnFunction_fp32(torch.autograd.Function):
         multi_scale_deformable_attn_function.py:130-162."""
         value, loc, attn = ctx.saved_tensors
         (shapes, _), (starts, _) = ctx.levels
-        bs, keys, heads, dim = value.shape
-        _, Q, _, L, P, _ = loc.shape
-        grad_output = grad_output.contiguous().float()
-        grad_value = torch.zeros_like(value)
-        grad_loc, grad_attn = torch.empty_like(loc), torch.empty_like(attn)
-        rc = _lib.lib().rac_msda_bwd(_lib.ptr(grad_output), _lib.ptr(value), shapes, starts, _lib.ptr(loc), _lib.ptr(attn),
-                                     _lib.ptr(grad_value), _lib.ptr(grad_loc), _lib.ptr(grad_attn), bs, keys, heads, dim,
-                                     Q, L, P, _lib.stream_ptr())
-        _lib.check(rc, "rac_msda_bwd")
+        grad_value, grad_loc, grad_attn = _msda_bwd_launch(grad_output, value, shapes, starts, loc, attn)
         return grad_value, None, None, grad_loc, grad_attn, None
 
 

@@ -63,9 +63,23 @@ def msmv_forward(mlvl_feats, sampling_locations, scale_weights, out_layout=_lib.
     return out
 
 
-def msmv_backward(grad_output, mlvl_feats, sampling_locations, scale_weights):
-    """rac_msmv_bwd: -> (grad_feats (list), grad_sampling_locations, grad_scale_weights), the tuple the
-    reference's ``_ms_deform_attn_cuda_*_backward`` returns (msmv_sampling.cpp:302-497).  fp32 only."""
+def _grad_shape(grad_layout, S, Q, C, P, num_frames, num_groups, what):
+    """the shape a gradient in ``grad_layout`` must have (the forward's output shape in that layout)"""
+    if grad_layout == _lib.OUT_SQCP:
+        return (S, Q, C, P)
+    if grad_layout != _lib.OUT_BQGTPC:
+        raise RuntimeError(f"{what}: unknown gradient layout {grad_layout}")
+    if num_frames < 1 or num_groups < 1 or S % (num_frames * num_groups):
+        raise RuntimeError(f"{what}: B'={S} is not a multiple of num_frames*num_groups={num_frames}*{num_groups}")
+    return (S // (num_frames * num_groups), Q, num_groups, num_frames * P, C)
+
+
+def msmv_backward(grad_output, mlvl_feats, sampling_locations, scale_weights, grad_layout=_lib.OUT_SQCP, num_frames=1,
+                  num_groups=1):
+    """rac_msmv_bwd_ex: -> (grad_feats (list), grad_sampling_locations, grad_scale_weights), the tuple the
+    reference's ``_ms_deform_attn_cuda_*_backward`` returns (msmv_sampling.cpp:302-497).  fp32 only.
+    ``grad_layout=OUT_BQGTPC``: ``grad_output`` is ``[B, Q, G, T*P, C]`` (what msmv_forward writes with that layout), read as it
+    lies; the results are those of the permuted [B', Q, C, P] gradient."""
     feats = list(mlvl_feats)
     L = len(feats)
     grad_output = grad_output.contiguous()
@@ -74,16 +88,19 @@ def msmv_backward(grad_output, mlvl_feats, sampling_locations, scale_weights):
         raise RuntimeError("msmv_sampling backward: float32 features only")
     S, N, _, _, C = feats[0].shape
     _, Q, P, _ = sampling_locations.shape
+    want = _grad_shape(grad_layout, S, Q, C, P, num_frames, num_groups, "msmv_sampling backward")
+    if tuple(grad_output.shape) != want:
+        raise RuntimeError(f"msmv_sampling backward: grad_output must be {list(want)}, got {list(grad_output.shape)}")
     grad_feats = [torch.zeros_like(f) for f in feats]
     grad_loc = torch.empty_like(sampling_locations)
     grad_w = torch.empty_like(scale_weights)
     ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
     gptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in grad_feats])
     hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[2:4]])
-    rc = _lib.lib().rac_msmv_bwd(_lib.ptr(grad_output), ptrs, hw, L, _lib.ptr(sampling_locations),
-                                 _lib.ptr(scale_weights), gptrs, _lib.ptr(grad_loc), _lib.ptr(grad_w), S, N, Q, P, C,
-                                 _lib.stream_ptr())
-    _lib.check(rc, "rac_msmv_bwd")
+    rc = _lib.lib().rac_msmv_bwd_ex(_lib.ptr(grad_output), grad_layout, num_frames, num_groups, ptrs, hw, L,
+                                    _lib.ptr(sampling_locations), _lib.ptr(scale_weights), gptrs, _lib.ptr(grad_loc),
+                                    _lib.ptr(grad_w), S, N, Q, P, C, _lib.stream_ptr())
+    _lib.check(rc, "rac_msmv_bwd_ex")
     return grad_feats, grad_loc, grad_w
 
 
@@ -181,9 +198,11 @@ def msmv_v2_forward(mlvl_feats, sampling_locations, scale_weights, out_layout=_l
     return out
 
 
-def msmv_v2_backward(grad_output, mlvl_feats, sampling_locations, scale_weights, channels_first=False):
-    """rac_msmv_v2_bwd: -> (grad_feats (list, only the chosen levels' taps non-zero), grad_sampling_locations with a zero
-    view component).  The weights get no gradient: argmax cuts the graph, as in the reference.  fp32 only."""
+def msmv_v2_backward(grad_output, mlvl_feats, sampling_locations, scale_weights, channels_first=False,
+                     grad_layout=_lib.OUT_SQCP, num_frames=1, num_groups=1):
+    """rac_msmv_v2_bwd_ex: -> (grad_feats (list, only the chosen levels' taps non-zero), grad_sampling_locations with a zero
+    view component).  The weights get no gradient: argmax cuts the graph, as in the reference.  fp32 only.
+    ``grad_layout`` / ``num_frames`` / ``num_groups``: as msmv_backward."""
     feats = list(mlvl_feats)
     L = len(feats)
     grad_output = grad_output.contiguous()
@@ -191,16 +210,17 @@ def msmv_v2_backward(grad_output, mlvl_feats, sampling_locations, scale_weights,
     if any(f.dtype != torch.float32 for f in feats):
         raise RuntimeError("msmv_sampling_v2 backward: float32 features only")
     S, N, C, Q, P, hw = _v2_shapes(feats, sampling_locations, scale_weights, channels_first, "msmv_sampling_v2 backward")
-    if tuple(grad_output.shape) != (S, Q, C, P):
-        raise RuntimeError(f"msmv_sampling_v2 backward: grad_output must be [B', Q, C, P], got {tuple(grad_output.shape)}")
+    want = _grad_shape(grad_layout, S, Q, C, P, num_frames, num_groups, "msmv_sampling_v2 backward")
+    if tuple(grad_output.shape) != want:
+        raise RuntimeError(f"msmv_sampling_v2 backward: grad_output must be {list(want)}, got {list(grad_output.shape)}")
     grad_feats = [torch.zeros_like(f) for f in feats]
     grad_loc = torch.empty_like(sampling_locations)
     ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
     gptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in grad_feats])
-    rc = _lib.lib().rac_msmv_v2_bwd(_lib.ptr(grad_output), ptrs, hw, L, _lib.ptr(sampling_locations),
-                                    _lib.ptr(scale_weights), gptrs, _lib.ptr(grad_loc), S, N, Q, P, C,
-                                    _lib.FEAT_CF if channels_first else _lib.FEAT_CL, _lib.stream_ptr())
-    _lib.check(rc, "rac_msmv_v2_bwd")
+    rc = _lib.lib().rac_msmv_v2_bwd_ex(_lib.ptr(grad_output), grad_layout, num_frames, num_groups, ptrs, hw, L,
+                                       _lib.ptr(sampling_locations), _lib.ptr(scale_weights), gptrs, _lib.ptr(grad_loc), S, N,
+                                       Q, P, C, _lib.FEAT_CF if channels_first else _lib.FEAT_CL, _lib.stream_ptr())
+    _lib.check(rc, "rac_msmv_v2_bwd_ex")
     return grad_feats, grad_loc
 
 

@@ -33,8 +33,8 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act
                     pack_gemm_split_weight,
                     pe_head, refine_fused, row_gemm,
                     row_seg, rowgemm_launch, sampling4d_fused, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
-from .msda import msda_forward
-from .msmv import msmv_forward, msmv_v2_forward
+from .msda import msda_backward, msda_forward
+from .msmv import msmv_backward, msmv_forward, msmv_v2_backward, msmv_v2_forward
 
 try:  # registry decorators are applied only if mmdet happens to be importable
     from mmdet.models.utils.builder import TRANSFORMER as _TRANSFORMER
@@ -290,6 +290,48 @@ class RaCFormerSampling(nn.Module):
         return res
 
 
+class _Sampling4DGather(torch.autograd.Function):
+    """The gather of sampling_4d: apply(aggregate, T, G, loc [S,Q,P,3], w [S,Q,P,L], *feats) -> [B,Q,G,T*P,C].  The forward
+    writes that layout directly (rac_msmv_fwd / rac_msmv_v2_fwd) and the backward reads the incoming gradient in the same
+    layout (rac_msmv_bwd_ex / rac_msmv_v2_bwd_ex): no permute copy either way.  aggregate: gradients for the locations
+    (view component 0), the weights and every level; hard level: the locations and the features, None for the weights (argmax
+    cuts the graph, as in the reference).  The launchers are looked up as this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, aggregate, T, G, loc, w, *feats):
+        ctx.aggregate, ctx.T, ctx.G = aggregate, T, G
+        ctx.save_for_backward(loc, w, *feats)
+        launch = msmv_forward if aggregate else msmv_v2_forward
+        return launch(feats, loc, w, out_layout=_lib.OUT_BQGTPC, num_frames=T, num_groups=G)
+
+    @staticmethod
+    def backward(ctx, grad_final):
+        loc, w, *feats = ctx.saved_tensors
+        kw = dict(grad_layout=_lib.OUT_BQGTPC, num_frames=ctx.T, num_groups=ctx.G)
+        if ctx.aggregate:
+            grad_feats, grad_loc, grad_w = msmv_backward(grad_final.contiguous(), feats, loc, w, **kw)
+        else:
+            (grad_feats, grad_loc), grad_w = msmv_v2_backward(grad_final.contiguous(), feats, loc, w, **kw), None
+        return (None, None, None, grad_loc, grad_w, *grad_feats)
+
+
+class _BEVAttendGather(torch.autograd.Function):
+    """The MSDA gather of BEVSelfAttention.attend: apply(value, loc, attn, shapes) -> [B*T,Q,C], msda_forward as it was called
+    before (no im2col_step check, no cast) and rac_msda_bwd behind it (float32 values)."""
+
+    @staticmethod
+    def forward(ctx, value, loc, attn, shapes):
+        ctx.shapes = shapes
+        ctx.save_for_backward(value, loc, attn)
+        return msda_forward(value, shapes, [0], loc, attn)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        value, loc, attn = ctx.saved_tensors
+        grad_value, grad_loc, grad_attn = msda_backward(grad_out, value, ctx.shapes, [0], loc, attn)
+        return grad_value, grad_loc, grad_attn, None
+
+
 def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, image_w, aggregate=True,
                 eps=1e-5, loc_tap=None, view_in=None):
     """sparsebev_sampling.py:28-134 on the HIP msmv operator.
@@ -298,7 +340,9 @@ def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, im
     selection and the (b,g,t)-vs-(b,t,g) weight slot order (:113-120) are as in the reference.
     ``aggregate=False`` (:125-134): every point is sampled on its argmax-weight level only (msmv_sampling_v2, rac_msmv_v2_fwd)
     and the result is (final [B,Q,G,T*P,C], homo[:,0] [B,N,Q,G*P,1] -- the first frame's raw camera depth, before the eps
-    clamp --, i_view[:,0] [B,Q,G*P,1] int64 -- the camera sampled, the imposed one under ``view_in``)."""
+    clamp --, i_view[:,0] [B,Q,G*P,1] int64 -- the camera sampled, the imposed one under ``view_in``).
+    Differentiable in both modes (float32 features): the gather is _Sampling4DGather, the projection and selection torch ops,
+    so gradients reach sample_points, the features, scale_weights (aggregate mode only) and lidar2img if it requires grad."""
     B, Q, T, G, P, _ = sample_points.shape
     N = lidar2img.shape[1] // T
     m = lidar2img.view(B, T, N, 1, 1, 4, 4)
@@ -323,10 +367,10 @@ def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, im
         loc_tap.append(own.view(B, T, Q, G, P, 3).permute(0, 1, 3, 2, 4, 5).reshape(B * T * G, Q, P, 3))
     L = scale_weights.shape[-1]
     w = scale_weights.reshape(B, Q, G, T, P, L).permute(0, 2, 3, 1, 4, 5).reshape(B * G * T, Q, P, L).contiguous()
+    final = _Sampling4DGather.apply(bool(aggregate), T, G, loc, w, *mlvl_feats)
     if not aggregate:
-        final = msmv_v2_forward(mlvl_feats, loc, w, out_layout=_lib.OUT_BQGTPC, num_frames=T, num_groups=G)
         return final, homo[:, 0, ..., None], i_view[:, 0, 0, ..., None]
-    return msmv_forward(mlvl_feats, loc, w, out_layout=_lib.OUT_BQGTPC, num_frames=T, num_groups=G)
+    return final
 
 
 # ------------------------------------------------------------------------------- BEV branch
@@ -658,7 +702,7 @@ class BEVSelfAttention(nn.Module):
             .reshape(B * T, Q, Hn, self.num_levels, P, 2).contiguous()
         aw = attention_weights.view(B, Q, Hn, T, self.num_levels, P).permute(3, 0, 1, 2, 4, 5) \
             .reshape(B * T, Q, Hn, self.num_levels, P).contiguous()
-        out = msda_forward(value, [list(spatial_shapes)], [0], loc, aw)                   # [B*T,Q,C]
+        out = _BEVAttendGather.apply(value, loc, aw, [list(spatial_shapes)])              # [B*T,Q,C]
         out = out.permute(1, 2, 0).reshape(Q, C, B, T)
         if self.queue_weight:
             qw = self.bev_queue_weight(query).permute(1, 0, 2).reshape(Q, 1, B, T)

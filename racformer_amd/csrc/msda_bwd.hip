@@ -12,7 +12,7 @@
 // value scatter uses atomics.  Round 4: lane c of a group owns channels c + 16 j (not 4c .. 4c+3), so that every atomic
 // instruction adds whole 64-byte segments (see msmv_bwd.hip).
 // The caller zero-fills grad_value; grad_loc / grad_attn are fully overwritten.
-#include "rac_common.h"
+#include "gather_device.h"
 
 struct MsdaBwdArgs {
     const float *grad_out;  // [bs,Q,heads*dim]
@@ -24,14 +24,6 @@ struct MsdaBwdArgs {
     long start[RAC_MAX_LEVELS];
     int bs, keys, heads, dim, Q, L, P;
 };
-
-__device__ __forceinline__ float db_group_sum16(float v)
-{
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 16);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void msda_bwd_d64_kernel(const MsdaBwdArgs a)
 {
@@ -52,19 +44,14 @@ __global__ __launch_bounds__(256) void msda_bwd_d64_kernel(const MsdaBwdArgs a)
     for (int j = 0; j < 4; ++j)
         g[j] = act ? a.grad_out[item * 64 + 16 * j + lane16] : 0.f;
     const int H = a.H[l], W = a.W[l];
-    const float h_im = y * (float)H - 0.5f, w_im = x * (float)W - 0.5f;
-    const bool in = act && h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-    // outside the guard the footprint is pinned to (0, 0): a NaN / inf coordinate would make the tap weights NaN, and
-    // NaN times the zero taps would reach grad_attn / grad_loc
-    const float hf = in ? floorf(h_im) : 0.f, wf = in ? floorf(w_im) : 0.f;
-    const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-    const float lh = in ? h_im - hf : 0.f, lw = in ? w_im - wf : 0.f, hh = 1.f - lh, hw = 1.f - lw;
+    const RacFootprint f = rac_footprint(y * (float)H - 0.5f, x * (float)W - 0.5f, H, W);
+    const int h_low = f.h_low, w_low = f.w_low, h_high = h_low + 1, w_high = w_low + 1;
+    const float lh = f.lh, lw = f.lw, hh = f.hh, hw = f.hw;
     const int stride = a.heads * 64;
     const size_t map = (((size_t)b * a.keys + a.start[l]) * a.heads + h) * 64 + lane16;
     const float *base = a.value + map;
     float *gbase = a.gvalue + map;
-    const bool ok[4] = {in && h_low >= 0 && w_low >= 0, in && h_low >= 0 && w_high <= W - 1,
-                        in && h_high <= H - 1 && w_low >= 0, in && h_high <= H - 1 && w_high <= W - 1};
+    const bool ok[4] = {act && f.ok[0], act && f.ok[1], act && f.ok[2], act && f.ok[3]};
     const size_t o[4] = {((size_t)h_low * W + w_low) * stride, ((size_t)h_low * W + w_high) * stride,
                          ((size_t)h_high * W + w_low) * stride, ((size_t)h_high * W + w_high) * stride};
     const float tw[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
@@ -86,9 +73,9 @@ __global__ __launch_bounds__(256) void msda_bwd_d64_kernel(const MsdaBwdArgs a)
         sh += dh[t] * dot;
         sw_ += dw[t] * dot;
     }
-    sv = db_group_sum16(sv);
-    sh = db_group_sum16(sh);
-    sw_ = db_group_sum16(sw_);
+    sv = rac_group_sum16(sv);
+    sh = rac_group_sum16(sh);
+    sw_ = rac_group_sum16(sw_);
     if (act && lane16 == 0) {
         a.gattn[sc] = sv;
         a.gloc[sc * 2] = (float)W * sw_ * at;
@@ -107,19 +94,17 @@ __global__ __launch_bounds__(256) void msda_bwd_generic_kernel(const MsdaBwdArgs
         const int b = (int)(item / ((long)a.heads * a.Q));
         const float x = a.loc[sc * 2], y = a.loc[sc * 2 + 1], at = a.attn[sc];
         const int H = a.H[l], W = a.W[l];
-        const float h_im = y * (float)H - 0.5f, w_im = x * (float)W - 0.5f;
+        const RacFootprint f = rac_footprint(y * (float)H - 0.5f, x * (float)W - 0.5f, H, W);
         float sv = 0.f, sh = 0.f, sw_ = 0.f;
-        if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
-            const float hf = floorf(h_im), wf = floorf(w_im);
-            const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-            const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
+        if (f.in) {
+            const int h_low = f.h_low, w_low = f.w_low, h_high = h_low + 1, w_high = w_low + 1;
+            const float lh = f.lh, lw = f.lw, hh = f.hh, hw = f.hw;
             const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
             const int stride = a.heads * a.dim;
             const size_t map = (((size_t)b * a.keys + a.start[l]) * a.heads + h) * a.dim;
             const float *base = a.value + map;
             float *gbase = a.gvalue + map;
-            const bool ok1 = h_low >= 0 && w_low >= 0, ok2 = h_low >= 0 && w_high <= W - 1;
-            const bool ok3 = h_high <= H - 1 && w_low >= 0, ok4 = h_high <= H - 1 && w_high <= W - 1;
+            const bool ok1 = f.ok[0], ok2 = f.ok[1], ok3 = f.ok[2], ok4 = f.ok[3];
             const size_t o1 = ((size_t)h_low * W + w_low) * stride, o2 = ((size_t)h_low * W + w_high) * stride;
             const size_t o3 = ((size_t)h_high * W + w_low) * stride, o4 = ((size_t)h_high * W + w_high) * stride;
             for (int c = 0; c < a.dim; ++c) {

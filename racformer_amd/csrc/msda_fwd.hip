@@ -14,7 +14,7 @@
 // offsets + four weights), the taps are buffer-descriptor loads whose range check zero-fills taps outside the map,
 // the accumulation is packed FMAs; blocks are mapped so that all workgroups of one BEV frame (one `bs` index,
 // 16.8 MB of value) run on one XCD.
-#include "rac_common.h"
+#include "gather_device.h"
 
 struct MsdaArgs {
     const void *value;
@@ -29,28 +29,6 @@ struct MsdaArgs {
 };
 
 #define MSDA_ITEMS 16 /* items per 256-thread workgroup: 4 waves x 4 sixteen-lane groups */
-
-#define MSDA_TAP_OUTSIDE 0x80000000u   /* tap offset past the end of the value buffer: the buffer load returns zeros */
-typedef float msda_f2 __attribute__((ext_vector_type(2)));
-typedef unsigned int msda_u2 __attribute__((ext_vector_type(2)));
-typedef unsigned int msda_u4 __attribute__((ext_vector_type(4)));
-
-// Four channels of one tap through a buffer descriptor: its range check stands in for the four branches of the bilinear
-// footprint (a tap outside the map carries the offset MSDA_TAP_OUTSIDE and reads as zero).
-template <typename FT>
-__device__ __forceinline__ rac_f4 msda_tap(__amdgpu_buffer_rsrc_t rsrc, unsigned off);
-template <>
-__device__ __forceinline__ rac_f4 msda_tap<float>(__amdgpu_buffer_rsrc_t rsrc, unsigned off)
-{
-    return __builtin_bit_cast(rac_f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
-}
-template <>
-__device__ __forceinline__ rac_f4 msda_tap<unsigned short>(__amdgpu_buffer_rsrc_t rsrc, unsigned off)
-{
-    const msda_u2 r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);    // 4 x bf16
-    return (rac_f4){__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
-                    __uint_as_float(r.y & 0xffff0000u)};
-}
 
 template <typename FT>
 __global__ __launch_bounds__(256) void msda_fwd_d64_kernel(const MsdaArgs a)
@@ -72,14 +50,14 @@ __global__ __launch_bounds__(256) void msda_fwd_d64_kernel(const MsdaArgs a)
     const int nitems = min(MSDA_ITEMS, per_b - i0);
     const size_t item0 = (size_t)b * per_b + i0;
 
-    // tap table [items][LPp][8]: per point 4 tap byte offsets into the value buffer (MSDA_TAP_OUTSIDE = outside the map) and 4
+    // tap table [items][LPp][8]: per point 4 tap byte offsets into the value buffer (RAC_TAP_OUTSIDE = outside the map) and 4
     // bilinear weights with the attention weight folded in -- one thread per point builds it from the op's location / weight
     // rows, instead of each of the 16 lanes that gather the point
     float *stab = smem;
     const unsigned key_bytes = (unsigned)(a.heads * 64 * sizeof(FT));       // one key: heads x 64 channels
     for (int i = tid; i < nitems * LPp; i += 256) {
         const int it = i / LPp, lp = i - it * LPp;
-        msda_u4 off = {MSDA_TAP_OUTSIDE, MSDA_TAP_OUTSIDE, MSDA_TAP_OUTSIDE, MSDA_TAP_OUTSIDE};
+        rac_u4 off = {RAC_TAP_OUTSIDE, RAC_TAP_OUTSIDE, RAC_TAP_OUTSIDE, RAC_TAP_OUTSIDE};
         rac_f4 w4 = {0.f, 0.f, 0.f, 0.f};
         if (lp < LP) {
             const int l = lp / a.P;
@@ -87,22 +65,17 @@ __global__ __launch_bounds__(256) void msda_fwd_d64_kernel(const MsdaArgs a)
             const float *gl = a.loc + ((item0 + it) * LP + lp) * 2;
             const float x = gl[0], y = gl[1];
             const float at = a.attn[(item0 + it) * LP + lp];
-            const float h_im = y * (float)H - 0.5f, w_im = x * (float)W - 0.5f;
-            const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-            const float hf = floorf(h_im), wf = floorf(w_im);
-            const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-            const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-            const bool t_ok = in && h_low >= 0, b_ok = in && h_high <= H - 1;
-            const bool l_ok = w_low >= 0, r_ok = w_high <= W - 1;
+            const RacFootprint f = rac_footprint(y * (float)H - 0.5f, x * (float)W - 0.5f, H, W);
+            const int h_low = f.h_low, w_low = f.w_low, h_high = h_low + 1, w_high = w_low + 1;
             const int h = (i0 + it) % a.heads;
             const unsigned base = ((unsigned)((long)b * a.keys + a.start[l]) * (unsigned)a.heads + (unsigned)h) * (unsigned)(64 * sizeof(FT));
-            off.x = t_ok && l_ok ? base + (unsigned)(h_low * W + w_low) * key_bytes : MSDA_TAP_OUTSIDE;
-            off.y = t_ok && r_ok ? base + (unsigned)(h_low * W + w_high) * key_bytes : MSDA_TAP_OUTSIDE;
-            off.z = b_ok && l_ok ? base + (unsigned)(h_high * W + w_low) * key_bytes : MSDA_TAP_OUTSIDE;
-            off.w = b_ok && r_ok ? base + (unsigned)(h_high * W + w_high) * key_bytes : MSDA_TAP_OUTSIDE;
-            w4 = (rac_f4){hh * hw * at, hh * lw * at, lh * hw * at, lh * lw * at};
+            off.x = f.ok[0] ? base + (unsigned)(h_low * W + w_low) * key_bytes : RAC_TAP_OUTSIDE;
+            off.y = f.ok[1] ? base + (unsigned)(h_low * W + w_high) * key_bytes : RAC_TAP_OUTSIDE;
+            off.z = f.ok[2] ? base + (unsigned)(h_high * W + w_low) * key_bytes : RAC_TAP_OUTSIDE;
+            off.w = f.ok[3] ? base + (unsigned)(h_high * W + w_high) * key_bytes : RAC_TAP_OUTSIDE;
+            w4 = (rac_f4){f.hh * f.hw * at, f.hh * f.lw * at, f.lh * f.hw * at, f.lh * f.lw * at};
         }
-        *reinterpret_cast<msda_u4 *>(stab + i * 8) = off;
+        *reinterpret_cast<rac_u4 *>(stab + i * 8) = off;
         *reinterpret_cast<rac_f4 *>(stab + i * 8 + 4) = w4;
     }
     __syncthreads();
@@ -116,12 +89,12 @@ __global__ __launch_bounds__(256) void msda_fwd_d64_kernel(const MsdaArgs a)
         rac_f4 v[4][4], tw[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const msda_u4 o = *reinterpret_cast<const msda_u4 *>(e + (p0 + k) * 8);
+            const rac_u4 o = *reinterpret_cast<const rac_u4 *>(e + (p0 + k) * 8);
             tw[k] = *reinterpret_cast<const rac_f4 *>(e + (p0 + k) * 8 + 4);
-            v[k][0] = msda_tap<FT>(rsrc, o.x + lane_off);
-            v[k][1] = msda_tap<FT>(rsrc, o.y + lane_off);
-            v[k][2] = msda_tap<FT>(rsrc, o.z + lane_off);
-            v[k][3] = msda_tap<FT>(rsrc, o.w + lane_off);
+            v[k][0] = rac_tap<FT>(rsrc, o.x + lane_off);
+            v[k][1] = rac_tap<FT>(rsrc, o.y + lane_off);
+            v[k][2] = rac_tap<FT>(rsrc, o.z + lane_off);
+            v[k][3] = rac_tap<FT>(rsrc, o.w + lane_off);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -136,13 +109,6 @@ __global__ __launch_bounds__(256) void msda_fwd_d64_kernel(const MsdaArgs a)
     rac_acc4_get(acc4, r.x, r.y, r.z, r.w);
     *reinterpret_cast<rac_f4 *>(a.out + (item0 + grp) * 64 + c4 * 4) = r;
 }
-
-template <typename FT>
-__device__ __forceinline__ float msda_ld1(const FT *p);
-template <>
-__device__ __forceinline__ float msda_ld1<float>(const float *p) { return *p; }
-template <>
-__device__ __forceinline__ float msda_ld1<unsigned short>(const unsigned short *p) { return rac_bf16_to_f32(*p); }
 
 template <typename FT>
 __global__ __launch_bounds__(256) void msda_fwd_generic_kernel(const MsdaArgs a)
@@ -164,18 +130,16 @@ __global__ __launch_bounds__(256) void msda_fwd_generic_kernel(const MsdaArgs a)
             const FT *base = (const FT *)a.value + (((size_t)b * a.keys + a.start[l]) * a.heads + h) * a.dim + c;
             for (int p = 0; p < a.P; ++p) {
                 const float x = lp[(l * a.P + p) * 2], y = lp[(l * a.P + p) * 2 + 1];
-                const float h_im = y * (float)H - 0.5f, w_im = x * (float)W - 0.5f;
-                if (!(h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W))
+                const RacFootprint f = rac_footprint(y * (float)H - 0.5f, x * (float)W - 0.5f, H, W);
+                if (!f.in)
                     continue;
-                const float hf = floorf(h_im), wf = floorf(w_im);
-                const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-                const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
+                const int h_low = f.h_low, w_low = f.w_low, h_high = h_low + 1, w_high = w_low + 1;
                 float v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f;
-                if (h_low >= 0 && w_low >= 0) v1 = msda_ld1(base + ((long)h_low * W + w_low) * stride);
-                if (h_low >= 0 && w_high <= W - 1) v2 = msda_ld1(base + ((long)h_low * W + w_high) * stride);
-                if (h_high <= H - 1 && w_low >= 0) v3 = msda_ld1(base + ((long)h_high * W + w_low) * stride);
-                if (h_high <= H - 1 && w_high <= W - 1) v4 = msda_ld1(base + ((long)h_high * W + w_high) * stride);
-                acc += (hh * hw * v1 + hh * lw * v2 + lh * hw * v3 + lh * lw * v4) * ap[l * a.P + p];
+                if (f.ok[0]) v1 = rac_ld1(base + ((long)h_low * W + w_low) * stride);
+                if (f.ok[1]) v2 = rac_ld1(base + ((long)h_low * W + w_high) * stride);
+                if (f.ok[2]) v3 = rac_ld1(base + ((long)h_high * W + w_low) * stride);
+                if (f.ok[3]) v4 = rac_ld1(base + ((long)h_high * W + w_high) * stride);
+                acc += (f.hh * f.hw * v1 + f.hh * f.lw * v2 + f.lh * f.hw * v3 + f.lh * f.lw * v4) * ap[l * a.P + p];
             }
         }
         a.out[idx] = acc;
@@ -213,7 +177,7 @@ extern "C" int rac_msda_fwd(const void *value, const int64_t *shapes, const int6
     const size_t lds = (size_t)MSDA_ITEMS * ((L * P + 3) & ~3) * 8 * sizeof(float);
     const size_t value_bytes = (size_t)bs * keys * heads * dim * (dtype == RAC_F32 ? 4 : 2);
     a.value_bytes = (unsigned)value_bytes;
-    if (dim == 64 && P >= 1 && lds <= 64 * 1024 && value_bytes < (size_t)MSDA_TAP_OUTSIDE) {   // (larger values: 31-bit tap offsets do not reach)
+    if (dim == 64 && P >= 1 && lds <= 64 * 1024 && value_bytes < (size_t)RAC_TAP_OUTSIDE) {   // (larger values: 31-bit tap offsets do not reach)
         const int nb = 8 * ((bs + 7) / 8) * a.blocks_per_b;
         if (dtype == RAC_F32)
             hipLaunchKernelGGL(msda_fwd_d64_kernel<float>, dim3(nb), dim3(256), lds, st, a);

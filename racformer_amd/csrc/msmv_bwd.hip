@@ -20,47 +20,11 @@
 // 256-byte row at C = 64: lane c of a group reads floats c + 16 j of it, four whole 64-byte segments per instruction.
 // Only the index of grad_out depends on the layout; every sum is formed in the same order, so grad_loc / grad_weight are
 // bit-identical between the two layouts.
-#include "rac_common.h"
-
-struct MsmvBwdArgs {
-    const void *feat[RAC_MAX_LEVELS];
-    float *gfeat[RAC_MAX_LEVELS];
-    int H[RAC_MAX_LEVELS];
-    int W[RAC_MAX_LEVELS];
-    const float *grad_out;  // [S,Q,C,P], or [B,Q,G,T*P,C] when T > 0
-    const float *loc;       // [S,Q,P,3]
-    const float *w;         // [S,Q,P,L]
-    float *gloc;            // [S,Q,P,3]
-    float *gw;              // [S,Q,P,L]
-    int L, S, N, Q, P, C;
-    int T, G;               // T > 0: grad_out is RAC_OUT_BQGTPC, slot s = (b*T + t)*G + g
-};
-
-// grad_out of point (row = s*Q + q, p): index of channel 0 and the distance between consecutive channels
-__device__ __forceinline__ void mb_gout_row(const MsmvBwdArgs &a, long row, int p, size_t &base, size_t &cstride)
-{
-    if (a.T > 0) {   // RAC_OUT_BQGTPC
-        const int s = (int)(row / a.Q), q = (int)(row % a.Q);
-        const int g = s % a.G, t = (s / a.G) % a.T, b = s / (a.G * a.T);
-        base = ((((size_t)b * a.Q + q) * a.G + g) * a.T + t) * a.P * a.C + (size_t)p * a.C;
-        cstride = 1;
-    } else {         // RAC_OUT_SQCP
-        base = (size_t)row * a.C * a.P + p;
-        cstride = (size_t)a.P;
-    }
-}
-
-__device__ __forceinline__ float mb_group_sum16(float v)
-{
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 16);
-    return v;
-}
+#include "gather_device.h"
 
 // C = 64, fp32 features: one 16-lane group per (row, point); lane c of the group owns channels c + 16 j, j = 0..3
 template <int L>
-__global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const MsmvBwdArgs a)
+__global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const MsmvArgs a)
 {
     const int lane16 = threadIdx.x & 15;
     const long pt = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;  // (s*Q+q)*P + p
@@ -69,39 +33,32 @@ __global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const MsmvBwdArgs a)
     const long ptc = act ? pt : 0;
     const int p = (int)(ptc % a.P);
     const long row = ptc / a.P;
-    const int s = (int)(row / a.Q);
+    const int s = (int)(row / a.Q), q = (int)(row % a.Q);
     const float *lp = a.loc + ptc * 3;
     const float *wp = a.w + ptc * L;
     const float lu = lp[0], lv = lp[1];
-    int view = (int)roundf(lp[2] * (float)(a.N - 1));
-    view = min(max(view, 0), a.N - 1);
+    const int view = rac_msmv_view(lp[2], a.N);
     // grad_out of this lane's 4 channels (BQGTPC: floats lane16 + 16 j of the point's 64-float row)
     float g[4];
     {
-        size_t gb, cs;
-        mb_gout_row(a, row, p, gb, cs);
-        const float *go = a.grad_out + gb + lane16 * cs;
+        const RacOutIdx gi = msmv_out_index(a, a.T > 0, s, q, p, lane16);
+        const float *go = a.grad_out + gi.base;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            g[j] = act ? go[(size_t)(16 * j) * cs] : 0.f;
+            g[j] = act ? go[(size_t)(16 * j) * gi.cstride] : 0.f;
     }
     float gu = 0.f, gv = 0.f;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
         const int H = a.H[l], W = a.W[l];
-        const float h_im = lv * (float)(H - 1), w_im = lu * (float)(W - 1);
-        const bool in = act && h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-        // outside the guard the footprint is pinned to (0, 0): a NaN / inf coordinate would make the tap weights NaN, and
-        // NaN times the zero taps would reach grad_loc through the location sums
-        const float hf = in ? floorf(h_im) : 0.f, wf = in ? floorf(w_im) : 0.f;
-        const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-        const float lh = in ? h_im - hf : 0.f, lw = in ? w_im - wf : 0.f, hh = 1.f - lh, hw = 1.f - lw;
+        const RacFootprint f = rac_footprint(lv * (float)(H - 1), lu * (float)(W - 1), H, W);
+        const int h_low = f.h_low, w_low = f.w_low, h_high = h_low + 1, w_high = w_low + 1;
+        const float lh = f.lh, lw = f.lw, hh = f.hh, hw = f.hw;
         const size_t map = ((size_t)s * a.N + view) * H * W * 64 + lane16;
         const float *base = (const float *)a.feat[l] + map;
         float *gbase = a.gfeat[l] + map;
         const float wl = wp[l];
-        const bool ok[4] = {in && h_low >= 0 && w_low >= 0, in && h_low >= 0 && w_high <= W - 1,
-                            in && h_high <= H - 1 && w_low >= 0, in && h_high <= H - 1 && w_high <= W - 1};
+        const bool ok[4] = {act && f.ok[0], act && f.ok[1], act && f.ok[2], act && f.ok[3]};
         const size_t o[4] = {((size_t)h_low * W + w_low) * 64, ((size_t)h_low * W + w_high) * 64,
                              ((size_t)h_high * W + w_low) * 64, ((size_t)h_high * W + w_high) * 64};
         const float tw[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
@@ -124,11 +81,11 @@ __global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const MsmvBwdArgs a)
             sh += dh[t] * dot;
             sw_ += dw[t] * dot;
         }
-        sv = mb_group_sum16(sv);
-        sh = mb_group_sum16(sh);
-        sw_ = mb_group_sum16(sw_);
+        sv = rac_group_sum16(sv);
+        sh = rac_group_sum16(sh);
+        sw_ = rac_group_sum16(sw_);
         if (act && lane16 == 0)
-            a.gw[ptc * L + l] = in ? sv : 0.f;
+            a.gw[ptc * L + l] = f.in ? sv : 0.f;
         gu += (float)(W - 1) * sw_ * wl;
         gv += (float)(H - 1) * sh * wl;
     }
@@ -141,36 +98,33 @@ __global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const MsmvBwdArgs a)
 
 // generic path: any C, any L <= 8.  One thread per (row, point); serial over channels (no atomics for
 // grad_loc / grad_weight either, atomics for the feature scatter).
-__global__ __launch_bounds__(256) void msmv_bwd_generic_kernel(const MsmvBwdArgs a)
+__global__ __launch_bounds__(256) void msmv_bwd_generic_kernel(const MsmvArgs a)
 {
     const long npts = (long)a.S * a.Q * a.P;
     for (long pt = (long)blockIdx.x * blockDim.x + threadIdx.x; pt < npts; pt += (long)gridDim.x * blockDim.x) {
         const int p = (int)(pt % a.P);
         const long row = pt / a.P;
-        const int s = (int)(row / a.Q);
+        const int s = (int)(row / a.Q), q = (int)(row % a.Q);
         const float *lp = a.loc + pt * 3;
         const float *wp = a.w + pt * a.L;
         const float lu = lp[0], lv = lp[1];
-        int view = (int)roundf(lp[2] * (float)(a.N - 1));
-        view = min(max(view, 0), a.N - 1);
-        size_t gb, cs;
-        mb_gout_row(a, row, p, gb, cs);
-        const float *go = a.grad_out + gb;
+        const int view = rac_msmv_view(lp[2], a.N);
+        const RacOutIdx gi = msmv_out_index(a, a.T > 0, s, q, p);
+        const float *go = a.grad_out + gi.base;
+        const size_t cs = gi.cstride;
         float gu = 0.f, gv = 0.f;
         for (int l = 0; l < a.L; ++l) {
             const int H = a.H[l], W = a.W[l];
-            const float h_im = lv * (float)(H - 1), w_im = lu * (float)(W - 1);
+            const RacFootprint f = rac_footprint(lv * (float)(H - 1), lu * (float)(W - 1), H, W);
             float sv = 0.f, sh = 0.f, sw_ = 0.f;
-            if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
-                const float hf = floorf(h_im), wf = floorf(w_im);
-                const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-                const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
+            if (f.in) {
+                const int h_low = f.h_low, w_low = f.w_low, h_high = h_low + 1, w_high = w_low + 1;
+                const float lh = f.lh, lw = f.lw, hh = f.hh, hw = f.hw;
                 const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
                 const size_t map = ((size_t)s * a.N + view) * H * W * a.C;
                 const float *base = (const float *)a.feat[l] + map;
                 float *gbase = a.gfeat[l] + map;
-                const bool ok1 = h_low >= 0 && w_low >= 0, ok2 = h_low >= 0 && w_high <= W - 1;
-                const bool ok3 = h_high <= H - 1 && w_low >= 0, ok4 = h_high <= H - 1 && w_high <= W - 1;
+                const bool ok1 = f.ok[0], ok2 = f.ok[1], ok3 = f.ok[2], ok4 = f.ok[3];
                 const size_t o1 = ((size_t)h_low * W + w_low) * a.C, o2 = ((size_t)h_low * W + w_high) * a.C;
                 const size_t o3 = ((size_t)h_high * W + w_low) * a.C, o4 = ((size_t)h_high * W + w_high) * a.C;
                 for (int c = 0; c < a.C; ++c) {
@@ -197,38 +151,17 @@ __global__ __launch_bounds__(256) void msmv_bwd_generic_kernel(const MsmvBwdArgs
     }
 }
 
-// argument checks (all before the first HIP call) and the launch of both entry points; `what` names the caller in errors
+// the launch of both entry points; `what` names the caller in errors
 static int msmv_bwd_impl(const char *what, const float *grad_out, int grad_layout, int T, int G, const void *const *feats,
                          const int32_t *hw, int L, const float *loc, const float *w, void *const *grad_feats, float *grad_loc,
                          float *grad_w, int S, int N, int Q, int P, int C, void *stream)
 {
-    RAC_CHECK_ARG(L >= 1 && L <= RAC_MAX_LEVELS, "%s: L=%d out of [1,%d]", what, L, RAC_MAX_LEVELS);
-    RAC_CHECK_ARG(S >= 0 && Q >= 0 && N >= 1 && C >= 1, "%s: bad sizes S=%d N=%d Q=%d C=%d", what, S, N, Q, C);
-    RAC_CHECK_ARG(P >= 0 && P <= RAC_MAX_POINTS, "%s: num_point exceed limits (P=%d > %d)", what, P, RAC_MAX_POINTS);
-    RAC_CHECK_ARG(grad_layout == RAC_OUT_SQCP || grad_layout == RAC_OUT_BQGTPC, "%s: gradient layout %d", what, grad_layout);
-    RAC_CHECK_ARG(T >= 1 && G >= 1, "%s: T=%d G=%d must be >= 1", what, T, G);
-    if (grad_layout == RAC_OUT_BQGTPC)
-        RAC_CHECK_ARG(S % (T * G) == 0, "%s: S=%d not a multiple of T*G=%d*%d", what, S, T, G);
-    if (S == 0 || Q == 0 || P == 0)
-        return 0;
-    RAC_CHECK_ARG(grad_out && feats && hw && loc && w && grad_feats && grad_loc && grad_w, "%s: null pointer", what);
-    MsmvBwdArgs a;
-    for (int l = 0; l < RAC_MAX_LEVELS; ++l) {
-        a.feat[l] = nullptr;
-        a.gfeat[l] = nullptr;
-        a.H[l] = a.W[l] = 1;
-    }
-    for (int l = 0; l < L; ++l) {
-        RAC_CHECK_ARG(feats[l] && grad_feats[l] && hw[2 * l] >= 1 && hw[2 * l + 1] >= 1, "%s: level %d", what, l);
-        a.feat[l] = feats[l];
-        a.gfeat[l] = (float *)grad_feats[l];
-        a.H[l] = hw[2 * l];
-        a.W[l] = hw[2 * l + 1];
-    }
-    a.grad_out = grad_out; a.loc = loc; a.w = w; a.gloc = grad_loc; a.gw = grad_w;
-    a.L = L; a.S = S; a.N = N; a.Q = Q; a.P = P; a.C = C;
-    a.T = grad_layout == RAC_OUT_BQGTPC ? T : 0;
-    a.G = grad_layout == RAC_OUT_BQGTPC ? G : 1;
+    MsmvArgs a;
+    const int rc = msmv_fill_args(a, MSMV_BWD, what, grad_layout, T, G, feats, grad_feats, hw, L, loc, w,
+                                  grad_out && grad_loc && grad_w, S, N, Q, P, C, RAC_F32, RAC_FEAT_CL);
+    if (rc || a.S == 0)
+        return rc;
+    a.grad_out = grad_out; a.gloc = grad_loc; a.gw = grad_w;
     hipStream_t st = (hipStream_t)stream;
     const long npts = (long)S * Q * P;
     if (C == 64 && (L == 2 || L == 4 || L == 5)) {

@@ -22,22 +22,7 @@
 //    c+48 (as msmv_bwd.hip) so that each atomic wave-instruction adds four whole 64-byte segments.
 //  * any other C, and channel-first: one thread per (point, channel) forward, one thread per point backward, through a
 //    stride table that covers both layouts.
-#include "rac_common.h"
-
-struct MsmvV2Args {
-    const void *feat[RAC_MAX_LEVELS];
-    float *gfeat[RAC_MAX_LEVELS];
-    int H[RAC_MAX_LEVELS];
-    int W[RAC_MAX_LEVELS];
-    const float *loc;       // [S,Q,P,3]
-    const float *w;         // [S,Q,P,L]
-    const float *grad_out;  // layout by T          (backward)
-    float *out;             // layout by T          (forward)
-    float *gloc;            // [S,Q,P,3]           (backward)
-    int L, S, N, Q, P, C;
-    int T, G;               // T > 0: RAC_OUT_BQGTPC, slot s = (b*T + t)*G + g
-    int cf;                 // 1: features [S,C,N,H,W]
-};
+#include "gather_device.h"
 
 // torch.argmax over a weight row: ties -> first index, NaN is maximal (first NaN wins), all -inf -> 0
 __device__ __forceinline__ int v2_argmax(const float *wp, int L)
@@ -64,7 +49,7 @@ struct V2Level {
     float *gfeat;
     int H, W;
 };
-__device__ __forceinline__ V2Level v2_level(const MsmvV2Args &a, int lsel)
+__device__ __forceinline__ V2Level v2_level(const MsmvArgs &a, int lsel)
 {
     V2Level r{a.feat[0], a.gfeat[0], a.H[0], a.W[0]};
 #pragma unroll
@@ -80,56 +65,15 @@ __device__ __forceinline__ V2Level v2_level(const MsmvV2Args &a, int lsel)
     return r;
 }
 
-// Bilinear footprint of one point on one map, computed as rac_msmv_fwd / rac_msmv_bwd do (products and differences rounded
-// one by one; the guard keeps huge coordinates away from the float -> int conversion).
-struct V2Taps {
-    int h_low, w_low;
-    float lh, lw, hh, hw;
-    bool ok[4];  // top-left, top-right, bottom-left, bottom-right inside the map
-    bool in;
-};
-__device__ __forceinline__ V2Taps v2_taps(float lu, float lv, int H, int W)
+// footprint of a point on the chosen level (align_corners=True)
+__device__ __forceinline__ RacFootprint v2_footprint(float lu, float lv, int H, int W)
 {
-#pragma clang fp contract(off)
-    V2Taps t;
-    const float h_im = lv * (float)(H - 1);
-    const float w_im = lu * (float)(W - 1);
-    t.in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-    const float hf = t.in ? floorf(h_im) : 0.f, wf = t.in ? floorf(w_im) : 0.f;
-    t.h_low = (int)hf;
-    t.w_low = (int)wf;
-    t.lh = t.in ? h_im - hf : 0.f;
-    t.lw = t.in ? w_im - wf : 0.f;
-    t.hh = 1.f - t.lh;
-    t.hw = 1.f - t.lw;
-    const bool top = t.in && t.h_low >= 0, bot = t.in && t.h_low + 1 <= H - 1;
-    const bool left = t.w_low >= 0, right = t.w_low + 1 <= W - 1;
-    t.ok[0] = top && left;
-    t.ok[1] = top && right;
-    t.ok[2] = bot && left;
-    t.ok[3] = bot && right;
-    return t;
-}
-
-__device__ __forceinline__ int v2_view(const float *lp, int N)
-{
-    const int view = (int)roundf(lp[2] * (float)(N - 1));
-    return min(max(view, 0), N - 1);
-}
-
-__device__ __forceinline__ size_t v2_out_index(const MsmvV2Args &a, long row, int p, int c)
-{
-    const int s = (int)(row / a.Q), q = (int)(row % a.Q);
-    if (a.T > 0) {   // RAC_OUT_BQGTPC
-        const int g = s % a.G, t = (s / a.G) % a.T, b = s / (a.G * a.T);
-        return (((((size_t)b * a.Q + q) * a.G + g) * a.T + t) * a.P + p) * a.C + c;
-    }
-    return ((size_t)row * a.C + c) * a.P + p;
+    return rac_footprint(lv * (float)(H - 1), lu * (float)(W - 1), H, W);
 }
 
 // ---- forward, C = 64, channel-last: one 16-lane group per point, 4 adjacent channels per lane
 template <typename FT>
-__global__ __launch_bounds__(256) void msmv_v2_fwd_c64_kernel(const MsmvV2Args a)
+__global__ __launch_bounds__(256) void msmv_v2_fwd_c64_kernel(const MsmvArgs a)
 {
     const int c4 = threadIdx.x & 15;
     const long pt = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;   // (s*Q + q)*P + p
@@ -141,9 +85,9 @@ __global__ __launch_bounds__(256) void msmv_v2_fwd_c64_kernel(const MsmvV2Args a
     const int s = (int)(row / a.Q);
     const float *lp = a.loc + pt * 3;
     const float lu = lp[0], lv = lp[1];
-    const int view = v2_view(lp, a.N);
+    const int view = rac_msmv_view(lp[2], a.N);
     const V2Level lv_ = v2_level(a, v2_argmax(a.w + pt * a.L, a.L));
-    const V2Taps t = v2_taps(lu, lv, lv_.H, lv_.W);
+    const RacFootprint t = v2_footprint(lu, lv, lv_.H, lv_.W);
     const FT *base = (const FT *)lv_.feat + ((size_t)s * a.N + view) * lv_.H * lv_.W * 64 + c4 * 4;
     const size_t pix[4] = {(size_t)t.h_low * lv_.W + t.w_low, (size_t)t.h_low * lv_.W + t.w_low + 1,
                            (size_t)(t.h_low + 1) * lv_.W + t.w_low, (size_t)(t.h_low + 1) * lv_.W + t.w_low + 1};
@@ -165,10 +109,10 @@ __global__ __launch_bounds__(256) void msmv_v2_fwd_c64_kernel(const MsmvV2Args a
         rac_tap_fma(acc, v[k].x, v[k].y, v[k].z, v[k].w, tw[k]);
     rac_f4 r;
     rac_acc4_get(acc, r.x, r.y, r.z, r.w);
+    float *o = a.out + msmv_out_index(a, a.T > 0, s, (int)(row % a.Q), p, c4 * 4).base;
     if (a.T > 0) {
-        *reinterpret_cast<rac_f4 *>(a.out + v2_out_index(a, row, p, c4 * 4)) = r;
+        *reinterpret_cast<rac_f4 *>(o) = r;
     } else {
-        float *o = a.out + v2_out_index(a, row, p, c4 * 4);
         o[0] = r.x;
         o[(size_t)a.P] = r.y;
         o[(size_t)2 * a.P] = r.z;
@@ -180,7 +124,7 @@ __global__ __launch_bounds__(256) void msmv_v2_fwd_c64_kernel(const MsmvV2Args a
 struct V2Strides {
     size_t map, pix, ch;
 };
-__device__ __forceinline__ V2Strides v2_strides(const MsmvV2Args &a, int s, int view, int H, int W)
+__device__ __forceinline__ V2Strides v2_strides(const MsmvArgs &a, int s, int view, int H, int W)
 {
     const size_t hw = (size_t)H * W;
     if (a.cf)   // [S,C,N,H,W]
@@ -188,16 +132,9 @@ __device__ __forceinline__ V2Strides v2_strides(const MsmvV2Args &a, int s, int 
     return V2Strides{((size_t)s * a.N + view) * hw * a.C, (size_t)a.C, 1};   // [S,N,H,W,C]
 }
 
-template <typename FT>
-__device__ __forceinline__ float v2_ld1(const FT *p);
-template <>
-__device__ __forceinline__ float v2_ld1<float>(const float *p) { return *p; }
-template <>
-__device__ __forceinline__ float v2_ld1<unsigned short>(const unsigned short *p) { return rac_bf16_to_f32(*p); }
-
 // ---- forward, any C, either feature layout: one thread per (point, channel), channel fastest
 template <typename FT>
-__global__ __launch_bounds__(256) void msmv_v2_fwd_generic_kernel(const MsmvV2Args a)
+__global__ __launch_bounds__(256) void msmv_v2_fwd_generic_kernel(const MsmvArgs a)
 {
     const long total = (long)a.S * a.Q * a.P * a.C;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -205,11 +142,11 @@ __global__ __launch_bounds__(256) void msmv_v2_fwd_generic_kernel(const MsmvV2Ar
         const long pt = idx / a.C;
         const int p = (int)(pt % a.P);
         const long row = pt / a.P;
-        const int s = (int)(row / a.Q);
+        const int s = (int)(row / a.Q), q = (int)(row % a.Q);
         const float *lp = a.loc + pt * 3;
-        const int view = v2_view(lp, a.N);
+        const int view = rac_msmv_view(lp[2], a.N);
         const V2Level lv_ = v2_level(a, v2_argmax(a.w + pt * a.L, a.L));
-        const V2Taps t = v2_taps(lp[0], lp[1], lv_.H, lv_.W);
+        const RacFootprint t = v2_footprint(lp[0], lp[1], lv_.H, lv_.W);
         const V2Strides st = v2_strides(a, s, view, lv_.H, lv_.W);
         const FT *base = (const FT *)lv_.feat + st.map + (size_t)c * st.ch;
         const size_t W = (size_t)lv_.W;
@@ -218,26 +155,18 @@ __global__ __launch_bounds__(256) void msmv_v2_fwd_generic_kernel(const MsmvV2Ar
         float v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            v[k] = t.ok[k] ? v2_ld1(base + pix[k] * st.pix) : 0.f;
+            v[k] = t.ok[k] ? rac_ld1(base + pix[k] * st.pix) : 0.f;
         float acc;
         {
 #pragma clang fp contract(off)
             acc = t.hh * t.hw * v[0] + t.hh * t.lw * v[1] + t.lh * t.hw * v[2] + t.lh * t.lw * v[3];
         }
-        a.out[v2_out_index(a, row, p, c)] = acc;
+        a.out[msmv_out_index(a, a.T > 0, s, q, p, c).base] = acc;
     }
 }
 
-__device__ __forceinline__ float v2_group_sum16(float v)
-{
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 16);
-    return v;
-}
-
 // ---- backward, C = 64, channel-last, fp32: one 16-lane group per point; lane c of the group owns channels c + 16 j
-__global__ __launch_bounds__(256) void msmv_v2_bwd_c64_kernel(const MsmvV2Args a)
+__global__ __launch_bounds__(256) void msmv_v2_bwd_c64_kernel(const MsmvArgs a)
 {
     const int lane16 = threadIdx.x & 15;
     const long pt = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
@@ -246,19 +175,19 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_c64_kernel(const MsmvV2Args a
     const long ptc = act ? pt : 0;
     const int p = (int)(ptc % a.P);
     const long row = ptc / a.P;
-    const int s = (int)(row / a.Q);
+    const int s = (int)(row / a.Q), q = (int)(row % a.Q);
     const float *lp = a.loc + ptc * 3;
-    const int view = v2_view(lp, a.N);
+    const int view = rac_msmv_view(lp[2], a.N);
     const V2Level lv_ = v2_level(a, v2_argmax(a.w + ptc * a.L, a.L));
     const int H = lv_.H, W = lv_.W;
-    V2Taps t = v2_taps(lp[0], lp[1], H, W);
+    const RacFootprint t = v2_footprint(lp[0], lp[1], H, W);
     float g[4];
     {   // channel c of the point at go + c * cs: BQGTPC one contiguous 64-float row, SQCP P floats apart
-        const size_t cs = a.T > 0 ? 1 : (size_t)a.P;
-        const float *go = a.grad_out + v2_out_index(a, row, p, lane16);
+        const RacOutIdx gi = msmv_out_index(a, a.T > 0, s, q, p, lane16);
+        const float *go = a.grad_out + gi.base;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            g[j] = act ? go[(size_t)(16 * j) * cs] : 0.f;
+            g[j] = act ? go[(size_t)(16 * j) * gi.cstride] : 0.f;
     }
     const size_t map = ((size_t)s * a.N + view) * H * W * 64 + lane16;
     const float *base = (const float *)lv_.feat + map;
@@ -284,8 +213,8 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_c64_kernel(const MsmvV2Args a
         sh += dh[k] * dot;
         sw_ += dw[k] * dot;
     }
-    sh = v2_group_sum16(sh);
-    sw_ = v2_group_sum16(sw_);
+    sh = rac_group_sum16(sh);
+    sw_ = rac_group_sum16(sw_);
     if (act && lane16 == 0) {
         a.gloc[ptc * 3] = (float)(W - 1) * sw_;
         a.gloc[ptc * 3 + 1] = (float)(H - 1) * sh;
@@ -294,18 +223,18 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_c64_kernel(const MsmvV2Args a
 }
 
 // ---- backward, any C, either feature layout, fp32: one thread per point, serial over the channels
-__global__ __launch_bounds__(256) void msmv_v2_bwd_generic_kernel(const MsmvV2Args a)
+__global__ __launch_bounds__(256) void msmv_v2_bwd_generic_kernel(const MsmvArgs a)
 {
     const long npts = (long)a.S * a.Q * a.P;
     for (long pt = (long)blockIdx.x * blockDim.x + threadIdx.x; pt < npts; pt += (long)gridDim.x * blockDim.x) {
         const int p = (int)(pt % a.P);
         const long row = pt / a.P;
-        const int s = (int)(row / a.Q);
+        const int s = (int)(row / a.Q), q = (int)(row % a.Q);
         const float *lp = a.loc + pt * 3;
-        const int view = v2_view(lp, a.N);
+        const int view = rac_msmv_view(lp[2], a.N);
         const V2Level lv_ = v2_level(a, v2_argmax(a.w + pt * a.L, a.L));
         const int H = lv_.H, W = lv_.W;
-        const V2Taps t = v2_taps(lp[0], lp[1], H, W);
+        const RacFootprint t = v2_footprint(lp[0], lp[1], H, W);
         const V2Strides st = v2_strides(a, s, view, H, W);
         const float *base = (const float *)lv_.feat + st.map;
         float *gbase = lv_.gfeat + st.map;
@@ -314,8 +243,9 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_generic_kernel(const MsmvV2Ar
         const float tw[4] = {t.hh * t.hw, t.hh * t.lw, t.lh * t.hw, t.lh * t.lw};
         float sh = 0.f, sw_ = 0.f;
         if (t.in) {
-            const float *go = a.grad_out + v2_out_index(a, row, p, 0);
-            const size_t gs = a.T > 0 ? 1 : (size_t)a.P;
+            const RacOutIdx gi = msmv_out_index(a, a.T > 0, s, q, p);
+            const float *go = a.grad_out + gi.base;
+            const size_t gs = gi.cstride;
             for (int c = 0; c < a.C; ++c) {
                 const float g = go[(size_t)c * gs];
                 const size_t cc = (size_t)c * st.ch;
@@ -336,57 +266,16 @@ __global__ __launch_bounds__(256) void msmv_v2_bwd_generic_kernel(const MsmvV2Ar
     }
 }
 
-// argument checks shared by both entry points; everything before the first HIP call
-static int v2_fill_args(MsmvV2Args &a, const char *what, const void *const *feats, void *const *grad_feats, bool need_grad,
-                        const int32_t *hw, int L, const float *loc, const float *w, int S, int N, int Q, int P, int C,
-                        int feat_layout)
-{
-    RAC_CHECK_ARG(hw && feats && (!need_grad || grad_feats), "%s: null pointer", what);
-    for (int l = 0; l < RAC_MAX_LEVELS; ++l) {
-        a.feat[l] = nullptr;
-        a.gfeat[l] = nullptr;
-        a.H[l] = a.W[l] = 1;
-    }
-    for (int l = 0; l < L; ++l) {
-        RAC_CHECK_ARG(feats[l] != nullptr && (!need_grad || grad_feats[l] != nullptr), "%s: level %d pointer is null", what, l);
-        RAC_CHECK_ARG(hw[2 * l] >= 1 && hw[2 * l + 1] >= 1, "%s: level %d has an empty map", what, l);
-        a.feat[l] = feats[l];
-        a.gfeat[l] = need_grad ? (float *)grad_feats[l] : nullptr;
-        a.H[l] = hw[2 * l];
-        a.W[l] = hw[2 * l + 1];
-    }
-    RAC_CHECK_ARG(loc && w, "%s: null pointer", what);
-    a.loc = loc; a.w = w;
-    a.grad_out = nullptr; a.out = nullptr; a.gloc = nullptr;
-    a.L = L; a.S = S; a.N = N; a.Q = Q; a.P = P; a.C = C;
-    a.T = 0; a.G = 1;
-    a.cf = feat_layout == RAC_FEAT_CF;
-    return 0;
-}
-
 extern "C" int rac_msmv_v2_fwd(const void *const *feats, const int32_t *hw, int L, const float *loc, const float *w,
                                float *out, int S, int N, int Q, int P, int C, int dtype, int feat_layout, int out_layout,
                                int T, int G, void *stream)
 {
-    RAC_CHECK_ARG(L >= 1 && L <= RAC_MAX_LEVELS, "rac_msmv_v2_fwd: L=%d out of [1,%d]", L, RAC_MAX_LEVELS);
-    RAC_CHECK_ARG(S >= 0 && Q >= 0 && N >= 1 && C >= 1, "rac_msmv_v2_fwd: bad sizes S=%d N=%d Q=%d C=%d", S, N, Q, C);
-    RAC_CHECK_ARG(P >= 0 && P <= RAC_MAX_POINTS, "rac_msmv_v2_fwd: num_point exceed limits (P=%d > %d)", P, RAC_MAX_POINTS);
-    RAC_CHECK_ARG(dtype == RAC_F32 || dtype == RAC_BF16, "rac_msmv_v2_fwd: dtype %d", dtype);
-    RAC_CHECK_ARG(feat_layout == RAC_FEAT_CL || feat_layout == RAC_FEAT_CF, "rac_msmv_v2_fwd: feature layout %d", feat_layout);
-    RAC_CHECK_ARG(feat_layout == RAC_FEAT_CL || dtype == RAC_F32, "rac_msmv_v2_fwd: channel-first features are float32 only");
-    RAC_CHECK_ARG(out_layout == RAC_OUT_SQCP || out_layout == RAC_OUT_BQGTPC, "rac_msmv_v2_fwd: layout %d", out_layout);
-    if (out_layout == RAC_OUT_BQGTPC)
-        RAC_CHECK_ARG(T >= 1 && G >= 1 && S % (T * G) == 0, "rac_msmv_v2_fwd: S=%d not a multiple of T*G=%d*%d", S, T, G);
-    if (S == 0 || Q == 0 || P == 0)
-        return 0;  // empty output: nothing to launch (torch hands out null data pointers for empty tensors)
-    RAC_CHECK_ARG(out != nullptr, "rac_msmv_v2_fwd: null pointer");
-    MsmvV2Args a;
-    const int rc = v2_fill_args(a, "rac_msmv_v2_fwd", feats, nullptr, false, hw, L, loc, w, S, N, Q, P, C, feat_layout);
-    if (rc)
+    MsmvArgs a;
+    const int rc = msmv_fill_args(a, MSMV_V2_FWD, "rac_msmv_v2_fwd", out_layout, T, G, feats, nullptr, hw, L, loc, w,
+                                  out != nullptr, S, N, Q, P, C, dtype, feat_layout);
+    if (rc || a.S == 0)
         return rc;
     a.out = out;
-    a.T = out_layout == RAC_OUT_BQGTPC ? T : 0;
-    a.G = out_layout == RAC_OUT_BQGTPC ? G : 1;
     hipStream_t st = (hipStream_t)stream;
     const long npts = (long)S * Q * P;
     if (C == 64 && feat_layout == RAC_FEAT_CL) {
@@ -410,25 +299,13 @@ static int msmv_v2_bwd_impl(const char *what, const float *grad_out, int grad_la
                             const int32_t *hw, int L, const float *loc, const float *w, void *const *grad_feats, float *grad_loc,
                             int S, int N, int Q, int P, int C, int feat_layout, void *stream)
 {
-    RAC_CHECK_ARG(L >= 1 && L <= RAC_MAX_LEVELS, "%s: L=%d out of [1,%d]", what, L, RAC_MAX_LEVELS);
-    RAC_CHECK_ARG(S >= 0 && Q >= 0 && N >= 1 && C >= 1, "%s: bad sizes S=%d N=%d Q=%d C=%d", what, S, N, Q, C);
-    RAC_CHECK_ARG(P >= 0 && P <= RAC_MAX_POINTS, "%s: num_point exceed limits (P=%d > %d)", what, P, RAC_MAX_POINTS);
-    RAC_CHECK_ARG(feat_layout == RAC_FEAT_CL || feat_layout == RAC_FEAT_CF, "%s: feature layout %d", what, feat_layout);
-    RAC_CHECK_ARG(grad_layout == RAC_OUT_SQCP || grad_layout == RAC_OUT_BQGTPC, "%s: gradient layout %d", what, grad_layout);
-    RAC_CHECK_ARG(T >= 1 && G >= 1, "%s: T=%d G=%d must be >= 1", what, T, G);
-    if (grad_layout == RAC_OUT_BQGTPC)
-        RAC_CHECK_ARG(S % (T * G) == 0, "%s: S=%d not a multiple of T*G=%d*%d", what, S, T, G);
-    if (S == 0 || Q == 0 || P == 0)
-        return 0;
-    RAC_CHECK_ARG(grad_out && grad_loc, "%s: null pointer", what);
-    MsmvV2Args a;
-    const int rc = v2_fill_args(a, what, feats, grad_feats, true, hw, L, loc, w, S, N, Q, P, C, feat_layout);
-    if (rc)
+    MsmvArgs a;
+    const int rc = msmv_fill_args(a, MSMV_V2_BWD, what, grad_layout, T, G, feats, grad_feats, hw, L, loc, w,
+                                  grad_out && grad_loc, S, N, Q, P, C, RAC_F32, feat_layout);
+    if (rc || a.S == 0)
         return rc;
     a.grad_out = grad_out;
     a.gloc = grad_loc;
-    a.T = grad_layout == RAC_OUT_BQGTPC ? T : 0;
-    a.G = grad_layout == RAC_OUT_BQGTPC ? G : 1;
     hipStream_t st = (hipStream_t)stream;
     const long npts = (long)S * Q * P;
     if (C == 64 && feat_layout == RAC_FEAT_CL) {

@@ -26,29 +26,12 @@ def msmv_forward(mlvl_feats, sampling_locations, scale_weights, out_layout=_lib.
     feats = list(mlvl_feats)
     L = len(feats)
     _lib.require_gpu(*feats, sampling_locations, scale_weights, what="msmv_sampling")
-    S, N, H0, W0, C = feats[0].shape
-    _, Q, P, three = sampling_locations.shape
-    if three != 3 or sampling_locations.shape[0] != S:
-        raise RuntimeError("msmv_sampling: sampling_locations must be [B', Q, P, 3]")
-    if tuple(scale_weights.shape) != (S, Q, P, L):
-        raise RuntimeError(f"msmv_sampling: scale_weights must be [B', Q, P, {L}], got {tuple(scale_weights.shape)}")
-    if P > 128:
-        raise RuntimeError("num_point exceed limits")
+    S, N, C, Q, P = _shapes(feats, sampling_locations, scale_weights, False, "msmv_sampling")
     code = _lib.dtype_code(feats[0])
-    for f in feats:
-        if f.dtype != feats[0].dtype or f.shape[0] != S or f.shape[1] != N or f.shape[4] != C:
-            raise RuntimeError("msmv_sampling: all levels must share dtype and [B', N, ., ., C]")
-    if sampling_locations.dtype != torch.float32 or scale_weights.dtype != torch.float32:
-        raise RuntimeError("msmv_sampling: locations / weights must be float32")
-    if out_layout == _lib.OUT_SQCP:
-        shape = (S, Q, C, P)
-    else:
-        B = S // (num_frames * num_groups)
-        shape = (B, Q, num_groups, num_frames * P, C)
     if out is None:
-        out = torch.empty(shape, device=feats[0].device, dtype=torch.float32)
-    ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[2:4]])
+        out = torch.empty(_out_shape(out_layout, S, Q, C, P, num_frames, num_groups),
+                          device=feats[0].device, dtype=torch.float32)
+    ptrs, hw = _levels(feats, False)
     ev = _lib.timer.record("msmv_fwd") if _lib.timer is not None else None
     if ev:
         ev[0].record()
@@ -63,15 +46,55 @@ def msmv_forward(mlvl_feats, sampling_locations, scale_weights, out_layout=_lib.
     return out
 
 
+def _shapes(feats, sampling_locations, scale_weights, channels_first, what):
+    """-> (S, N, C, Q, P) of a call, raising the RuntimeErrors of the reference's wrapper on inconsistent operands.
+    Features channel-last ``[B', N, H, W, C]`` or, ``channels_first``, ``[B', C, N, H, W]``."""
+    L = len(feats)
+    if any(f.dim() != 5 for f in feats):
+        raise RuntimeError(f"{what}: features must be 5-d")
+    if channels_first:
+        S, C, N = feats[0].shape[:3]
+    else:
+        S, N, _, _, C = feats[0].shape
+    _, Q, P, three = sampling_locations.shape
+    if three != 3 or sampling_locations.shape[0] != S:
+        raise RuntimeError(f"{what}: sampling_locations must be [B', Q, P, 3]")
+    if tuple(scale_weights.shape) != (S, Q, P, L):
+        raise RuntimeError(f"{what}: scale_weights must be [B', Q, P, {L}], got {tuple(scale_weights.shape)}")
+    if P > 128:
+        raise RuntimeError("num_point exceed limits")
+    for f in feats:
+        lead = (f.shape[0], f.shape[1], f.shape[2]) if channels_first else (f.shape[0], f.shape[1], f.shape[4])
+        if f.dtype != feats[0].dtype or lead != ((S, C, N) if channels_first else (S, N, C)):
+            layout = "[B', C, N, ., .]" if channels_first else "[B', N, ., ., C]"
+            raise RuntimeError(f"{what}: all levels must share dtype and {layout}")
+    if sampling_locations.dtype != torch.float32 or scale_weights.dtype != torch.float32:
+        raise RuntimeError(f"{what}: locations / weights must be float32")
+    return S, N, C, Q, P
+
+
+def _out_shape(layout, S, Q, C, P, num_frames, num_groups):
+    """the forward's output shape in ``layout``: [B', Q, C, P], or [B, Q, G, T*P, C] for OUT_BQGTPC"""
+    if layout == _lib.OUT_SQCP:
+        return (S, Q, C, P)
+    return (S // (num_frames * num_groups), Q, num_groups, num_frames * P, C)
+
+
 def _grad_shape(grad_layout, S, Q, C, P, num_frames, num_groups, what):
     """the shape a gradient in ``grad_layout`` must have (the forward's output shape in that layout)"""
-    if grad_layout == _lib.OUT_SQCP:
-        return (S, Q, C, P)
-    if grad_layout != _lib.OUT_BQGTPC:
+    if grad_layout not in (_lib.OUT_SQCP, _lib.OUT_BQGTPC):
         raise RuntimeError(f"{what}: unknown gradient layout {grad_layout}")
-    if num_frames < 1 or num_groups < 1 or S % (num_frames * num_groups):
+    if grad_layout == _lib.OUT_BQGTPC and (num_frames < 1 or num_groups < 1 or S % (num_frames * num_groups)):
         raise RuntimeError(f"{what}: B'={S} is not a multiple of num_frames*num_groups={num_frames}*{num_groups}")
-    return (S // (num_frames * num_groups), Q, num_groups, num_frames * P, C)
+    return _out_shape(grad_layout, S, Q, C, P, num_frames, num_groups)
+
+
+def _levels(feats, channels_first):
+    """-> the C-ABI's level pointer array and [L, 2] (H, W) array of ``feats``"""
+    hw_dims = slice(3, 5) if channels_first else slice(2, 4)
+    ptrs = (ctypes.c_void_p * len(feats))(*[f.data_ptr() for f in feats])
+    hw = (ctypes.c_int32 * (2 * len(feats)))(*[int(x) for f in feats for x in f.shape[hw_dims]])
+    return ptrs, hw
 
 
 def msmv_backward(grad_output, mlvl_feats, sampling_locations, scale_weights, grad_layout=_lib.OUT_SQCP, num_frames=1,
@@ -86,17 +109,15 @@ def msmv_backward(grad_output, mlvl_feats, sampling_locations, scale_weights, gr
     _lib.require_gpu(grad_output, *feats, sampling_locations, scale_weights, what="msmv_sampling backward")
     if any(f.dtype != torch.float32 for f in feats):
         raise RuntimeError("msmv_sampling backward: float32 features only")
-    S, N, _, _, C = feats[0].shape
-    _, Q, P, _ = sampling_locations.shape
+    S, N, C, Q, P = _shapes(feats, sampling_locations, scale_weights, False, "msmv_sampling backward")
     want = _grad_shape(grad_layout, S, Q, C, P, num_frames, num_groups, "msmv_sampling backward")
     if tuple(grad_output.shape) != want:
         raise RuntimeError(f"msmv_sampling backward: grad_output must be {list(want)}, got {list(grad_output.shape)}")
     grad_feats = [torch.zeros_like(f) for f in feats]
     grad_loc = torch.empty_like(sampling_locations)
     grad_w = torch.empty_like(scale_weights)
-    ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    gptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in grad_feats])
-    hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[2:4]])
+    ptrs, hw = _levels(feats, False)
+    gptrs, _ = _levels(grad_feats, False)
     rc = _lib.lib().rac_msmv_bwd_ex(_lib.ptr(grad_output), grad_layout, num_frames, num_groups, ptrs, hw, L,
                                     _lib.ptr(sampling_locations), _lib.ptr(scale_weights), gptrs, _lib.ptr(grad_loc),
                                     _lib.ptr(grad_w), S, N, Q, P, C, _lib.stream_ptr())
@@ -143,34 +164,6 @@ def msmv_sampling(mlvl_feats, sampling_locations, scale_weights):
 
 
 # ------------------------------------------------------------------------------------------ v2: hard level
-def _v2_shapes(feats, sampling_locations, scale_weights, channels_first, what):
-    """-> (S, N, C, Q, P, hw) of a v2 call, raising the RuntimeErrors msmv_forward raises."""
-    L = len(feats)
-    if any(f.dim() != 5 for f in feats):
-        raise RuntimeError(f"{what}: features must be 5-d")
-    if channels_first:
-        S, C, N = feats[0].shape[:3]
-    else:
-        S, N, _, _, C = feats[0].shape
-    _, Q, P, three = sampling_locations.shape
-    if three != 3 or sampling_locations.shape[0] != S:
-        raise RuntimeError(f"{what}: sampling_locations must be [B', Q, P, 3]")
-    if tuple(scale_weights.shape) != (S, Q, P, L):
-        raise RuntimeError(f"{what}: scale_weights must be [B', Q, P, {L}], got {tuple(scale_weights.shape)}")
-    if P > 128:
-        raise RuntimeError("num_point exceed limits")
-    for f in feats:
-        lead = (f.shape[0], f.shape[1], f.shape[2]) if channels_first else (f.shape[0], f.shape[1], f.shape[4])
-        if f.dtype != feats[0].dtype or lead != ((S, C, N) if channels_first else (S, N, C)):
-            layout = "[B', C, N, ., .]" if channels_first else "[B', N, ., ., C]"
-            raise RuntimeError(f"{what}: all levels must share dtype and {layout}")
-    if sampling_locations.dtype != torch.float32 or scale_weights.dtype != torch.float32:
-        raise RuntimeError(f"{what}: locations / weights must be float32")
-    hw_dims = slice(3, 5) if channels_first else slice(2, 4)
-    hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[hw_dims]])
-    return S, N, C, Q, P, hw
-
-
 def msmv_v2_forward(mlvl_feats, sampling_locations, scale_weights, out_layout=_lib.OUT_SQCP, num_frames=1, num_groups=1,
                     channels_first=False, out=None):
     """Launches rac_msmv_v2_fwd on the current stream: each point sampled on its argmax-weight level only, not scaled by
@@ -179,18 +172,14 @@ def msmv_v2_forward(mlvl_feats, sampling_locations, scale_weights, out_layout=_l
     feats = list(mlvl_feats)
     L = len(feats)
     _lib.require_gpu(*feats, sampling_locations, scale_weights, what="msmv_sampling_v2")
-    S, N, C, Q, P, hw = _v2_shapes(feats, sampling_locations, scale_weights, channels_first, "msmv_sampling_v2")
+    S, N, C, Q, P = _shapes(feats, sampling_locations, scale_weights, channels_first, "msmv_sampling_v2")
     code = _lib.dtype_code(feats[0])
     if channels_first and code != _lib.RAC_F32:
         raise RuntimeError("msmv_sampling_v2: channel-first features must be float32")
-    if out_layout == _lib.OUT_SQCP:
-        shape = (S, Q, C, P)
-    else:
-        B = S // (num_frames * num_groups)
-        shape = (B, Q, num_groups, num_frames * P, C)
     if out is None:
-        out = torch.empty(shape, device=feats[0].device, dtype=torch.float32)
-    ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
+        out = torch.empty(_out_shape(out_layout, S, Q, C, P, num_frames, num_groups),
+                          device=feats[0].device, dtype=torch.float32)
+    ptrs, hw = _levels(feats, channels_first)
     rc = _lib.lib().rac_msmv_v2_fwd(ptrs, hw, L, _lib.ptr(sampling_locations), _lib.ptr(scale_weights), _lib.ptr(out),
                                     S, N, Q, P, C, code, _lib.FEAT_CF if channels_first else _lib.FEAT_CL, out_layout,
                                     num_frames, num_groups, _lib.stream_ptr())
@@ -209,14 +198,14 @@ def msmv_v2_backward(grad_output, mlvl_feats, sampling_locations, scale_weights,
     _lib.require_gpu(grad_output, *feats, sampling_locations, scale_weights, what="msmv_sampling_v2 backward")
     if any(f.dtype != torch.float32 for f in feats):
         raise RuntimeError("msmv_sampling_v2 backward: float32 features only")
-    S, N, C, Q, P, hw = _v2_shapes(feats, sampling_locations, scale_weights, channels_first, "msmv_sampling_v2 backward")
+    S, N, C, Q, P = _shapes(feats, sampling_locations, scale_weights, channels_first, "msmv_sampling_v2 backward")
     want = _grad_shape(grad_layout, S, Q, C, P, num_frames, num_groups, "msmv_sampling_v2 backward")
     if tuple(grad_output.shape) != want:
         raise RuntimeError(f"msmv_sampling_v2 backward: grad_output must be {list(want)}, got {list(grad_output.shape)}")
     grad_feats = [torch.zeros_like(f) for f in feats]
     grad_loc = torch.empty_like(sampling_locations)
-    ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    gptrs = (ctypes.c_void_p * L)(*[g.data_ptr() for g in grad_feats])
+    ptrs, hw = _levels(feats, channels_first)
+    gptrs, _ = _levels(grad_feats, channels_first)
     rc = _lib.lib().rac_msmv_v2_bwd_ex(_lib.ptr(grad_output), grad_layout, num_frames, num_groups, ptrs, hw, L,
                                        _lib.ptr(sampling_locations), _lib.ptr(scale_weights), gptrs, _lib.ptr(grad_loc), S, N,
                                        Q, P, C, _lib.FEAT_CF if channels_first else _lib.FEAT_CL, _lib.stream_ptr())

@@ -153,11 +153,13 @@ def msmv_reference(feats, loc, w, gout, N, v2=False):
     f64 = [f.detach().cpu().double().requires_grad_() for f in feats]
     l64 = loc_o.clone().requires_grad_()
     w64 = w_c.double().requires_grad_(not v2)
-    R.msmv_gather_torch(f64, l64, w64, f32_coords=True).backward(g64)
-    # magnitudes of feat / w
+    fwd = R.msmv_gather_torch(f64, l64, w64, f32_coords=True)
+    fwd.backward(g64)
+    # magnitudes of the output and of feat / w
     fa = [f.detach().cpu().double().abs().requires_grad_() for f in feats]
     wa = w_c.double().abs().requires_grad_()
-    R.msmv_gather_torch(fa, loc_o, wa, f32_coords=True).backward(g64.abs())
+    fwd_a = R.msmv_gather_torch(fa, loc_o, wa, f32_coords=True)
+    fwd_a.backward(g64.abs())
     # magnitude of loc
     geo = MsmvGeom(hws, loc_c, N)
     ga = _g_rows(gout).abs()
@@ -169,7 +171,8 @@ def msmv_reference(feats, loc, w, gout, N, v2=False):
         au += (W - 1) * wa_rows[:, l] * T
         av += (H - 1) * wa_rows[:, l] * T
     A_loc = torch.stack([au, av, torch.zeros_like(au)], -1).reshape(loc.shape)
-    out = {"feat": ([f.grad for f in f64], [f.grad for f in fa]), "loc": (l64.grad, A_loc)}
+    out = {"feat": ([f.grad for f in f64], [f.grad for f in fa]), "loc": (l64.grad, A_loc),
+           "out": (fwd.detach(), fwd_a.detach())}
     if not v2:
         out["w"] = (w64.grad, wa.grad)
     out["geo"], out["w_used"] = geo, w_c.double()
@@ -209,8 +212,11 @@ def msmv_drop_one_tap(ref, feats, gout, hws):
     return wrong
 
 
-def msmv_compare(name, ref, got_feats, got_loc, got_w, feats, gout):
+def msmv_compare(name, ref, got_feats, got_loc, got_w, feats, gout, got_out=None):
+    """got_out: the forward's output, checked too (a non-finite location contributes what FAR does: nothing)"""
     hws = [tuple(f.shape[2:4]) for f in feats]
+    if got_out is not None:
+        check(f"{name} out", "feat", got_out, *ref["out"])
     for l in range(len(feats)):
         check(f"{name} feat{l}", "feat", got_feats[l], ref["feat"][0][l], ref["feat"][1][l])
     check(f"{name} loc", "loc", got_loc, *ref["loc"])
@@ -266,16 +272,17 @@ def run_msmv(feats, loc, w, gout):
     from racformer_amd.msmv import msmv_sampling
     gf = [f.to(DEV).requires_grad_() for f in feats]
     gl, gw = loc.to(DEV).requires_grad_(), w.to(DEV).requires_grad_()
-    msmv_sampling(gf, gl, gw).backward(gout.to(DEV))
-    return [f.grad for f in gf], gl.grad, gw.grad
+    out = msmv_sampling(gf, gl, gw)
+    out.backward(gout.to(DEV))
+    return [f.grad for f in gf], gl.grad, gw.grad, out.detach()
 
 
 @pytest.mark.parametrize("L", [2, 4, 5])
 def test_msmv_bwd_c64_fast_path(L):
     feats, loc, w, gout = msmv_case(100 + L, S=2, N=6, Q=12, P=9, C=64, hws=HWS[L])
     ref = msmv_reference(feats, loc, w, gout, 6)
-    gf, gl, gw = run_msmv(feats, loc, w, gout)
-    msmv_compare(f"msmv c64 L{L}", ref, gf, gl, gw, feats, gout)
+    gf, gl, gw, out = run_msmv(feats, loc, w, gout)
+    msmv_compare(f"msmv c64 L{L}", ref, gf, gl, gw, feats, gout, out)
 
 
 @pytest.mark.parametrize("N", [1, 6])
@@ -284,8 +291,8 @@ def test_msmv_bwd_c64_fast_path(L):
 def test_msmv_bwd_generic(C, L, N):
     feats, loc, w, gout = msmv_case(1000 + 10 * C + L + N, S=2, N=N, Q=5, P=5, C=C, hws=HWS[L])
     ref = msmv_reference(feats, loc, w, gout, N)
-    gf, gl, gw = run_msmv(feats, loc, w, gout)
-    msmv_compare(f"msmv generic C{C}", ref, gf, gl, gw, feats, gout)
+    gf, gl, gw, out = run_msmv(feats, loc, w, gout)
+    msmv_compare(f"msmv generic C{C}", ref, gf, gl, gw, feats, gout, out)
 
 
 def test_msmv_bwd_generic_past_the_grid():
@@ -294,8 +301,8 @@ def test_msmv_bwd_generic_past_the_grid():
     assert S * Q * P > 4096 * 256
     feats, loc, w, gout = msmv_case(7, S=S, N=2, Q=Q, P=P, C=8, hws=[(9, 17)])
     ref = msmv_reference(feats, loc, w, gout, 2)
-    gf, gl, gw = run_msmv(feats, loc, w, gout)
-    msmv_compare("msmv generic 1.15M", ref, gf, gl, gw, feats, gout)
+    gf, gl, gw, out = run_msmv(feats, loc, w, gout)
+    msmv_compare("msmv generic 1.15M", ref, gf, gl, gw, feats, gout, out)
 
 
 def test_msmv_bwd_collision():
@@ -304,8 +311,8 @@ def test_msmv_bwd_collision():
     feats, loc, w, gout = msmv_case(8, S=S, N=N, Q=Q, P=P, C=64, hws=HWS[2], edges=False)
     loc[..., 0], loc[..., 1] = 0.3, 0.6
     ref = msmv_reference(feats, loc, w, gout, N)
-    gf, gl, gw = run_msmv(feats, loc, w, gout)
-    msmv_compare("msmv c64 collision", ref, gf, gl, gw, feats, gout)
+    gf, gl, gw, out = run_msmv(feats, loc, w, gout)
+    msmv_compare("msmv c64 collision", ref, gf, gl, gw, feats, gout, out)
 
 
 def test_msmv_bwd_autograd_plumbing():
@@ -349,32 +356,33 @@ def run_v2(feats, loc, w, gout, channels_first=False):
     fs = [f.permute(0, 4, 1, 2, 3).contiguous() if channels_first else f for f in feats]
     gf = [f.to(DEV).requires_grad_() for f in fs]
     gl, gw = loc.to(DEV).requires_grad_(), w.to(DEV).requires_grad_()
-    msmv_sampling_v2(gf, gl, gw, channels_first=channels_first).backward(gout.to(DEV))
+    out = msmv_sampling_v2(gf, gl, gw, channels_first=channels_first)
+    out.backward(gout.to(DEV))
     assert gw.grad is None
     grads = [f.grad.permute(0, 2, 3, 4, 1) if channels_first else f.grad for f in gf]
-    return grads, gl.grad
+    return grads, gl.grad, out.detach()
 
 
 @pytest.mark.parametrize("L,channels_first", [(2, False), (5, False), (4, True)])
 def test_msmv_v2_bwd(L, channels_first):
     feats, loc, w, gout = msmv_case(200 + L, S=2, N=6, Q=12, P=9, C=64, hws=HWS[L])
     ref = msmv_reference(feats, loc, w, gout, 6, v2=True)
-    gf, gl = run_v2(feats, loc, w, gout, channels_first)
-    msmv_compare(f"v2 c64 L{L}{' cf' if channels_first else ''}", ref, gf, gl, None, feats, gout)
+    gf, gl, out = run_v2(feats, loc, w, gout, channels_first)
+    msmv_compare(f"v2 c64 L{L}{' cf' if channels_first else ''}", ref, gf, gl, None, feats, gout, out)
 
 
 def test_msmv_v2_bwd_generic_past_the_grid():
     S, Q, P = 32, 900, 40
     feats, loc, w, gout = msmv_case(11, S=S, N=2, Q=Q, P=P, C=8, hws=HWS[2])
     ref = msmv_reference(feats, loc, w, gout, 2, v2=True)
-    gf, gl = run_v2(feats, loc, w, gout)
-    msmv_compare("v2 generic 1.15M", ref, gf, gl, None, feats, gout)
+    gf, gl, out = run_v2(feats, loc, w, gout)
+    msmv_compare("v2 generic 1.15M", ref, gf, gl, None, feats, gout, out)
 
 
 def test_msmv_v2_bwd_deterministic_loc():
     feats, loc, w, gout = msmv_case(12, S=2, N=6, Q=12, P=9, C=64, hws=HWS[4])
-    _, a = run_v2(feats, loc, w, gout)
-    _, b = run_v2(feats, loc, w, gout)
+    _, a, _ = run_v2(feats, loc, w, gout)
+    _, b, _ = run_v2(feats, loc, w, gout)
     assert torch.equal(a, b)
 
 
@@ -419,9 +427,11 @@ def msda_reference(value, shapes, starts, loc, attn, gout):
     loc_o = _finite_for_oracle(loc).double()
     g64 = gout.double()
     v64, l64, a64 = value.double().requires_grad_(), loc_o.clone().requires_grad_(), attn.double().requires_grad_()
-    R.msda_torch(v64, shapes, starts, l64, a64, f32_coords=True).backward(g64)
+    fwd = R.msda_torch(v64, shapes, starts, l64, a64, f32_coords=True)
+    fwd.backward(g64)
     va, aa = value.double().abs().requires_grad_(), attn.double().abs().requires_grad_()
-    R.msda_torch(va, shapes, starts, loc_o, aa, f32_coords=True).backward(g64.abs())
+    fwd_a = R.msda_torch(va, shapes, starts, loc_o, aa, f32_coords=True)
+    fwd_a.backward(g64.abs())
     # loc magnitude and the geometry of the negative control
     ga = g64.abs().reshape(bs, Q, heads, dim)
     A_loc = torch.zeros(bs, Q, heads, L, P, 2, dtype=torch.float64)
@@ -440,7 +450,8 @@ def msda_reference(value, shapes, starts, loc, attn, gout):
         A_loc[:, :, :, l, :, 0] = (W * a * T).reshape(bs, Q, heads, P)
         A_loc[:, :, :, l, :, 1] = (H * a * T).reshape(bs, Q, heads, P)
         geo[l] = (taps, bi, qi, hi_)
-    return {"feat": (v64.grad, va.grad), "w": (a64.grad, aa.grad), "loc": (l64.grad, A_loc), "geo": geo}
+    return {"feat": (v64.grad, va.grad), "w": (a64.grad, aa.grad), "loc": (l64.grad, A_loc), "geo": geo,
+            "out": (fwd.detach(), fwd_a.detach())}
 
 
 def msda_drop_one_tap(ref, value, shapes, starts, loc, attn, gout):
@@ -472,11 +483,14 @@ def run_msda(value, shapes, starts, loc, attn, gout, need=(True, True, True)):
     v, l, a = value.to(DEV).requires_grad_(need[0]), loc.to(DEV).requires_grad_(need[1]), attn.to(DEV).requires_grad_(need[2])
     out = F32.apply(v, torch.tensor(shapes, device=DEV), torch.tensor(starts, device=DEV), l, a, 64)
     out.backward(gout.to(DEV))
-    return v.grad, l.grad, a.grad
+    return v.grad, l.grad, a.grad, out.detach()
 
 
 def msda_compare(name, ref, got, case):
-    gv, gl, ga = got
+    """got: (grad_value, grad_loc, grad_attn[, forward output])"""
+    gv, gl, ga, *fwd = got
+    if fwd:
+        check(f"{name} out", "feat", fwd[0], *ref["out"])
     check(f"{name} value", "feat", gv, *ref["feat"])
     check(f"{name} loc", "loc", gl, *ref["loc"])
     check(f"{name} attn", "w", ga, *ref["w"])
@@ -541,7 +555,7 @@ def test_msda_bwd_autograd_plumbing():
     out = F32.apply(value.to(DEV), sh, st, loc.to(DEV), a2, 64)
     (out.permute(1, 0, 2) * G.to(DEV)).sum().backward()
     check("msda permuted attn", "w", a2.grad, *ref["w"])
-    _, _, ga = run_msda(value, shapes, starts, loc, attn, G.permute(1, 0, 2).contiguous())
+    _, _, ga, _ = run_msda(value, shapes, starts, loc, attn, G.permute(1, 0, 2).contiguous())
     assert torch.equal(ga, a2.grad)
 
 

@@ -35,6 +35,8 @@
  *                        models/racformer_transformer.py:589-603
  *   rac_sasa_fwd      <- ScaleAdaptiveSelfAttention.inner_forward's mask + attention product
  *                        models/racformer_transformer.py:296-335
+ *   rac_sasa_fwd_ex / rac_sasa_bwd <- the same forward saving each row's log-sum-exp, and its backward (autograd of the
+ *                        reference's float-mask nn.MultiheadAttention in q, k, v and tau; the distances are no_grad there)
  *   rac_decode_fwd    <- NMSFreeCoder.decode_single + get_bboxes, models/bbox/coders/nms_free_coder.py:37-88,
  *                        models/racformer_head.py:488-507
  *   rac_outproj_fwd / rac_gemm_split_pack_fwd <- AdaptiveMixing.out_proj (nn.Linear 32768 -> 256), models/racformer_transformer.py:566,606
@@ -57,7 +59,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 10
+#define RAC_ABI_VERSION 11
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -213,6 +215,23 @@ int rac_bev_sampling_multi_q16_fwd(int nstreams, const void *const *values, cons
  *   v_mfma_f32_16x16x4_f32 (exact fp32); larger Q: an LDS-tiled fp32 VALU kernel. */
 int rac_sasa_fwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table, float *out,
                  int ld_qkv, int ld_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream);
+
+/* rac_sasa_fwd that also writes lse : device f32 [B,heads,Q], the log-sum-exp m + log(l) of every query row's logits
+ * (NULL: nothing more is written).  `out` is bit-identical to rac_sasa_fwd's with or without lse. */
+int rac_sasa_fwd_ex(const float *qkv, const float *tau, const float *query_bbox, const float *box_table, float *out,
+                    float *lse, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream);
+
+/* Backward of rac_sasa_fwd in qkv and tau (none for query_bbox: the reference forms the distances under no_grad).
+ * qkv, tau, query_bbox, box_table, pc_range, B, Q, heads, dim: as given to rac_sasa_fwd_ex; out [B,Q,heads*dim] and
+ * lse [B,heads,Q]: what it wrote; grad_out: device f32 [B,Q,heads*dim] (contiguous).
+ *   grad_qkv : device f32, token row (b,q) at grad_qkv + (b*Q+q)*ld_grad_qkv receiving dq|dk|dv ([heads, dim] each; even ld)
+ *   grad_tau : device f32, token row at grad_tau + (b*Q+q)*ld_grad_tau receiving the `heads` values of dtau
+ * The two may be column slices of one [B,Q,3*heads*dim+heads] buffer (the gradient of the in_proj + gen_tau GEMM output).
+ * Every element of the two is written once (no accumulation, no atomics: bit-reproducible); S is recomputed from lse,
+ * nothing of size Q x Q is stored.  dim must be 32, Q <= 6144.  No host synchronisation, no allocation. */
+int rac_sasa_bwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table, const float *out,
+                 const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau, int ld_qkv, int ld_tau,
+                 int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream);
 
 /* Layouts of the f16 hi / lo activation images that rac_add_ln_fwd and rac_rowgemm_fwd can emit beside their fp32 rows */
 enum {

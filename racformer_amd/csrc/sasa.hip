@@ -27,6 +27,7 @@ struct SasaArgs {
     const float *qbox;  // [B,Q,10]
     const float *box;   // optional [B,Q,8] from rac_box_prep_fwd (cx, cy, ...): skips the trig prologue
     float *out;         // [B,Q,H*d]
+    float *lse;         // optional [B,H,Q]: log-sum-exp of every query row's logits (rac_sasa_fwd_ex)
     float pc[6];
     int B, Q, H, ld_tau, ld_qkv;
     int row_blocks;
@@ -162,6 +163,8 @@ __global__ __launch_bounds__(256) void sasa_d32_kernel(const SasaArgs a)
         m = mn;
     }
     if (live) {
+        if (a.lse && r == 0)
+            a.lse[((size_t)b * H + h) * Q + i] = m + logf(l);
         // lane r writes channels 2r, 2r+1 (all lanes hold the merged state)
         const float inv = 1.f / l;
         float o0 = 0.f, o1 = 0.f;
@@ -189,6 +192,25 @@ __global__ __launch_bounds__(256) void sasa_d32_kernel(const SasaArgs a)
 typedef float sasa_f4 __attribute__((ext_vector_type(4)));
 #define SASA_NT 16 /* key tiles per wave: Q <= 4*16*16 = 1024 */
 
+// The centres (metres) of batch element b's Q boxes into LDS, by the workgroup's 256 threads: from the box table when there
+// is one, else decode_bbox(theta_d2xy(query_bbox))[:2] here.
+__device__ __forceinline__ void sasa_centres(float *scen, const float *box, const float *qbox, const float *pc, int b, int Q)
+{
+    for (int j = threadIdx.x; j < Q; j += 256) {
+        if (box) {
+            scen[2 * j] = box[((size_t)b * Q + j) * 8];
+            scen[2 * j + 1] = box[((size_t)b * Q + j) * 8 + 1];
+        } else {
+            const float *qb = qbox + ((size_t)b * Q + j) * 10;
+            const float ang = qb[0] * SASA_TWO_PI, rad = qb[1] * 65.0f;
+            const float xn = fminf(fmaxf((51.2f + rad * cosf(ang)) / 102.4f, 0.f), 1.f);
+            const float yn = fminf(fmaxf((51.2f + rad * sinf(ang)) / 102.4f, 0.f), 1.f);
+            scen[2 * j] = xn * (pc[3] - pc[0]) + pc[0];
+            scen[2 * j + 1] = yn * (pc[4] - pc[1]) + pc[1];
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
 {
     extern __shared__ float smem[];
@@ -205,19 +227,7 @@ __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
     const size_t tok = (size_t)b * Q;
     const int ld = a.ld_qkv;
 
-    for (int j = tid; j < Q; j += 256) {
-        if (a.box) {
-            scen[2 * j] = a.box[((size_t)b * Q + j) * 8];
-            scen[2 * j + 1] = a.box[((size_t)b * Q + j) * 8 + 1];
-        } else {
-            const float *qb = a.qbox + ((size_t)b * Q + j) * 10;
-            const float ang = qb[0] * SASA_TWO_PI, rad = qb[1] * 65.0f;
-            const float xn = fminf(fmaxf((51.2f + rad * cosf(ang)) / 102.4f, 0.f), 1.f);
-            const float yn = fminf(fmaxf((51.2f + rad * sinf(ang)) / 102.4f, 0.f), 1.f);
-            scen[2 * j] = xn * (a.pc[3] - a.pc[0]) + a.pc[0];
-            scen[2 * j + 1] = yn * (a.pc[4] - a.pc[1]) + a.pc[1];
-        }
-    }
+    sasa_centres(scen, a.box, a.qbox, a.pc, b, Q);
     // this lane's query column
     const int qi = rb * SASA_ROWS + li;
     const int qc = qi < Q ? qi : Q - 1;
@@ -348,22 +358,26 @@ __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
             }
             *reinterpret_cast<float2 *>(a.out + (tok + qrow) * (size_t)(H * SASA_D) + h * SASA_D + cp) =
                 make_float2(o0 / l, o1 / l);
+            if (a.lse && cp == 0) {
+                const float m = fmaxf(fmaxf(sred[qq], sred[16 + qq]), fmaxf(sred[32 + qq], sred[48 + qq]));
+                a.lse[((size_t)b * H + h) * Q + qrow] = m + logf(l);
+            }
         }
     }
 }
 
-extern "C" int rac_sasa_fwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
-                            float *out, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim, const float *pc_range,
-                            void *stream)
+extern "C" int rac_sasa_fwd_ex(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                               float *out, float *lse, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim,
+                               const float *pc_range, void *stream)
 {
-    RAC_CHECK_ARG(dim == SASA_D, "rac_sasa_fwd: head dim %d (the kernel is built for %d)", dim, SASA_D);
-    RAC_CHECK_ARG(B >= 0 && Q >= 0 && heads >= 1 && ld_tau >= heads && ld_qkv >= 3 * heads * dim && ld_qkv % 4 == 0, "rac_sasa_fwd: bad sizes B=%d Q=%d heads=%d", B, Q, heads);
-    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "rac_sasa_fwd: Q=%d too large for the LDS centre table", Q);
+    RAC_CHECK_ARG(dim == SASA_D, "rac_sasa_fwd_ex: head dim %d (the kernel is built for %d)", dim, SASA_D);
+    RAC_CHECK_ARG(B >= 0 && Q >= 0 && heads >= 1 && ld_tau >= heads && ld_qkv >= 3 * heads * dim && ld_qkv % 4 == 0, "rac_sasa_fwd_ex: bad sizes B=%d Q=%d heads=%d", B, Q, heads);
+    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "rac_sasa_fwd_ex: Q=%d too large for the LDS centre table", Q);
     if (B == 0 || Q == 0)
         return 0;
-    RAC_CHECK_ARG(qkv && tau && query_bbox && out && pc_range, "rac_sasa_fwd: null pointer");
+    RAC_CHECK_ARG(qkv && tau && query_bbox && out && pc_range, "rac_sasa_fwd_ex: null pointer");
     SasaArgs a;
-    a.qkv = qkv; a.tau = tau; a.qbox = query_bbox; a.box = box_table; a.out = out;
+    a.qkv = qkv; a.tau = tau; a.qbox = query_bbox; a.box = box_table; a.out = out; a.lse = lse;
     for (int i = 0; i < 6; ++i)
         a.pc[i] = pc_range[i];
     a.B = B; a.Q = Q; a.H = heads; a.ld_tau = ld_tau; a.ld_qkv = ld_qkv;
@@ -377,5 +391,265 @@ extern "C" int rac_sasa_fwd(const float *qkv, const float *tau, const float *que
         const size_t lds = (cen + 2 * SASA_TILE * SASA_KS) * sizeof(float);
         hipLaunchKernelGGL(sasa_d32_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
     }
-    return rac_launch_status("rac_sasa_fwd");
+    return rac_launch_status("rac_sasa_fwd_ex");
+}
+
+extern "C" int rac_sasa_fwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                            float *out, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim, const float *pc_range,
+                            void *stream)
+{
+    return rac_sasa_fwd_ex(qkv, tau, query_bbox, box_table, out, nullptr, ld_qkv, ld_tau, B, Q, heads, dim, pc_range, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Backward.  With s_ij = (q_i . k_j)/sqrt(d) - r_ij tau_i, P = exp(s - lse), D_i = dO_i . O_i:
+//   dP = dO V^T,  dS = P o (dP - D),  dq = dS K / sqrt(d),  dk = dS^T Q / sqrt(d),  dv = P^T dO,  dtau_i = -sum_j dS_ij r_ij.
+// S is recomputed from the forward's lse: nothing of size Q x Q touches HBM.  One launch, two workgroup roles, each the
+// forward's MFMA structure (v_mfma_f32_16x16x4_f32, exact fp32) streamed over all tiles of the other index, so every Q the
+// forward accepts runs here (the statistics come in; no tile of S is kept across the loop):
+//   row role    (blocks [0, n)):  16 queries of one (batch, head); the 4 waves take the 16-key tiles round-robin.
+//     S^T and dP^T [16 keys x 16 queries] = K.Q^T and V.dO^T (A: key rows, B: the workgroup's query rows, as the forward), and
+//     dS^T in the same accumulator layout is the B operand of dq^T [32 ch x 16 queries] = K^T . dS^T.  dtau is a register sum.
+//   column role (blocks [n, 2n)): 16 keys of one (batch, head); the 4 waves take the 16-query tiles round-robin.
+//     S and dP [16 queries x 16 keys] = Q.K^T and dO.V^T (A: query rows, B: the workgroup's key rows), so P and dS are the B
+//     operands of dv^T [32 ch x 16 keys] = dO^T . P and dk^T = (Q/sqrt(d))^T . dS.
+// Each role forms D_i itself from dO and O (a 32-wide dot, the same lanes and order in both), so the roles are independent.
+// The four waves' partial sums are combined through LDS in a fixed order: every output element has one writer and no
+// atomics, so the result is bit-reproducible.
+struct SasaBwdArgs {
+    const float *qkv, *tau, *qbox, *box, *out, *lse, *gout;
+    float *gqkv, *gtau;
+    float pc[6];
+    int B, Q, H, ld_qkv, ld_tau, ld_gqkv, ld_gtau;
+    int row_blocks;
+};
+
+#define SASA_MFMA8(acc, a4, b4)                                                       \
+    do {                                                                              \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0].x, b4[0].x, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0].y, b4[0].y, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0].z, b4[0].z, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0].w, b4[0].w, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1].x, b4[1].x, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1].y, b4[1].y, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1].z, b4[1].z, acc, 0, 0, 0);   \
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[1].w, b4[1].w, acc, 0, 0, 0);   \
+    } while (0)
+
+// channels 16u + 4*lk .. +3 (u = 0, 1) of a token row: the 8 k-steps of a 32-deep product as the forward assigns them
+__device__ __forceinline__ void sasa_row8(rac_f4 (&v)[2], const float *row, int lk, float mul)
+{
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        v[u] = rac_ld4(row + 16 * u + 4 * lk);
+        v[u].x *= mul; v[u].y *= mul; v[u].z *= mul; v[u].w *= mul;
+    }
+}
+
+__device__ __forceinline__ float sasa_dot8(const rac_f4 (&a)[2], const rac_f4 (&b)[2])
+{
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+        s += a[u].x * b[u].x + a[u].y * b[u].y + a[u].z * b[u].z + a[u].w * b[u].w;
+    return s;
+}
+
+// the four waves' [32 ch x 16] accumulators -> so[wave][ch][col]; after the barrier thread t sums column t>>4, channels
+// 2(t&15), +1 over the waves in a fixed order
+__device__ __forceinline__ float2 sasa_combine(float *so, const sasa_f4 (&acc)[2], int wave, int li, int lk)
+{
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            so[(wave * 32 + 16 * c + 4 * lk + r) * 16 + li] = acc[c][r];
+    __syncthreads();
+    const int col = threadIdx.x >> 4, cp = (threadIdx.x & 15) * 2;
+    float o0 = 0.f, o1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        o0 += so[(w * 32 + cp) * 16 + col];
+        o1 += so[(w * 32 + cp + 1) * 16 + col];
+    }
+    return make_float2(o0, o1);
+}
+
+__global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
+{
+    extern __shared__ float smem[];
+    float *scen = smem;                         // [Q][2] centres (metres)
+    float *sred = smem + 2 * ((a.Q + 1) & ~1);  // [4 waves][16] dtau partials
+    float *so = sred + 4 * 16;                  // [4 waves][32 ch][16]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int nblk = a.B * a.H * a.row_blocks;
+    const bool row_role = (int)blockIdx.x < nblk;
+    int bid = row_role ? blockIdx.x : blockIdx.x - nblk;
+    const int rb = bid % a.row_blocks; bid /= a.row_blocks;
+    const int h = bid % a.H;
+    const int b = bid / a.H;
+    const int Q = a.Q, H = a.H;
+    const size_t tok = (size_t)b * Q;
+    const int ld = a.ld_qkv, ldo = H * SASA_D;
+    const float scale = 0.17677669529663687f;
+    const float *lse = a.lse + ((size_t)b * H + h) * Q;
+    const int ntiles = (Q + 15) >> 4;
+
+    sasa_centres(scen, a.box, a.qbox, a.pc, b, Q);
+    // this lane's row of the workgroup's 16 (query in the row role, key in the column role)
+    const int own = rb * SASA_ROWS + li;
+    const int oc = own < Q ? own : Q - 1;
+    __syncthreads();
+
+    if (row_role) {
+        rac_f4 qs[2], go[2], o4[2];
+        sasa_row8(qs, a.qkv + (tok + oc) * ld + h * SASA_D, lk, scale);
+        sasa_row8(go, a.gout + (tok + oc) * ldo + h * SASA_D, lk, 1.f);
+        sasa_row8(o4, a.out + (tok + oc) * ldo + h * SASA_D, lk, 1.f);
+        float Di = sasa_dot8(go, o4);
+        Di += __shfl_xor(Di, 16, 64);
+        Di += __shfl_xor(Di, 32, 64);
+        const float tau = a.tau[(tok + oc) * a.ld_tau + h], lse_i = lse[oc];
+        const float cqx = scen[2 * oc], cqy = scen[2 * oc + 1];
+        sasa_f4 dq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        float dtau = 0.f;
+        for (int tile = wave; tile < ntiles; tile += 4) {
+            const int k0 = tile * 16;
+            const int kr = k0 + li < Q ? k0 + li : Q - 1;
+            rac_f4 kA[2], vA[2];
+            sasa_row8(kA, a.qkv + (tok + kr) * ld + (H + h) * SASA_D, lk, 1.f);
+            sasa_row8(vA, a.qkv + (tok + kr) * ld + (2 * H + h) * SASA_D, lk, 1.f);
+            // K^T operand of dq: K[key k0 + 4lk + i][channel li (+16)]
+            float kt[2][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int key = k0 + 4 * lk + i;
+                const float *kp = a.qkv + (tok + (key < Q ? key : Q - 1)) * ld + (H + h) * SASA_D;
+                kt[0][i] = kp[li];
+                kt[1][i] = kp[16 + li];
+            }
+            sasa_f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+            SASA_MFMA8(s, kA, qs);     // s[r]  = S^T[key k0 + 4lk + r][query li]
+            SASA_MFMA8(dp, vA, go);    // dp[r] = dP^T[same]
+            sasa_f4 ds;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = k0 + 4 * lk + r;
+                const int kc = key < Q ? key : Q - 1;
+                const float dx = cqx - scen[2 * kc], dy = cqy - scen[2 * kc + 1];
+                const float dist = sqrtf(dx * dx + dy * dy);
+                const float p = key < Q ? expf(s[r] - dist * tau - lse_i) : 0.f;
+                ds[r] = p * (dp[r] - Di);
+                dtau -= ds[r] * dist;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                dq[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt[0][i], ds[i], dq[0], 0, 0, 0);
+                dq[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(kt[1][i], ds[i], dq[1], 0, 0, 0);
+            }
+        }
+        dtau += __shfl_xor(dtau, 16, 64);
+        dtau += __shfl_xor(dtau, 32, 64);
+        if (lk == 0)
+            sred[wave * 16 + li] = dtau;
+        const float2 g = sasa_combine(so, dq, wave, li, lk);   // (its barrier also publishes sred)
+        const int col = tid >> 4, cp = (tid & 15) * 2, qrow = rb * SASA_ROWS + col;
+        if (qrow < Q) {
+            *reinterpret_cast<float2 *>(a.gqkv + (tok + qrow) * a.ld_gqkv + h * SASA_D + cp) = make_float2(g.x * scale, g.y * scale);
+            if (cp == 0)
+                a.gtau[(tok + qrow) * a.ld_gtau + h] = (sred[col] + sred[16 + col]) + (sred[32 + col] + sred[48 + col]);
+        }
+    } else {
+        rac_f4 kB[2], vB[2];
+        sasa_row8(kB, a.qkv + (tok + oc) * ld + (H + h) * SASA_D, lk, 1.f);
+        sasa_row8(vB, a.qkv + (tok + oc) * ld + (2 * H + h) * SASA_D, lk, 1.f);
+        const float ckx = scen[2 * oc], cky = scen[2 * oc + 1];
+        sasa_f4 dk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        sasa_f4 dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        for (int tile = wave; tile < ntiles; tile += 4) {
+            const int q0 = tile * 16;
+            const int qr = q0 + li < Q ? q0 + li : Q - 1;
+            rac_f4 qA[2], gA[2], oA[2];
+            sasa_row8(qA, a.qkv + (tok + qr) * ld + h * SASA_D, lk, scale);
+            sasa_row8(gA, a.gout + (tok + qr) * ldo + h * SASA_D, lk, 1.f);
+            sasa_row8(oA, a.out + (tok + qr) * ldo + h * SASA_D, lk, 1.f);
+            // D of query q0 + li (as the row role forms it), then moved to the lanes that hold query q0 + 4lk + r
+            float Dq = sasa_dot8(gA, oA);
+            Dq += __shfl_xor(Dq, 16, 64);
+            Dq += __shfl_xor(Dq, 32, 64);
+            // Q^T and dO^T operands: row q0 + 4lk + i, channel li (+16)
+            float qt[2][4], gt[2][4], tq[4], lq[4], cx[4], cy[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int qi = q0 + 4 * lk + i;
+                const size_t t = tok + (qi < Q ? qi : Q - 1);
+                const float *qp = a.qkv + t * ld + h * SASA_D;
+                const float *gp = a.gout + t * ldo + h * SASA_D;
+                qt[0][i] = qp[li] * scale; qt[1][i] = qp[16 + li] * scale;
+                gt[0][i] = gp[li]; gt[1][i] = gp[16 + li];
+                tq[i] = a.tau[t * a.ld_tau + h];
+                lq[i] = lse[t - tok];
+                cx[i] = scen[2 * (t - tok)]; cy[i] = scen[2 * (t - tok) + 1];
+            }
+            sasa_f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+            SASA_MFMA8(s, qA, kB);     // s[r]  = S[query q0 + 4lk + r][key li]
+            SASA_MFMA8(dp, gA, vB);    // dp[r] = dP[same]
+            sasa_f4 p, ds;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float D = __shfl(Dq, 4 * lk + r, 64);
+                const float dx = cx[r] - ckx, dy = cy[r] - cky;
+                const float dist = sqrtf(dx * dx + dy * dy);
+                p[r] = q0 + 4 * lk + r < Q ? expf(s[r] - dist * tq[r] - lq[r]) : 0.f;
+                ds[r] = p[r] * (dp[r] - D);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                dv[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(gt[0][i], p[i], dv[0], 0, 0, 0);
+                dv[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(gt[1][i], p[i], dv[1], 0, 0, 0);
+                dk[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(qt[0][i], ds[i], dk[0], 0, 0, 0);
+                dk[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(qt[1][i], ds[i], dk[1], 0, 0, 0);
+            }
+        }
+        const int col = tid >> 4, cp = (tid & 15) * 2, krow = rb * SASA_ROWS + col;
+        float *gk = a.gqkv + (tok + krow) * a.ld_gqkv;
+        const float2 gkv = sasa_combine(so, dk, wave, li, lk);
+        if (krow < Q)
+            *reinterpret_cast<float2 *>(gk + (H + h) * SASA_D + cp) = gkv;
+        __syncthreads();   // so is reused
+        const float2 gvv = sasa_combine(so, dv, wave, li, lk);
+        if (krow < Q)
+            *reinterpret_cast<float2 *>(gk + (2 * H + h) * SASA_D + cp) = gvv;
+    }
+}
+
+extern "C" int rac_sasa_bwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                            const float *out, const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau,
+                            int ld_qkv, int ld_tau, int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim,
+                            const float *pc_range, void *stream)
+{
+    RAC_CHECK_ARG(dim == SASA_D, "rac_sasa_bwd: head dim %d (the kernel is built for %d)", dim, SASA_D);
+    RAC_CHECK_ARG(B >= 0 && Q >= 0 && heads >= 1 && ld_tau >= heads && ld_qkv >= 3 * heads * dim && ld_qkv % 4 == 0 &&
+                      ld_grad_qkv >= 3 * heads * dim && ld_grad_qkv % 2 == 0 && ld_grad_tau >= heads,
+                  "rac_sasa_bwd: bad sizes B=%d Q=%d heads=%d ld_qkv=%d ld_tau=%d ld_grad_qkv=%d ld_grad_tau=%d", B, Q, heads,
+                  ld_qkv, ld_tau, ld_grad_qkv, ld_grad_tau);
+    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "rac_sasa_bwd: Q=%d too large for the LDS centre table", Q);
+    if (B == 0 || Q == 0)
+        return 0;
+    RAC_CHECK_ARG(qkv && tau && query_bbox && out && lse && grad_out && grad_qkv && grad_tau && pc_range,
+                  "rac_sasa_bwd: null pointer");
+    SasaBwdArgs a;
+    a.qkv = qkv; a.tau = tau; a.qbox = query_bbox; a.out = out; a.lse = lse; a.gout = grad_out;
+    // the centres the forward used: its VALU kernel (Q > 1024) always decodes the boxes itself
+    a.box = Q <= 4 * SASA_NT * 16 ? box_table : nullptr;
+    a.gqkv = grad_qkv; a.gtau = grad_tau;
+    for (int i = 0; i < 6; ++i)
+        a.pc[i] = pc_range[i];
+    a.B = B; a.Q = Q; a.H = heads; a.ld_qkv = ld_qkv; a.ld_tau = ld_tau; a.ld_gqkv = ld_grad_qkv; a.ld_gtau = ld_grad_tau;
+    a.row_blocks = (Q + SASA_ROWS - 1) / SASA_ROWS;
+    const int nb = 2 * B * heads * a.row_blocks;
+    const size_t lds = ((size_t)2 * ((Q + 1) & ~1) + 4 * 16 + 4 * 32 * 16) * sizeof(float);
+    hipLaunchKernelGGL(sasa_bwd_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
+    return rac_launch_status("rac_sasa_bwd");
 }

@@ -210,26 +210,67 @@ def bev_sampling_multi_fused(streams, hw, query_bbox, time_diff, num_frames, num
     return out
 
 
-def sasa_fused(qkv, tau, query_bbox, num_heads, pc_range, box_table=None):
+def sasa_fused(qkv, tau, query_bbox, num_heads, pc_range, box_table=None, lse_out=None):
     """qkv [B,Q,3*E] (q|k|v, each [heads, E/heads]; may be a column slice), tau [B,Q,heads] ->
-    attention output [B,Q,E] before out_proj."""
+    attention output [B,Q,E] before out_proj.
+    ``lse_out``: optional contiguous f32 [B,heads,Q] that receives every query row's log-sum-exp (rac_sasa_fwd_ex, for
+    sasa_backward); the output is bit-identical either way."""
     _lib.require_gpu(query_bbox, what="sasa_fused")
     B, Q, _ = query_bbox.shape
     E = qkv.shape[-1] // 3
     p_qkv, ld_qkv = _rows(qkv, 3 * E, "sasa_fused(qkv)")
     p_tau, ld_tau = _rows(tau, num_heads, "sasa_fused(tau)")
+    if lse_out is not None:
+        _lib.require_gpu(lse_out, what="sasa_fused(lse_out)")
+        if tuple(lse_out.shape) != (B, num_heads, Q) or lse_out.dtype != torch.float32:
+            raise RuntimeError(f"sasa_fused: lse_out must be float32 [{B},{num_heads},{Q}]")
     out = torch.empty(B, Q, E, device=qkv.device, dtype=torch.float32)
     pc = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
     ev = _lib.timer.record("sasa_fwd") if _lib.timer is not None else None
     if ev:
         ev[0].record()
-    rc = _lib.lib().rac_sasa_fwd(p_qkv, p_tau, _lib.ptr(query_bbox), _lib.ptr(box_table) if box_table is not None else None,
-                                 _lib.ptr(out), ld_qkv, ld_tau, B, Q, num_heads,
-                                 E // num_heads, pc, _lib.stream_ptr())
+    box = _lib.ptr(box_table) if box_table is not None else None
+    if lse_out is None:
+        rc = _lib.lib().rac_sasa_fwd(p_qkv, p_tau, _lib.ptr(query_bbox), box, _lib.ptr(out), ld_qkv, ld_tau, B, Q, num_heads,
+                                     E // num_heads, pc, _lib.stream_ptr())
+    else:
+        rc = _lib.lib().rac_sasa_fwd_ex(p_qkv, p_tau, _lib.ptr(query_bbox), box, _lib.ptr(out), _lib.ptr(lse_out), ld_qkv,
+                                        ld_tau, B, Q, num_heads, E // num_heads, pc, _lib.stream_ptr())
     if ev:
         ev[1].record()
-    _lib.check(rc, "rac_sasa_fwd")
+    _lib.check(rc, "rac_sasa_fwd" if lse_out is None else "rac_sasa_fwd_ex")
     return out
+
+
+def sasa_backward(qkv, tau, query_bbox, num_heads, pc_range, out, lse, grad_out, box_table=None, grad_qkv=None, grad_tau=None):
+    """Backward of sasa_fused (rac_sasa_bwd): qkv, tau, query_bbox, box_table as given to it, out and lse what it returned and
+    wrote, grad_out [B,Q,E] -> (grad_qkv [B,Q,3*E], grad_tau [B,Q,heads]).  ``grad_qkv`` / ``grad_tau``: destinations with
+    unit inner stride and a row stride of their own (e.g. the two column slices of one [B,Q,3*E+heads] buffer); allocated as
+    that one buffer when not given.  Every element of both is written."""
+    _lib.require_gpu(query_bbox, out, lse, grad_out, what="sasa_backward")
+    B, Q, _ = query_bbox.shape
+    E = qkv.shape[-1] // 3
+    p_qkv, ld_qkv = _rows(qkv, 3 * E, "sasa_backward(qkv)")
+    p_tau, ld_tau = _rows(tau, num_heads, "sasa_backward(tau)")
+    for t_, shape, what in ((out, (B, Q, E), "out"), (grad_out, (B, Q, E), "grad_out"), (lse, (B, num_heads, Q), "lse")):
+        if tuple(t_.shape) != shape or t_.dtype != torch.float32:
+            raise RuntimeError(f"sasa_backward: {what} must be float32 {list(shape)}")
+    if grad_qkv is None or grad_tau is None:
+        wide = torch.empty(B, Q, 3 * E + num_heads, device=qkv.device, dtype=torch.float32)
+        grad_qkv, grad_tau = wide[..., :3 * E], wide[..., 3 * E:]
+    p_gqkv, ld_gqkv = _rows(grad_qkv, 3 * E, "sasa_backward(grad_qkv)")
+    p_gtau, ld_gtau = _rows(grad_tau, num_heads, "sasa_backward(grad_tau)")
+    pc = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
+    ev = _lib.timer.record("sasa_bwd") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_sasa_bwd(p_qkv, p_tau, _lib.ptr(query_bbox), _lib.ptr(box_table) if box_table is not None else None,
+                                 _lib.ptr(out), _lib.ptr(lse), _lib.ptr(grad_out), p_gqkv, p_gtau, ld_qkv, ld_tau, ld_gqkv,
+                                 ld_gtau, B, Q, num_heads, E // num_heads, pc, _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_sasa_bwd")
+    return grad_qkv, grad_tau
 
 
 def mixing_fused(x, params, in_points, n_groups, out_points=128, eps=1e-5, split=False, param_scale=1.0, f16x3=False, out=None):

@@ -32,7 +32,7 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
                     pe_head, refine_fused, row_gemm,
-                    row_seg, rowgemm_launch, sampling4d_fused, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
+                    row_seg, rowgemm_launch, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
 from .msda import msda_backward, msda_forward
 from .msmv import msmv_backward, msmv_forward, msmv_v2_backward, msmv_v2_forward
 
@@ -137,10 +137,20 @@ class ScaleAdaptiveSelfAttention(nn.Module):
         if self.fused and pre_attn_mask is None and self.embed_dims // self.num_heads == 32:
             # one GEMM for in_proj + gen_tau, one HIP kernel for mask + QK^T + softmax + AV
             p = self.attention.attn
+            E = self.embed_dims
+            params = (p.in_proj_weight, p.in_proj_bias, self.gen_tau.weight, self.gen_tau.bias)
+            if torch.is_grad_enabled() and (query_feat.requires_grad or any(t.requires_grad for t in params)):
+                # training: through _SASACore (rac_sasa_fwd_ex + rac_sasa_bwd).  A prepared operand without autograd history
+                # (the decoder layer's cache) would cut the weight gradients: the wide operand is then built from the live
+                # parameters.
+                if prepared_w is None or not (prepared_w[0].requires_grad and prepared_w[1].requires_grad):
+                    prepared_w = self.wide_in_proj()
+                lin = F.linear(query_feat, prepared_w[0], prepared_w[1])
+                o = _SASACore.apply(lin, query_bbox.detach().contiguous(), None, self.num_heads, self.pc_range)
+                return query_feat + p.out_proj(o)
             if prepared_w is None:
                 prepared_w = self.wide_in_proj()
             lin = F.linear(query_feat, prepared_w[0], prepared_w[1])
-            E = self.embed_dims
             o = sasa_fused(lin[..., :3 * E], lin[..., 3 * E:], query_bbox.contiguous(), self.num_heads, self.pc_range)
             return query_feat + p.out_proj(o)
         return self.forward_unfused(query_bbox, query_feat, pre_attn_mask)
@@ -330,6 +340,33 @@ class _BEVAttendGather(torch.autograd.Function):
         value, loc, attn = ctx.saved_tensors
         grad_value, grad_loc, grad_attn = msda_backward(grad_out, value, ctx.shapes, [0], loc, attn)
         return grad_value, grad_loc, grad_attn, None
+
+
+class _SASACore(torch.autograd.Function):
+    """The SASA core: apply(lin [B,Q,3E+heads] = q|k|v|tau, query_bbox [B,Q,10], box_table [B,Q,8] or None, heads, pc_range)
+    -> O [B,Q,E] before out_proj.  The forward is rac_sasa_fwd_ex (the output of rac_sasa_fwd, plus each row's log-sum-exp);
+    the backward rac_sasa_bwd, writing dq|dk|dv and dtau into one [B,Q,3E+heads] gradient of lin (no cat).  No gradient for
+    the boxes: the reference forms the distances under no_grad (calc_bbox_dists).  The launchers are looked up as this
+    module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, lin, query_bbox, box_table, num_heads, pc_range):
+        B, Q, W = lin.shape
+        E = (W - num_heads) // 3
+        lse = torch.empty(B, num_heads, Q, device=lin.device, dtype=torch.float32)
+        o = sasa_fused(lin[..., :3 * E], lin[..., 3 * E:], query_bbox, num_heads, pc_range, box_table=box_table, lse_out=lse)
+        ctx.num_heads, ctx.pc_range = num_heads, pc_range
+        ctx.save_for_backward(lin, query_bbox, box_table, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, grad_o):
+        lin, query_bbox, box_table, o, lse = ctx.saved_tensors
+        E = (lin.shape[-1] - ctx.num_heads) // 3
+        grad_lin = torch.empty(lin.shape, device=lin.device, dtype=lin.dtype)
+        sasa_backward(lin[..., :3 * E], lin[..., 3 * E:], query_bbox, ctx.num_heads, ctx.pc_range, o, lse, grad_o.contiguous(),
+                      box_table=box_table, grad_qkv=grad_lin[..., :3 * E], grad_tau=grad_lin[..., 3 * E:])
+        return grad_lin, None, None, None, None
 
 
 def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, image_w, aggregate=True,

@@ -9,9 +9,12 @@ decode -> (N>1) RCCL all-gather of the fixed-shape detections.  Inputs (FPN pyra
 weights) are resident in HBM before the timed region.  Data-parallel: every rank processes its
 own sample, so scaling is weak and `value` = samples of all ranks / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 (contract: see the task statement); `roofline` is for the
-dominant hand-written kernel (msmv sampling), timed live with HIP events on the launch stream;
-`cpu_baseline` is the CPU oracle (port of the reference's CPU forward) on this box's host cores.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the
+headline (`value`, `ms_per_step`, ...) and nothing else.  `--full` adds everything that needs work of its own after the timed
+region: `roofline` for the dominant hand-written kernel (msmv sampling), timed with HIP events on the launch stream; `mfma`;
+the one-plan latency and the lanes' bitwise check against a single plan; the operator stress set; the pregrouped and int16
+secondary figures; `cpu_baseline`, the CPU oracle (port of the reference's CPU forward) on the host's cores, and the parity of
+the benchmarked step against it.
 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment starts its own N ranks (one fresh process per GPU
 through torch.distributed.run, before this process has touched the GPU) and exits with their status; started by a launcher
@@ -324,8 +327,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--config", default="f8", choices=["f8", "f8_3cam"])
     ap.add_argument("--feature-dtype", default="f32", choices=["f32", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stress", action="store_true", help="skip the uniform-stress timing of the operator kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline: kernel rooflines, MFMA "
+                         "rates, one-plan latency, lanes vs one plan, stress set, secondary figures, CPU baseline and parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity against it")
+    ap.add_argument("--no-stress", action="store_true", help="with --full: skip the uniform-stress timing of the operator kernels")
     ap.add_argument("--stress-only", action="store_true", help="print the uniform-stress block alone (kernel A/B runs) and exit")
     ap.add_argument("--pregrouped", action="store_true",
                     help="feed the pyramid already in the sampling layout (producer-side layout, row f2): no regroup")
@@ -456,9 +462,9 @@ def main():
         step()
     fence()
     # Eager plan: inside the timed region only the dominant kernel is bracketed with HIP events (each pair costs a 5-10 us
-    # bubble); the other instrumented launches are timed in three extra, untimed steps below.  Captured plan: a graph holds
-    # no event brackets, so the timed region is K replays and the dominant kernel is bracketed in K eager steps of the same
-    # work right behind it (same kernels, same inputs, same stream).
+    # bubble); with --full the other instrumented launches are timed in three extra, untimed steps below.  Captured plan: a
+    # graph holds no event brackets, so the timed region is K replays and, with --full, the dominant kernel is bracketed in K
+    # eager steps of the same work right behind it (same kernels, same inputs, same stream).
     if captured is None:
         _lib.timer = _lib.KernelTimer(only=("sampling4d_fwd", "mixing_sampled_fwd", "msmv_fwd"))
     t0 = time.perf_counter()
@@ -470,6 +476,57 @@ def main():
     if args.dump_outputs and rank == 0:
         # before anything else runs: a captured plan's outputs are its graph's buffers, rewritten by its next replay
         dump_outputs(args.dump_outputs, *out)
+    per_rank_ms, slowest = [1e3 * elapsed / args.steps], elapsed
+    if world > 1:
+        mine = torch.tensor([elapsed], device=device, dtype=torch.float64)
+        allr = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(allr, mine)
+        per_rank_ms = [1e3 * float(t.item()) / args.steps for t in allr]
+        slowest = max(float(t.item()) for t in allr)      # max over ranks
+    result = {
+        "metric": "samples/sec (6-cam 704x256, 900 queries, f8)" if args.config == "f8"
+                  else "samples/sec (3-cam 704x256, 900 queries, f8)",
+        "value": world * args.steps / slowest,
+        "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * slowest / args.steps, "per_rank_ms_per_step": per_rank_ms,
+        # host-side time to enqueue one step (Python + launches, rank 0): close to ms_per_step means the host is the limiter
+        "host_enqueue_ms_per_step": 1e3 * host_elapsed / args.steps,
+        "submission": ("eager: one launch per kernel from Python" + (f" (graph capture failed: {capture_error})" if not args.no_graph and capture_error else ""))
+                      if captured is None else
+                      "HIP graph: the step's kernels captured once (racformer_amd/graph.py), one replay per step; metas staged in "
+                      "front of it, all-gather behind it" + (f"; {len(lanes)} plans on streams of their own, replayed round-robin, so "
+                      "that up to that many samples are in flight per GPU (the latency-bound launches of one sample run beside the "
+                      "bandwidth-bound ones of another)" if lanes else ""),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if fdt == torch.float32 else "bf16-features/f32-math", "data": "synthetic",
+        "arithmetic_note": "fp32 arithmetic and fp32-accurate results throughout; inputs (pyramid, BEV maps), queries and every output in "
+                           "fp32; the largest contractions run on the 16-bit matrix cores as split-precision products (operands = sums "
+                           "of f16/bf16 terms, fp32 accumulate, truncation <= 2^-22 relative); "
+                           + ("the two hoisted BEV value streams (internal tensors: value_proj's outputs) are stored as int16 mantissas "
+                              "with one power-of-two scale per (pixel, head) block of 64 channels (opt-in mode, NOT the product default)"
+                              if args.value_storage == "i16" else "fp32 storage everywhere (BEV value streams as the reference's fp32 maps)"),
+        "config": {"workload": f"racformer_r50_nuimg_704x256_{args.config} query-decoder hot path: regroup + 6 decoder "
+                               "layers + NMS-free decode, 1 sample/GPU/step",
+                   "queries": cfg.num_query, "cams": cfg.num_cams, "frames": cfg.num_frames,
+                   "levels": cfg.num_levels, "samples_per_gpu": 1, "samples_in_flight_per_gpu": max(1, args.in_flight if captured is not None else 1),
+                   # each lane holds a sample of its own (pyramid, BEV stacks, metas: synthetic seeds rank * lanes + lane)
+                   "distinct_inputs_per_lane": bool(lanes) and not args.same_inputs_per_lane,
+                   "sample_seeds_this_rank": [seed + i for i in range(len(lanes) or 1)] if not args.same_inputs_per_lane else [seed],
+                   "parallelism": f"dp{world}", "bev_value_stream_storage": "int16-block" if args.value_storage == "i16" else "f32",
+                   "pyramid_layout": "pregrouped [B*T*G,N,H,W,C]" if args.pregrouped else "reference [B,T*N,G*C,H,W] (regroup timed)"},
+    }
+
+    def emit():
+        if rank == 0:
+            print(json.dumps(result))
+        if use_pg:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return emit()
+
     single = lanes_match = None
     if captured is not None:
         if not lanes:
@@ -514,7 +571,6 @@ def main():
         eager_step()
     fence()
     aux, _lib.timer = _lib.timer, None
-    per_rank_ms = [1e3 * elapsed / args.steps]
     collective = None
     if use_pg:
         # the gathered block of this rank's slot is its local block, bit for bit
@@ -525,11 +581,6 @@ def main():
         collective = {"backend": dist.get_backend(), "world": world, "forced_at_world_1": bool(args.force_collective and world == 1),
                       "gathered_shape": list(gathered.shape), "own_slot_equals_local": bool(torch.equal(gathered[rank], local))}
     if world > 1:
-        mine = torch.tensor([elapsed], device=device, dtype=torch.float64)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank_ms = [1e3 * float(t.item()) / args.steps for t in allr]
-        elapsed = max(float(t.item()) for t in allr)      # max over ranks
         merged = dp.merge_interleaved(out[1], world)        # one sample per rank per step, dataset order
         assert tuple(merged.shape) == (world, 300, 11)
     # the dominant kernel: the stand-alone sampling kernel (rac_sampling4d_fwd); with decoder_layer.fuse_sampling_mixing = True
@@ -606,47 +657,11 @@ def main():
                          "peak_tflops": PEAK16 if peak == 16 else PEAK32, "frac": tf / (PEAK16 if peak == 16 else PEAK32)}
     sasa_ms = aux.mean_ms("sasa_fwd")
 
-    result = {
-        "metric": "samples/sec (6-cam 704x256, 900 queries, f8)" if args.config == "f8"
-                  else "samples/sec (3-cam 704x256, 900 queries, f8)",
-        "value": world * args.steps / elapsed,
-        "unit": "samples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "per_rank_ms_per_step": per_rank_ms,
-        # host-side time to enqueue one step (Python + launches, rank 0): close to ms_per_step means the host is the limiter
-        "host_enqueue_ms_per_step": 1e3 * host_elapsed / args.steps,
-        "submission": ("eager: one launch per kernel from Python" + (f" (graph capture failed: {capture_error})" if not args.no_graph and capture_error else ""))
-                      if captured is None else
-                      "HIP graph: the step's kernels captured once (racformer_amd/graph.py), one replay per step; metas staged in "
-                      "front of it, all-gather behind it" + (f"; {len(lanes)} plans on streams of their own, replayed round-robin, so "
-                      "that up to that many samples are in flight per GPU (the latency-bound launches of one sample run beside the "
-                      "bandwidth-bound ones of another)" if lanes else ""),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "collective": collective,
+    result.update({
+        "collective": collective,
         "one_sample_in_flight": single,
         # per lane: detections of the lane's last replay (run beside the other lanes) == the single-plan eager result on that lane's sample
         "lanes_match_single_plan_bitwise": lanes_match,
-        "dtype": "f32" if fdt == torch.float32 else "bf16-features/f32-math", "data": "synthetic",
-        "arithmetic_note": "fp32 arithmetic and fp32-accurate results throughout; inputs (pyramid, BEV maps), queries and every output in "
-                           "fp32; the largest contractions run on the 16-bit matrix cores as split-precision products (operands = sums "
-                           "of f16/bf16 terms, fp32 accumulate, truncation <= 2^-22 relative); "
-                           + ("the two hoisted BEV value streams (internal tensors: value_proj's outputs) are stored as int16 mantissas "
-                              "with one power-of-two scale per (pixel, head) block of 64 channels (opt-in mode, NOT the product default)"
-                              if args.value_storage == "i16" else "fp32 storage everywhere (BEV value streams as the reference's fp32 maps)"),
-        "config": {"workload": f"racformer_r50_nuimg_704x256_{args.config} query-decoder hot path: regroup + 6 decoder "
-                               "layers + NMS-free decode, 1 sample/GPU/step",
-                   "queries": cfg.num_query, "cams": cfg.num_cams, "frames": cfg.num_frames,
-                   "levels": cfg.num_levels, "samples_per_gpu": 1, "samples_in_flight_per_gpu": max(1, args.in_flight if captured is not None else 1),
-                   # each lane holds a sample of its own (pyramid, BEV stacks, metas: synthetic seeds rank * lanes + lane)
-                   "distinct_inputs_per_lane": bool(lanes) and not args.same_inputs_per_lane,
-                   "sample_seeds_this_rank": [seed + i for i in range(len(lanes) or 1)] if not args.same_inputs_per_lane else [seed],
-                   "parallelism": f"dp{world}", "bev_value_stream_storage": "int16-block" if args.value_storage == "i16" else "f32",
-                   # the figures a reader of the driver's record needs beside `value` (the driver keeps this dict whole):
-                   # the reference's own evaluation semantics are one sample at a time (val.py:133-136)
-                   "one_sample_in_flight_samples_per_s": single["value"] if single else None,
-                   "one_sample_in_flight_ms_per_sample": single["ms_per_step"] if single else None,
-                   "kernel_ms_per_sample_one_plan": single.get("gpu_ms_per_replay_alone") if single else None,
-                   "lanes_match_single_plan_bitwise": lanes_match,
-                   "pyramid_layout": "pregrouped [B*T*G,N,H,W,C]" if args.pregrouped else "reference [B,T*N,G*C,H,W] (regroup timed)"},
         "roofline": {"bound": "hbm", "kernel": "mixing_c64_f16x3_kernel<4> (rac_mixing_sampled_fwd: keypoints + projection + view select + gather "
                                "of the item's 96 points AND both adaptive mixings + LayerNorms, one launch per layer)" if fused_sm else
                                "sampling4d_c64_kernel (rac_sampling4d_fwd: keypoints + projection + view select + gather)",
@@ -674,7 +689,13 @@ def main():
                                       "traffic": bev_traffic},
                      "sasa_avg_launch_ms": sasa_ms},
         "mfma": mfma,
-    }
+    })
+    # the figures a reader of the recorded line needs beside `value`, kept in `config` because a record keeps that dict whole:
+    # the reference's own evaluation semantics are one sample at a time (val.py:133-136)
+    result["config"].update({"one_sample_in_flight_samples_per_s": single["value"] if single else None,
+                             "one_sample_in_flight_ms_per_sample": single["ms_per_step"] if single else None,
+                             "kernel_ms_per_sample_one_plan": single.get("gpu_ms_per_replay_alone") if single else None,
+                             "lanes_match_single_plan_bitwise": lanes_match})
     if world > 1:
         # the CPU oracle and the operator stress set are timed on rank 0 of a ONE-rank run only (they would sit inside the other
         # ranks' barrier otherwise); the line says so instead of omitting the keys
@@ -817,11 +838,7 @@ def main():
         # a lane that does not reproduce the single-plan result is a wrong result, not a throughput: no headline number
         result["invalid"] = f"lanes_match_single_plan_bitwise = {lanes_match}: value withheld (was {result['value']:.2f})"
         result["value"] = None
-    if rank == 0:
-        print(json.dumps(result))
-    if use_pg:
-        dist.barrier()
-        dist.destroy_process_group()
+    emit()
     if bad_lanes:
         sys.exit(3)
 

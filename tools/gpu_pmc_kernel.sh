@@ -4,6 +4,7 @@
 # PMC_ARGS: extra bench.py arguments (default "--no-graph --in-flight 1": eager launches, counters serialise the kernels anyway)
 # PMC_JSON: if set, the averages are also written there as JSON (what profiles/r04_pmc_bev.json is made from)
 tag=$1; ksub=$2; shift 2
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 i=0
@@ -11,7 +12,7 @@ failed=""
 for grp in "$@"; do
   i=$((i+1))
   rm -rf $out/p$i $out/p$i.json $out/p$i.log      # no stale counter CSVs of an earlier run under the same tag
-  timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out/p$i -o run -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-stress --steps 3 --warmup 2 ${PMC_ARGS:---no-graph --in-flight 1} > $out/p$i.json 2> $out/p$i.log || { echo "pass $i ($grp) failed"; tail -3 $out/p$i.log; failed="$failed|$grp"; rm -rf $out/p$i; }
+  timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out/p$i -o run -- python3 "$root/bench.py" --full --no-cpu-baseline --no-stress --steps 3 --warmup 2 ${PMC_ARGS:---no-graph --in-flight 1} > $out/p$i.json 2> $out/p$i.log || { echo "pass $i ($grp) failed"; tail -3 $out/p$i.log; failed="$failed|$grp"; rm -rf $out/p$i; }
 done
 FAILED_GROUPS="$failed" python3 - "$out" "$ksub" <<'PY'
 import csv, glob, sys, os

@@ -33,6 +33,7 @@
  *                        models/racformer_transformer.py:230-236,265-269,134
  *   rac_mixing_fwd    <- AdaptiveMixing.inner_forward's matmul / layer_norm / relu chain
  *                        models/racformer_transformer.py:589-603
+ *   rac_mixing_bwd    <- autograd of the same chain (the reference checkpoints it: models/racformer_transformer.py:612-616)
  *   rac_sasa_fwd      <- ScaleAdaptiveSelfAttention.inner_forward's mask + attention product
  *                        models/racformer_transformer.py:296-335
  *   rac_sasa_fwd_ex / rac_sasa_bwd <- the same forward saving each row's log-sum-exp, and its backward (autograd of the
@@ -59,7 +60,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 11
+#define RAC_ABI_VERSION 12
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -306,6 +307,24 @@ enum {
 int rac_mixing_fwd(const float *x, const float *params, float param_scale, float *out, void *out_split,
                    float split_scale, int ld_params, int num_query, int groups, int in_points, int channels, int out_points,
                    float eps, int mfma_mode, void *stream);
+
+/* Backward of rac_mixing_fwd in RAC_MIX_F32 mode with param_scale 1 (the training forward): given dZ, the gradients in x and
+ * in the generated parameters.  x, params, ld_params, num_query, groups, in_points, channels, out_points, eps: as given to
+ * rac_mixing_fwd (channels 64, out_points 128, in_points 1..96; ld_params a multiple of 4).
+ *   grad_out    : device f32 [num_query, groups, 128, 64] (contiguous), dZ
+ *   grad_x      : device f32 [num_query, groups, in_points, 64] receiving dx
+ *   grad_params : device f32, row q at grad_params + q*ld_grad_params, laid out as params: per group [dM 64*64 | dS 128*in_points];
+ *                 every one of a row's groups*(64*64+128*in_points) columns is written (ld_grad_params >= that width)
+ *   z_out       : optional device f32 [num_query, groups, 128, 64] receiving the recomputed Z (NULL: not written); bit for bit
+ *                 rac_mixing_fwd's RAC_MIX_F32 output
+ * One workgroup per item recomputes the forward with its own arithmetic (so the ReLU masks are the forward's) and forms
+ *   g2 = dZ [B^ > 0],  dB = r2 (g2 - mean g2 - B^ mean(g2 B^)),  dS = dB Y^T,  dY = S^T dB,
+ *   g1 = dY [A^ > 0],  dA = r1 (g1 - mean g1 - A^ mean(g1 A^)),  dM = x^T dA, dx = dA M^T
+ * (A = x M, A^ = LN(A), B = S Y, B^ = LN(B); means over the P*64 / 128*64 elements).  Every output element has one writer (no
+ * accumulation, no atomics: bit-reproducible).  No host synchronisation, no allocation. */
+int rac_mixing_bwd(const float *x, const float *params, int ld_params, const float *grad_out, float *grad_x, float *grad_params,
+                   int ld_grad_params, float *z_out, int num_query, int groups, int in_points, int channels, int out_points,
+                   float eps, void *stream);
 
 /* rac_sampling4d_fwd and rac_mixing_fwd (RAC_MIX_F16X3) as ONE kernel: the mixing workgroup of a (query, group) item gathers the
  * item's T * NP * D sampling points itself -- keypoints, projection, first-valid-view selection, level softmax and bilinear taps

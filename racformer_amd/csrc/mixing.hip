@@ -94,9 +94,21 @@ __device__ __forceinline__ void mix_write_out(const MixArgs &a, const float *sO,
     }
 }
 
-__global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
+// What the f32 forward leaves in registers after its second LayerNorm statistics: wave w's columns 16w..16w+15 of
+// A = x @ M (6 row tiles) and of B = S @ Y (8 row tiles), each in the 16x16 accumulator layout (row 16m + 4lk + r, column
+// 16w + li in register r of tile m), and the two (mean, 1/std) pairs.  Y is then in LDS (region A, row stride MIX_MS) and
+// S half 1 in sS.
+struct MixF32State {
+    mix_f4 acc1[6], acc2[8];
+    float mean1, rstd1, mean2, rstd2;
+};
+
+// The f32 forward of item (q, g) up to its second LayerNorm statistics -- shared by mixing_c64_kernel and the backward's
+// recompute (mixing_c64_bwd_kernel), so both run the same MFMA k-order and the same block sums.
+__device__ __forceinline__ void mix_f32_core(const MixArgs &a, float *smem, int q, int g, MixF32State &st)
 {
-    extern __shared__ float smem[];
+    mix_f4 (&acc1)[6] = st.acc1;
+    mix_f4 (&acc2)[8] = st.acc2;
     float *sX = smem;                          // [P_pad][68]
     float *sM = smem + MIX_PMAX * MIX_XS;      // [64][80]
     float *sY = smem;                          // [P_pad][80]   (aliases sX|sM after step 1)
@@ -109,8 +121,6 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
     const int MT = (P + 15) >> 4;   // 16-row tiles of x / Y
     const int PP = MIX_PMAX;        // rows / K are always padded to 96 with zeros: branch-free MFMA loops
     (void)MT;
-    const int item = blockIdx.x;
-    const int q = item / a.G, g = item % a.G;
     const float *gx = a.x + ((size_t)q * a.G + g) * P * MIX_C;
     const float *gM = a.params + (size_t)q * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
     const float *gS = gM + MIX_C * MIX_C;
@@ -184,7 +194,6 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
     __syncthreads();
 
     // ---- step 1: Y = x @ M, wave w -> columns 16w.. ---------------------------------------------
-    mix_f4 acc1[6];
 #pragma unroll
     for (int m = 0; m < 6; ++m)
         acc1[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
@@ -208,6 +217,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
             part += (16 * m + lk * 4 + r < P) ? acc1[m][r] : 0.f;
     const float n1 = (float)(P * MIX_C);
     const float mean1 = mix_block_sum(part, red, wave, lane) / n1;
+    st.mean1 = mean1;
     part = 0.f;
 #pragma unroll
     for (int m = 0; m < 6; ++m)
@@ -217,6 +227,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
             part += (16 * m + lk * 4 + r < P) ? d * d : 0.f;
         }
     const float rstd1 = 1.f / sqrtf(mix_block_sum(part, red, wave, lane) / n1 + a.eps);
+    st.rstd1 = rstd1;
     // (the two block sums above end with barriers: every wave is past its last sX / sM read)
 #pragma unroll
     for (int m = 0; m < 6; ++m)
@@ -229,7 +240,6 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
     __syncthreads();
 
     // ---- step 2: Z = S @ Y in two 64-row halves --------------------------------------------------
-    mix_f4 acc2[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m)
         acc2[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
@@ -266,6 +276,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
             part += acc2[m][r];
     const float n2 = (float)(MIX_OUT * MIX_C);
     const float mean2 = mix_block_sum(part, red, wave, lane) / n2;
+    st.mean2 = mean2;
     part = 0.f;
 #pragma unroll
     for (int m = 0; m < 8; ++m)
@@ -274,16 +285,277 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
             const float d = acc2[m][r] - mean2;
             part += d * d;
         }
-    const float rstd2 = 1.f / sqrtf(mix_block_sum(part, red, wave, lane) / n2 + a.eps);
+    st.rstd2 = 1.f / sqrtf(mix_block_sum(part, red, wave, lane) / n2 + a.eps);
+}
+
+__global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
+{
+    extern __shared__ float smem[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int item = blockIdx.x;
+    const int q = item / a.G, g = item % a.G;
+    MixF32State st;
+    mix_f32_core(a, smem, q, g, st);
     // stage the normalised [128][64] tile through LDS (region A is free: Y is dead) for 16-byte stores
     float *sO = smem;  // [128][64], 8192 floats <= MIX_REGION_A
 #pragma unroll
     for (int m = 0; m < 8; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            sO[(16 * m + lk * 4 + r) * MIX_C + 16 * wave + li] = fmaxf((acc2[m][r] - mean2) * rstd2, 0.f);
+            sO[(16 * m + lk * 4 + r) * MIX_C + 16 * wave + li] = fmaxf((st.acc2[m][r] - st.mean2) * st.rstd2, 0.f);
     __syncthreads();
     mix_write_out(a, sO, q, g, tid);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Backward of the f32 core (rac_mixing_bwd).  One workgroup per (query, group) item recomputes A, Y and B with
+// mix_f32_core -- the forward's own arithmetic, so the ReLU masks are the forward's bits -- and then, with B^ = (B-mu2) r2
+// and A^ = (A-mu1) r1 (rows >= P excluded from every mean):
+//     g2 = dZ [B^ > 0],  dB = r2 (g2 - mean g2 - B^ mean(g2 B^))     dS = dB Y^T [128,P],  dY = S^T dB [P,64]
+//     g1 = dY [A^ > 0],  dA = r1 (g1 - mean g1 - A^ mean(g1 A^))     dM = x^T dA [64,64],  dx = dA M^T [P,64]
+// LDS plan: the forward's 72 KB (two workgroups per CU), nothing more.  dB stays in the accumulators and goes through LDS a
+// 32-row quarter at a time (the 8.5 KB between Y and sS); the quarters run in the order 2, 3, 0, 1 so that the S half the
+// recompute left in sS serves the first two, and half 0 is re-read (from L2) for the last two.  For the last two products
+// x and M are re-read into region A and dA is written over sS.  dM takes dA straight from the accumulators as its B operand
+// (k = 16m + 4lk + r: the accumulator rows of the lane).  Every output element has one writer; no atomics.
+#define MIXB_DBS 68                           /* dB quarter row stride */
+#define MIXB_DB_OFF (MIX_PMAX * MIX_MS)       /* dB quarter [32][68]: after Y in region A */
+#define MIXB_MS 68                            /* re-read M row stride */
+#define MIXB_DAS 66                           /* dA row stride (over sS) */
+
+struct MixBwdArgs {
+    MixArgs f;                 // x, params, ld_params, nq, G, P, eps as for the forward (param_scale 1, out unused)
+    const float *grad_out;     // [nq, G, 128, 64]
+    float *grad_x;             // [nq, G, P, 64]
+    float *grad_params;        // row q at grad_params + q*ld_grad_params: per group [dM 64*64 | dS 128*P]
+    float *z_out;              // optional [nq, G, 128, 64]: the recomputed Z
+    int ld_grad_params;
+};
+
+__global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs b)
+{
+    extern __shared__ float smem[];
+    const MixArgs &a = b.f;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int P = a.P;
+    const int item = blockIdx.x;
+    const int q = item / a.G, g = item % a.G;
+    float *sY = smem;                                   // [96][80] after the recompute
+    float *sDB = smem + MIXB_DB_OFF;                    // [32][68]
+    float *sS = smem + MIX_REGION_A;                    // [64][100]
+    float *red = sS + 64 * MIX_SS;
+    const size_t item_off = (size_t)q * a.G + g;
+    const float *gM = a.params + (size_t)q * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
+    const float *gS = gM + MIX_C * MIX_C;
+    const float *gdz = b.grad_out + item_off * MIX_OUT * MIX_C;
+    float *gdM = b.grad_params + (size_t)q * b.ld_grad_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
+    float *gdS = gdM + MIX_C * MIX_C;
+
+    MixF32State st;
+    mix_f32_core(a, smem, q, g, st);
+
+    // ---- LN2 + ReLU backward: dB (wave w: columns 16w.., all 128 rows, in the layout of B) ---------------------------
+    mix_f4 dB[8];
+    float s_g = 0.f, s_gb = 0.f;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * m + lk * 4 + r, col = 16 * wave + li;
+            const float bh = (st.acc2[m][r] - st.mean2) * st.rstd2;
+            if (b.z_out)
+                b.z_out[item_off * MIX_OUT * MIX_C + row * MIX_C + col] = fmaxf(bh, 0.f);
+            const float g2 = bh > 0.f ? gdz[row * MIX_C + col] : 0.f;
+            s_g += g2;
+            s_gb += g2 * bh;
+            dB[m][r] = g2;
+        }
+    const float n2 = (float)(MIX_OUT * MIX_C);
+    const float mg2 = mix_block_sum(s_g, red, wave, lane) / n2;
+    const float mgb2 = mix_block_sum(s_gb, red, wave, lane) / n2;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float bh = (st.acc2[m][r] - st.mean2) * st.rstd2;
+            dB[m][r] = st.rstd2 * (dB[m][r] - mg2 - bh * mgb2);
+        }
+
+    // ---- dS = dB Y^T and dY = S^T dB, a 32-row quarter of dB at a time ------------------------------------------------
+    // dS: wave w -> rows 16(w&1).. of the quarter, out-point columns 48(w>>1).. (3 tiles);  dY: wave w -> columns 16w..
+    mix_f4 dY[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+        dY[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+    const int ncol4 = MIX_PMAX >> 2;
+    const bool s_vec = (P & 3) == 0;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        const int j = (jj + 2) & 3;              // quarters 2, 3 (S half 1, left in sS by the recompute), then 0, 1
+        __syncthreads();                         // every wave is past its reads of the previous quarter (and of sS half 1)
+        if (jj == 2) {                           // S half 0 into sS (zero-padded columns, as the forward stages it)
+            for (int i = tid; i < 64 * ncol4; i += 256) {
+                const int r = i / ncol4, c4 = i - r * ncol4;
+                const float *src = gS + (size_t)r * P + c4 * 4;
+                rac_f4 v = {0.f, 0.f, 0.f, 0.f};
+                if (c4 * 4 + 3 < P) {
+                    if (s_vec) {
+                        v = rac_ld4(src);
+                    } else {
+                        v.x = src[0]; v.y = src[1]; v.z = src[2]; v.w = src[3];
+                    }
+                } else {
+                    if (c4 * 4 + 0 < P) v.x = src[0];
+                    if (c4 * 4 + 1 < P) v.y = src[1];
+                    if (c4 * 4 + 2 < P) v.z = src[2];
+                }
+                *reinterpret_cast<rac_f4 *>(sS + r * MIX_SS + c4 * 4) = v;
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                sDB[(16 * h + lk * 4 + r) * MIXB_DBS + 16 * wave + li] = dB[2 * j + h][r];
+        __syncthreads();
+        // dS tiles of the quarter
+        {
+            const int mo = wave & 1, n0 = 3 * (wave >> 1);
+            mix_f4 acc[3];
+#pragma unroll
+            for (int n = 0; n < 3; ++n)
+                acc[n] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int s = 0; s < MIX_C / 4; ++s) {
+                const float av = sDB[(16 * mo + li) * MIXB_DBS + 4 * s + lk];
+#pragma unroll
+                for (int n = 0; n < 3; ++n)
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, sY[(16 * (n0 + n) + li) * MIX_MS + 4 * s + lk], acc[n], 0, 0, 0);
+            }
+#pragma unroll
+            for (int n = 0; n < 3; ++n) {
+                const int p = 16 * (n0 + n) + li;
+                if (p < P)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        gdS[(size_t)(32 * j + 16 * mo + lk * 4 + r) * P + p] = acc[n][r];
+            }
+        }
+        // dY += S[32j.., :]^T dB[32j.., :]
+        const float *sSq = sS + 32 * (j & 1) * MIX_SS;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const float bv = sDB[(4 * s + lk) * MIXB_DBS + 16 * wave + li];
+#pragma unroll
+            for (int m = 0; m < 6; ++m)
+                dY[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(sSq[(4 * s + lk) * MIX_SS + 16 * m + li], bv, dY[m], 0, 0, 0);
+        }
+    }
+
+    // ---- LN1 + ReLU backward: dA (wave w: columns 16w.., rows >= P zero) -----------------------------------------------
+    // x and M are requested now and land while the statistics are formed
+    const float *gx = a.x + item_off * P * MIX_C;
+    rac_f4 vx[6], vm[4];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int i = tid + 256 * k, r = i >> 4, c4 = i & 15;
+        vx[k] = (rac_f4){0.f, 0.f, 0.f, 0.f};
+        if (r < P)
+            vx[k] = rac_ld4(gx + r * MIX_C + c4 * 4);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + 256 * k, r = i >> 4, c4 = i & 15;
+        vm[k] = rac_ld4(gM + r * MIX_C + c4 * 4);
+    }
+    float s_g1 = 0.f, s_ga = 0.f;
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * m + lk * 4 + r;
+            const float ah = (st.acc1[m][r] - st.mean1) * st.rstd1;
+            const float g1 = (row < P && ah > 0.f) ? dY[m][r] : 0.f;
+            s_g1 += g1;
+            s_ga += g1 * ah;
+            dY[m][r] = g1;
+        }
+    const float n1 = (float)(P * MIX_C);
+    const float mg1 = mix_block_sum(s_g1, red, wave, lane) / n1;
+    const float mga1 = mix_block_sum(s_ga, red, wave, lane) / n1;
+    // (the block sums end with barriers: every wave is past its reads of Y, dB and S)
+    float *sX = smem;                          // [96][68]
+    float *sMb = smem + MIX_PMAX * MIX_XS;     // [64][68]
+    float *sDA = sS;                           // [96][66]
+    mix_f4 dA[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * m + lk * 4 + r;
+            const float ah = (st.acc1[m][r] - st.mean1) * st.rstd1;
+            const float d = row < P ? st.rstd1 * (dY[m][r] - mg1 - ah * mga1) : 0.f;
+            dA[m][r] = d;
+            sDA[row * MIXB_DAS + 16 * wave + li] = d;
+        }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int i = tid + 256 * k, r = i >> 4, c4 = i & 15;
+        *reinterpret_cast<rac_f4 *>(sX + r * MIX_XS + c4 * 4) = vx[k];   // rows >= P are zeros
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + 256 * k, r = i >> 4, c4 = i & 15;
+        *reinterpret_cast<rac_f4 *>(sMb + r * MIXB_MS + c4 * 4) = vm[k];
+    }
+    __syncthreads();
+
+    // ---- dM = x^T dA: wave w -> columns 16w.. (its own dA columns, straight from the accumulators) ---------------------
+    {
+        mix_f4 acc[4];
+#pragma unroll
+        for (int mc = 0; mc < 4; ++mc)
+            acc[mc] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int m = 0; m < 6; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float *xr = sX + (16 * m + 4 * lk + r) * MIX_XS + li;
+#pragma unroll
+                for (int mc = 0; mc < 4; ++mc)
+                    acc[mc] = __builtin_amdgcn_mfma_f32_16x16x4f32(xr[16 * mc], dA[m][r], acc[mc], 0, 0, 0);
+            }
+#pragma unroll
+        for (int mc = 0; mc < 4; ++mc)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                gdM[(16 * mc + lk * 4 + r) * MIX_C + 16 * wave + li] = acc[mc][r];
+    }
+    // ---- dx = dA M^T: wave w -> columns 16w.. ---------------------------------------------------------------------------
+    {
+        mix_f4 acc[6];
+#pragma unroll
+        for (int m = 0; m < 6; ++m)
+            acc[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int s = 0; s < MIX_C / 4; ++s) {
+            const float bv = sMb[(16 * wave + li) * MIXB_MS + 4 * s + lk];
+#pragma unroll
+            for (int m = 0; m < 6; ++m)
+                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(sDA[(16 * m + li) * MIXB_DAS + 4 * s + lk], bv, acc[m], 0, 0, 0);
+        }
+        float *gdx = b.grad_x + item_off * P * MIX_C;
+#pragma unroll
+        for (int m = 0; m < 6; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * m + lk * 4 + r;
+                if (row < P)
+                    gdx[row * MIX_C + 16 * wave + li] = acc[m][r];
+            }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -683,6 +955,36 @@ extern "C" int rac_mixing_fwd(const float *x, const float *params, float param_s
     }
     hipLaunchKernelGGL(mixing_c64_kernel, dim3(num_query * groups), dim3(256), lds, (hipStream_t)stream, a);
     return rac_launch_status("rac_mixing_fwd");
+}
+
+extern "C" int rac_mixing_bwd(const float *x, const float *params, int ld_params, const float *grad_out, float *grad_x,
+                              float *grad_params, int ld_grad_params, float *z_out, int num_query, int groups, int in_points,
+                              int channels, int out_points, float eps, void *stream)
+{
+    RAC_CHECK_ARG(channels == MIX_C && out_points == MIX_OUT,
+                  "rac_mixing_bwd: built for 64 channels per group and 128 out points (got %d, %d)", channels, out_points);
+    RAC_CHECK_ARG(in_points >= 1 && in_points <= MIX_PMAX, "rac_mixing_bwd: in_points=%d out of [1,%d]", in_points, MIX_PMAX);
+    RAC_CHECK_ARG(num_query >= 0 && groups >= 1, "rac_mixing_bwd: bad sizes");
+    const long width = (long)groups * (MIX_C * MIX_C + MIX_OUT * in_points);
+    RAC_CHECK_ARG(ld_params >= width && ld_params % 4 == 0, "rac_mixing_bwd: parameter row stride %d", ld_params);
+    RAC_CHECK_ARG(ld_grad_params >= width, "rac_mixing_bwd: gradient row stride %d", ld_grad_params);
+    RAC_CHECK_ARG((long)num_query * groups <= 0x7fffffffL, "rac_mixing_bwd: %d x %d items", num_query, groups);
+    static_assert(MIXB_DB_OFF + 32 * MIXB_DBS <= MIX_REGION_A, "dB quarter must fit between Y and sS");
+    static_assert(MIX_PMAX * MIX_XS + MIX_C * MIXB_MS <= MIX_REGION_A, "x and M must fit region A");
+    static_assert(MIX_PMAX * MIXB_DAS <= 64 * MIX_SS, "dA must fit over sS");
+    if (num_query == 0)
+        return 0;
+    RAC_CHECK_ARG(x && params && grad_out && grad_x && grad_params, "rac_mixing_bwd: null pointer");
+    MixBwdArgs b;
+    memset(&b, 0, sizeof(b));
+    b.f.x = x; b.f.params = params; b.f.param_scale = 1.f;
+    b.f.nq = num_query; b.f.G = groups; b.f.P = in_points; b.f.ld_params = ld_params; b.f.eps = eps;
+    b.grad_out = grad_out; b.grad_x = grad_x; b.grad_params = grad_params; b.z_out = z_out; b.ld_grad_params = ld_grad_params;
+    const size_t lds = (size_t)MIX_LDS_FLOATS * sizeof(float);
+    if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_MIXING_BWD, reinterpret_cast<const void *>(mixing_c64_bwd_kernel), (int)lds))
+        return rc_attr;
+    hipLaunchKernelGGL(mixing_c64_bwd_kernel, dim3(num_query * groups), dim3(256), lds, (hipStream_t)stream, b);
+    return rac_launch_status("rac_mixing_bwd");
 }
 
 // AdaptiveMixing core with the adaptive 4D sampling inside (models/racformer_transformer.py:361-408 + sparsebev_sampling.py:45-131 +

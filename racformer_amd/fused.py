@@ -308,6 +308,44 @@ def mixing_fused(x, params, in_points, n_groups, out_points=128, eps=1e-5, split
     return out
 
 
+def mixing_backward(x, params, grad_out, in_points, n_groups, out_points=128, eps=1e-5, grad_x=None, grad_params=None, z_out=None):
+    """Backward of mixing_fused(..., f16x3=False, param_scale=1) (rac_mixing_bwd): x [B,Q,G,P,64] (contiguous) and params
+    [B,Q,G*(64*64+128*P)] (unit inner stride) as given to it, grad_out [B,Q,G*128*64] -> (grad_x [B,Q,G,P,64],
+    grad_params [B,Q,G*(64*64+128*P)]).  ``grad_x`` / ``grad_params``: destinations (grad_params may have a row stride of its
+    own); allocated when not given.  Every element of both is written.  ``z_out``: optional contiguous f32 [B,Q,G*128*64]
+    receiving the recomputed forward output."""
+    _lib.require_gpu(x, grad_out, what="mixing_backward")
+    B, Q, G, P, C = x.shape
+    if G != n_groups or P != in_points or x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("mixing_backward: x must be contiguous float32 [B,Q,G,P,64]")
+    width = G * (C * C + out_points * P)
+    p_par, ld_par = _rows(params, width, "mixing_backward(params)")
+    want = (B, Q, G * out_points * C)
+    if tuple(grad_out.shape) != want or grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
+        raise RuntimeError(f"mixing_backward: grad_out must be contiguous float32 {list(want)}")
+    if z_out is not None:
+        _lib.require_gpu(z_out, what="mixing_backward(z_out)")
+        if tuple(z_out.shape) != want or z_out.dtype != torch.float32 or not z_out.is_contiguous():
+            raise RuntimeError(f"mixing_backward: z_out must be contiguous float32 {list(want)}")
+    if grad_x is None:
+        grad_x = torch.empty_like(x)
+    elif tuple(grad_x.shape) != tuple(x.shape) or grad_x.dtype != torch.float32 or not grad_x.is_contiguous() or not grad_x.is_cuda:
+        raise RuntimeError("mixing_backward: grad_x must be a contiguous CUDA float32 tensor shaped like x")
+    if grad_params is None:
+        grad_params = torch.empty(B, Q, width, device=x.device, dtype=torch.float32)
+    p_gpar, ld_gpar = _rows(grad_params, width, "mixing_backward(grad_params)")
+    ev = _lib.timer.record("mixing_bwd") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_mixing_bwd(_lib.ptr(x), p_par, ld_par, _lib.ptr(grad_out), _lib.ptr(grad_x), p_gpar, ld_gpar,
+                                   _lib.ptr(z_out) if z_out is not None else None, B * Q, G, P, C, out_points, float(eps),
+                                   _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_mixing_bwd")
+    return grad_x, grad_params
+
+
 def mixing_sampled_fused(mlvl_feats, query_bbox, offsets, ray_logits, scale_logits, time_diff, lidar2img, num_frames, num_groups,
                          num_points, depth_num, pc_range, d_region, image_h, image_w, params, out_points=128, eps_proj=1e-5, eps=1e-5,
                          debug=False, box_table=None, view_in=None, param_scale=1.0):

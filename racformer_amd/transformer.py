@@ -28,7 +28,7 @@ from . import _lib
 from .bbox_utils import decode_bbox, inverse_sigmoid, theta_d2xy_coods, xy2theta_d_coods
 from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_sampling_fused, bev_sampling_multi_fused,
                     box_prep, conv_direct, quantize_values_i16, upsample2x_image,
-                    generator_fused, gru_gate_fused, layer_boundary_fused, mixing_fused, mixing_sampled_fused, mixing_sampled_supported, outproj_fused,
+                    generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, mixing_sampled_fused, mixing_sampled_supported, outproj_fused,
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
                     pe_head, refine_fused, row_gemm,
@@ -367,6 +367,25 @@ class _SASACore(torch.autograd.Function):
         sasa_backward(lin[..., :3 * E], lin[..., 3 * E:], query_bbox, ctx.num_heads, ctx.pc_range, o, lse, grad_o.contiguous(),
                       box_table=box_table, grad_qkv=grad_lin[..., :3 * E], grad_tau=grad_lin[..., 3 * E:])
         return grad_lin, None, None, None, None
+
+
+class _MixingCore(torch.autograd.Function):
+    """The AdaptiveMixing core: apply(x [B,Q,G,P,64] contiguous, params [B,Q,G*(64*64+128*P)], P, G) -> relu(LN(S @ relu(LN(x @ M))))
+    as [B,Q,G*128*64].  The forward is rac_mixing_fwd in f32 mode; the backward rac_mixing_bwd, which recomputes the forward on
+    chip, so only x and params are saved.  The launchers are looked up as this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, x, params, in_points, n_groups):
+        out = mixing_fused(x, params, in_points, n_groups, f16x3=False)
+        ctx.in_points, ctx.n_groups = in_points, n_groups
+        ctx.save_for_backward(x, params)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, params = ctx.saved_tensors
+        grad_x, grad_params = mixing_backward(x, params, grad_out.contiguous(), ctx.in_points, ctx.n_groups)
+        return grad_x, grad_params, None, None
 
 
 def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, image_w, aggregate=True,
@@ -972,7 +991,15 @@ class AdaptiveMixing(nn.Module):
         params = self.parameter_generator(query)
         if out_proj_split is not None and self.fused_supported(x):
             # fused plan: one MFMA kernel for both mixings + norms + ReLUs, split-K out_proj
-            out = mixing_fused(x.contiguous(), params, P, G, self.out_points)
+            if torch.is_grad_enabled() and (x.requires_grad or query.requires_grad or any(p.requires_grad for p in self.parameters())):
+                # training: through _MixingCore (rac_mixing_fwd in f32 mode + rac_mixing_bwd).  A cached out_proj_split
+                # without autograd history (the decoder layer's, built under no_grad) would cut out_proj's weight gradient:
+                # it is then rebuilt from the live weight.
+                if self.out_proj.weight.requires_grad and not out_proj_split.requires_grad:
+                    out_proj_split = self.split_out_proj()
+                out = _MixingCore.apply(x.contiguous(), params, P, G)
+            else:
+                out = mixing_fused(x.contiguous(), params, P, G, self.out_points)
             S_, N, k = out_proj_split.shape
             a3 = out.view(B * Q, S_, k).transpose(0, 1)
             proj = torch.bmm(a3, out_proj_split.transpose(1, 2)).sum(0) + self.out_proj.bias

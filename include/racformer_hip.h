@@ -50,6 +50,7 @@
  *                        models/racformer_transformer.py:631,655
  *   rac_bev_sampling_fwd <- BEVSampling keypoints + BEVSelfAttention's MSDA + frame fusion, fused
  *                        models/racformer_transformer.py:490-529, models/bev_self_attention.py:176-213
+ *   rac_bev_sampling_bwd <- autograd of the same chain (keypoints, MSDA, frame fusion) in one launch
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -60,7 +61,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 12
+#define RAC_ABI_VERSION 13
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -175,6 +176,34 @@ int rac_bev_sampling_fwd(const void *value, const float *query_bbox, const float
                          const float *time_diff, float *out, float *loc_out, int ld_off, int ld_ray,
                          int ld_scale, int ld_queue, int B, int T, int Q, int heads, int NP, int D, int H, int W,
                          int dim, const float *pc_range, const float *depth_base, float d_region, int dtype,
+                         void *stream);
+
+/* Backward of rac_bev_sampling_fwd in one launch: float32 value stream, B == 1, 64 channels per head.  Nothing of the forward
+ * is saved: keypoints, softmaxes and bilinear footprints are recomputed from the forward's inputs with the forward's own
+ * device functions.  Inputs as rac_bev_sampling_fwd (the same pointers and row strides), plus
+ *   grad_out     : device f32 [B,Q,heads*64]
+ * Outputs, all device f32:
+ *   grad_value   : [B*T, H*W, heads, 64], ZERO-FILLED BY THE CALLER; float atomics (sums in arrival order)
+ *   grad_offsets : rows of heads*NP*D*2 (stride gld_off);  grad_ray: rows of D (gld_ray);
+ *   grad_scale   : rows of heads*NP*D (gld_scale): gradient of the LOGITS (softmax backward over the points of a head);
+ *   grad_queue   : rows of T (gld_queue): gradient of the frame logits (softmax backward over T)
+ *                  -- the four may be column slices of one gradient of a fused Linear output
+ *   grad_box     : [B,Q,8] gradient of the box-table entries the forward reads (0, 1, 3, 4, 6, 7; 2 and 5 are written as 0)
+ *   grad_loc_out, grad_attn_out : optional debug outputs [B,Q,heads,T,NP*D,2] / [B,Q,heads,T,NP*D] (NULL, NULL to skip): per
+ *                  keypoint the gradient of its location (x, y in [0,1], its weight included) and of its combined weight
+ *                  softmax_P * softmax_T, before the chain tail -- the counterpart of the forward's loc_out
+ * Every element of every output except grad_value has one writer and a fixed summation order (bit-reproducible).  The clamp
+ * to [0,1] passes the gradient inside [0,1] inclusive; a keypoint outside the map contributes nothing; velocity and
+ * time_diff get no gradient.  A non-finite logit reaches grad_value at the pixels its keypoints tap, as in autograd; a
+ * non-finite box row samples nothing.  Refused before any launch: dtype other than RAC_F32, B > 1, T or NP*D above 64,
+ * heads*T*NP*D keypoints per query beyond the 64 KB LDS staging (about 2,600). */
+int rac_bev_sampling_bwd(const void *value, const float *query_bbox, const float *box_table, const float *offsets,
+                         const float *ray_logits, const float *scale_logits, const float *queue_logits,
+                         const float *time_diff, const float *grad_out, float *grad_value, float *grad_offsets,
+                         float *grad_ray, float *grad_scale, float *grad_queue, float *grad_box, float *grad_loc_out,
+                         float *grad_attn_out, int ld_off, int ld_ray, int ld_scale, int ld_queue, int gld_off,
+                         int gld_ray, int gld_scale, int gld_queue, int B, int T, int Q, int heads, int NP, int D, int H,
+                         int W, int dim, const float *pc_range, const float *depth_base, float d_region, int dtype,
                          void *stream);
 
 /* The same kernel for the BEV streams of one decoder layer (radar, LSS) in ONE launch: same queries, boxes and time_diff,

@@ -17,10 +17,7 @@
 // the frame weight.  Phase D: fixed-order LDS sum of the four point subsets (deterministic).
 // For B>1 the reference pairs value frame i=b*T+t with the locations of (t'=i/B, b'=i%B)
 // (bev_self_attention.py:185-188 vs :162,173, quirk Q2); reproduced as written.
-#include "rac_common.h"
-
-#define BEV_MAX_DEPTH 16
-#define BEV_TWO_PI 6.283185307179586f
+#include "bev_device.h"
 
 #define BEV_MAX_STREAMS 2
 // one BEV stream (radar / LSS): its value maps and the Linear outputs of its sampling module; blockIdx.y selects it, so
@@ -52,18 +49,6 @@ struct BevArgs {
     int list_holes;          // 1: some list slots have no keypoint (filled with zero-weight outside taps)
     int xcd_remap;           // 1: blocks that share an XCD (blockIdx & 7) take a contiguous range of items (speed only)
 };
-
-// polar jitter of a keypoint (racformer_transformer.py:512-522 through models/bbox/utils.py:84-106): (ex, ey) metres from the
-// map centre -> (dist, theta), dist += doff, back to the normalised map.  (Scaling the unit vector (ex, ey) / r directly
-// would skip atan2f / fmodf / cosf / sinf; measured: under 1 us of 81 per launch -- not worth leaving the reference's chain.)
-__device__ __forceinline__ void bev_polar_jitter(float ex, float ey, float doff, float *loc2)
-{
-    const float dist = sqrtf(ex * ex + ey * ey) / 65.0f + doff;
-    const float th = fmodf(atan2f(ey, ex) + BEV_TWO_PI, BEV_TWO_PI) / BEV_TWO_PI;
-    const float ang = th * BEV_TWO_PI, rad = dist * 65.0f;
-    loc2[0] = fminf(fmaxf((51.2f + rad * cosf(ang)) / 102.4f, 0.f), 1.f);
-    loc2[1] = fminf(fmaxf((51.2f + rad * sinf(ang)) / 102.4f, 0.f), 1.f);
-}
 
 __device__ __forceinline__ void bev_keypoint(const BevArgs &a, const BevStream &s, int bq, int tq, int q, int h, int p, float *loc2)
 {
@@ -132,33 +117,6 @@ __device__ __forceinline__ rac_f4 bev_tap<unsigned short>(__amdgpu_buffer_rsrc_t
     const bev_u2 r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);    // 4 x bf16
     return (rac_f4){__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
                     __uint_as_float(r.y & 0xffff0000u)};
-}
-
-// per-(t,p) half of the keypoint chain for B==1: warp the T-invariant base point, polar jitter.
-__device__ __forceinline__ void bev_warp(const BevArgs &a, float px, float py, float vx, float vy, float td,
-                                         float doff, float *loc2)
-{
-    const float sx = a.pc[3] - a.pc[0], sy = a.pc[4] - a.pc[1];
-    px -= vx * td;
-    py -= vy * td;
-    const float nx = (px - a.pc[0]) / sx, ny = (py - a.pc[1]) / sy;
-    const float ex = nx * 102.4f - 51.2f, ey = ny * 102.4f - 51.2f;
-    bev_polar_jitter(ex, ey, doff, loc2);
-}
-
-__device__ __forceinline__ float bev_wave_max(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ float bev_wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // GL = lanes of a group (one group gathers one tap row per load): 16 lanes x 4 channels for the 4-byte and bf16 streams; 8 lanes x 8
@@ -250,27 +208,20 @@ __global__ __launch_bounds__(256, BEV_OCC) void bev_sampling_d64_kernel(const Be
         for (int t = tid - 192; t < T; t += 32)
             std_[t] = a.time_diff[b * T + t];
     if (r_base) {
-        const float dx = g_bt[3] * g_o0, dy = g_bt[4] * g_o1;
-        sbase[tid * 2] = g_bt[0] + (dx * g_bt[6] - dy * g_bt[7]);
-        sbase[tid * 2 + 1] = g_bt[1] + (dx * g_bt[7] + dy * g_bt[6]);
+        bev_base_point(g_bt, g_o0, g_o1, sbase + tid * 2);
     }
     if (r_doff) {
         const int kk = (tid - 128) / D, dd = (tid - 128) - kk * D;
-        const float sg = 1.f / (1.f + expf(-g_ray));
-        sdoff[kk * BEV_MAX_DEPTH + dd] = a.depth_base[dd] + (sg * 2.f - 1.f) * a.d_region / (float)D / 2.f;
+        sdoff[kk * BEV_MAX_DEPTH + dd] = bev_depth_offset(bev_sigmoid(g_ray), a.depth_base[dd], a.d_region, D);
     }
     if (r_soft) {                                      // wave-uniform
-        const float mq = bev_wave_max(g_q);
-        const float eq = ln < T ? expf(g_q - mq) : 0.f;
-        const float sumq = bev_wave_sum(eq);
+        const float wq = bev_wave_softmax(g_q, ln < T);
         if (ln < T)
-            sq[wk * T + ln] = eq / sumq;
+            sq[wk * T + ln] = wq;
         if (a.B == 1) {
-            const float ml = bev_wave_max(g_lg);
-            const float el = ln < P ? expf(g_lg - ml) : 0.f;
-            const float suml = bev_wave_sum(el);
+            const float wl = bev_wave_softmax(g_lg, ln < P);
             if (ln < P)
-                sattn[wk * P + ln] = el / suml;
+                sattn[wk * P + ln] = wl;
         }
     }
     __syncthreads();
@@ -283,7 +234,7 @@ __global__ __launch_bounds__(256, BEV_OCC) void bev_sampling_d64_kernel(const Be
         const int it = i0 + kk, q = it / a.heads, h = it % a.heads;
         float loc[2];
         if (a.B == 1) {
-            bev_warp(a, sbase[(kk * P + p) * 2], sbase[(kk * P + p) * 2 + 1], svel[kk * 2], svel[kk * 2 + 1], std_[t],
+            bev_warp(a.pc, sbase[(kk * P + p) * 2], sbase[(kk * P + p) * 2 + 1], svel[kk * 2], svel[kk * 2 + 1], std_[t],
                      sdoff[kk * BEV_MAX_DEPTH + p % D], loc);
         } else {
             const int fi = b * T + t;                // value frame index

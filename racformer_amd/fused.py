@@ -133,6 +133,62 @@ def bev_sampling_fused(value, hw, query_bbox, offsets, ray_logits, scale_logits,
     return (out, loc_out) if debug else out
 
 
+def bev_sampling_backward(value, hw, query_bbox, offsets, ray_logits, scale_logits, queue_logits, time_diff, grad_out,
+                          num_frames, num_heads, num_points, depth_num, pc_range, d_region, box_table=None, grad_offsets=None,
+                          grad_ray=None, grad_scale=None, grad_queue=None, debug=False):
+    """Backward of bev_sampling_fused (rac_bev_sampling_bwd): the forward's arguments and grad_out [B,Q,heads*64] ->
+    (grad_value [B*T,H*W,heads,64], grad_offsets, grad_ray, grad_scale, grad_queue, grad_box [B,Q,8]); with ``debug`` also
+    the kernel's per-keypoint gradients (grad_loc [B,Q,heads,T,P,2], grad_attn [B,Q,heads,T,P]).  ``grad_offsets`` ..
+    ``grad_queue``: destinations with unit inner stride and a row stride of their own (column slices of one gradient of a
+    fused Linear output); allocated when not given.  Every element of them is written.  float32 values and B == 1 only."""
+    _lib.require_gpu(value, query_bbox, time_diff, grad_out, what="bev_sampling_backward")
+    B, Q, _ = query_bbox.shape
+    T, Hn, NP, D = num_frames, num_heads, num_points, depth_num
+    P = NP * D
+    H, W = hw
+    if tuple(value.shape) != (B * T, H * W, Hn, 64):
+        raise RuntimeError(f"bev_sampling_backward: value must be [{B * T},{H * W},{Hn},64], got {tuple(value.shape)}")
+    if tuple(grad_out.shape) != (B, Q, Hn * 64) or grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
+        raise RuntimeError(f"bev_sampling_backward: grad_out must be a contiguous float32 [{B},{Q},{Hn * 64}]")
+    p_off, ld_off = _rows(offsets, Hn * P * 2, "bev_sampling_backward(offsets)")
+    p_ray, ld_ray = _rows(ray_logits, D, "bev_sampling_backward(ray_logits)")
+    p_sc, ld_sc = _rows(scale_logits, Hn * P, "bev_sampling_backward(scale_logits)")
+    p_qu, ld_qu = _rows(queue_logits, T, "bev_sampling_backward(queue_logits)")
+    if box_table is None:
+        box_table = box_prep(query_bbox, pc_range)
+    dev = query_bbox.device
+
+    def dest(t_, width):
+        return torch.empty(B, Q, width, device=dev, dtype=torch.float32) if t_ is None else t_
+
+    grad_offsets, grad_ray = dest(grad_offsets, Hn * P * 2), dest(grad_ray, D)
+    grad_scale, grad_queue = dest(grad_scale, Hn * P), dest(grad_queue, T)
+    p_goff, gld_off = _rows(grad_offsets, Hn * P * 2, "bev_sampling_backward(grad_offsets)")
+    p_gray, gld_ray = _rows(grad_ray, D, "bev_sampling_backward(grad_ray)")
+    p_gsc, gld_sc = _rows(grad_scale, Hn * P, "bev_sampling_backward(grad_scale)")
+    p_gqu, gld_qu = _rows(grad_queue, T, "bev_sampling_backward(grad_queue)")
+    grad_value = torch.zeros(value.shape, device=dev, dtype=torch.float32)
+    grad_box = torch.empty(B, Q, 8, device=dev, dtype=torch.float32)
+    grad_loc = torch.empty(B, Q, Hn, T, P, 2, device=dev, dtype=torch.float32) if debug else None
+    grad_attn = torch.empty(B, Q, Hn, T, P, device=dev, dtype=torch.float32) if debug else None
+    pc = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
+    code = _lib.dtype_code(value) if value.dtype in (torch.float32, torch.bfloat16) else _lib.RAC_I16
+    ev = _lib.timer.record("bev_sampling_bwd") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_bev_sampling_bwd(
+        _lib.ptr(value), _lib.ptr(query_bbox), _lib.ptr(box_table), p_off, p_ray, p_sc, p_qu, _lib.ptr(time_diff),
+        _lib.ptr(grad_out), _lib.ptr(grad_value), p_goff, p_gray, p_gsc, p_gqu, _lib.ptr(grad_box),
+        _lib.ptr(grad_loc) if debug else None, _lib.ptr(grad_attn) if debug else None, ld_off, ld_ray, ld_sc, ld_qu,
+        gld_off, gld_ray, gld_sc, gld_qu, B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region),
+        code, _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_bev_sampling_bwd")
+    res = (grad_value, grad_offsets, grad_ray, grad_scale, grad_queue, grad_box)
+    return res + (grad_loc, grad_attn) if debug else res
+
+
 def quantize_values_i16(value):
     """A hoisted value stream [B*T, H*W, heads, 64] f32 -> (int16 mantissas of the same shape, scales [B*T, H*W, heads] f32):
     one power-of-two scale per (pixel, head) block of 64 channels, value = q * scale (rac_quant_i16_fwd; opt-in storage of

@@ -26,7 +26,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .bbox_utils import decode_bbox, inverse_sigmoid, theta_d2xy_coods, xy2theta_d_coods
-from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_sampling_fused, bev_sampling_multi_fused,
+from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_sampling_backward, bev_sampling_fused,
+                    bev_sampling_multi_fused,
                     box_prep, conv_direct, quantize_values_i16, upsample2x_image,
                     generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, mixing_sampled_fused, mixing_sampled_supported, outproj_fused,
                     pack_conv3x3_weight,
@@ -369,6 +370,45 @@ class _SASACore(torch.autograd.Function):
         return grad_lin, None, None, None, None
 
 
+class _BEVSamplingCore(torch.autograd.Function):
+    """The BEVSampling core: apply(value [B*T,H*W,heads,64], lin_off, lin_ray, lin_sc, lin_qu (the four Linear outputs),
+    query_ray [B,Q,10], box_graph, box_table, time_diff, hw, T, heads, NP, D, pc_range, d_region) -> [B,Q,heads*64] before
+    output_proj.  The forward is bev_sampling_fused exactly as BEVSampling.attend_prepared calls it under no_grad (same
+    kernels, same arguments: ``box_table`` is the caller's table or None); the backward rac_bev_sampling_bwd, which recomputes
+    the keypoints, so only the inputs are saved.  ``box_graph``: box_table_torch(query_ray) when the boxes need a gradient, else
+    None -- the kernels never read it; it receives grad_box, and plain autograd carries that on to query_ray (components 0, 1,
+    3, 4, 6, 7, as in the reference; the velocity is detached there).  The launchers are looked up as this module's globals at
+    call time."""
+
+    @staticmethod
+    def forward(ctx, value, lin_off, lin_ray, lin_sc, lin_qu, query_ray, box_graph, box_table, time_diff, hw, num_frames,
+                num_heads, num_points, depth_num, pc_range, d_region):
+        out = bev_sampling_fused(value, hw, query_ray, lin_off, lin_ray, lin_sc, lin_qu, time_diff, num_frames, num_heads,
+                                 num_points, depth_num, pc_range, d_region, box_table=box_table)
+        ctx.cfg = (hw, num_frames, num_heads, num_points, depth_num, pc_range, d_region)
+        ctx.has_table = box_table is not None
+        ctx.save_for_backward(value, lin_off, lin_ray, lin_sc, lin_qu, query_ray, time_diff, *((box_table,) if ctx.has_table else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        value, lin_off, lin_ray, lin_sc, lin_qu, query_ray, time_diff, *table = ctx.saved_tensors
+        hw, num_frames, num_heads, num_points, depth_num, pc_range, d_region = ctx.cfg
+        grad_value, grad_off, grad_ray, grad_sc, grad_qu, grad_box = bev_sampling_backward(
+            value, hw, query_ray, lin_off, lin_ray, lin_sc, lin_qu, time_diff, grad_out.contiguous(), num_frames, num_heads,
+            num_points, depth_num, pc_range, d_region, box_table=table[0] if ctx.has_table else None)
+        need = ctx.needs_input_grad
+        return (grad_value if need[0] else None, grad_off, grad_ray, grad_sc, grad_qu, None, grad_box if need[6] else None,
+                None, None, None, None, None, None, None, None, None)
+
+
+def box_table_torch(query_ray, pc_range):
+    """torch restatement of rac_box_prep_fwd: [B,Q,10] polar boxes -> [B,Q,8] (cx, cy, cz, w, l, h, cos yaw, sin yaw), with
+    autograd history."""
+    d = decode_bbox(theta_d2xy_coods(query_ray), pc_range)
+    return torch.cat([d[..., 0:6], torch.cos(d[..., 6:7]), torch.sin(d[..., 6:7])], dim=-1)
+
+
 class _MixingCore(torch.autograd.Function):
     """The AdaptiveMixing core: apply(x [B,Q,G,P,64] contiguous, params [B,Q,G*(64*64+128*P)], P, G) -> relu(LN(S @ relu(LN(x @ M))))
     as [B,Q,G*128*64].  The forward is rac_mixing_fwd in f32 mode; the backward rac_mixing_bwd, which recomputes the forward on
@@ -430,6 +470,11 @@ def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, im
 
 
 # ------------------------------------------------------------------------------- BEV branch
+def _records_grad(module, x):
+    """autograd is recording and ``x`` or a parameter of ``module`` requires grad"""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
 class ConvGRUCell(nn.Module):
     def __init__(self, input_channels, hidden_channels, kernel_size):
         super().__init__()
@@ -461,7 +506,8 @@ class ConvGRU(nn.Module):
         B, T, C, H, W = x.shape
         h = torch.zeros(B, self.hidden_channels, H, W, device=x.device, dtype=x.dtype)
         out = torch.zeros(B, T, self.hidden_channels, H, W, device=x.device, dtype=x.dtype)
-        fused = x.is_cuda and x.dtype == torch.float32 and (self.hidden_channels * H * W) % 4 == 0
+        # (the fused gate launch has no autograd history: a step that must carry a gradient runs the cell's torch ops)
+        fused = x.is_cuda and x.dtype == torch.float32 and (self.hidden_channels * H * W) % 4 == 0 and not _records_grad(self, x)
         for t in range(min(4, T)):
             if fused:
                 # gates convolution (MIOpen), then the whole element-wise update in one launch, written straight into
@@ -534,7 +580,7 @@ class RadarBEVTemporalEncoder(nn.Module):
         r = self.downsample_ratio
         gru = self.convGRU(down)
         Tv = min(4, T)
-        if not (down.is_cuda and down.dtype == torch.float32 and r == 2 and Tv < T):
+        if not (down.is_cuda and down.dtype == torch.float32 and r == 2 and Tv < T) or _records_grad(self, down):
             return self.upsample(gru.flatten(0, 1))
         return self.hidden_from_gru(gru[:, :Tv], T, H, W)
 
@@ -811,8 +857,9 @@ class BEVSampling(nn.Module):
         ``conv_pack["pixel_bias"]`` the pack holds value_proj o temporal_fusion (composed_value_pack) and the
         convolution's output IS the value stream."""
         H, W = bev_feats.shape[-2:]
+        # a packed convolution has no autograd history: a value stream that must carry a gradient takes the torch branch
         if self.temp_radar and conv_pack is not None and conv_pack.get("ws") is not None and \
-                self.temporal_encoder.fused_conv_supported(bev_feats):
+                self.temporal_encoder.fused_conv_supported(bev_feats) and not self._value_needs_grad(bev_feats):
             B, T = bev_feats.shape[:2]
             composed = bool(conv_pack.get("composed"))
             nhwc = self.temporal_encoder.forward_channel_last(bev_feats, conv_pack, q16=q16 and composed and self.attention.num_heads == 4)
@@ -851,16 +898,68 @@ class BEVSampling(nn.Module):
         return dict(ws=ws, alpha=alpha, bound=te.hidden_bound(), pixel_bias=pixel_bias.float().contiguous(),
                     pixel_bias_dead=dead.float().contiguous(), composed=True, **te.downsample_pack(H, W))
 
+    def _value_needs_grad(self, bev_feats):
+        mods = [self.attention.value_proj, self.positional_encoding] + ([self.temporal_encoder] if self.temp_radar else [])
+        return any(_records_grad(m, bev_feats) for m in mods)
+
     def attend_prepared(self, query_ray, query_feat, value, hw, time_diff, d_region, linear_out=None, box_table=None):
-        """One fused HIP kernel (rac_bev_sampling_fwd) + output_proj + identity."""
-        if linear_out is None:
+        """One fused HIP kernel (rac_bev_sampling_fwd) + output_proj + identity.  When autograd is recording and the value
+        stream, the queries, the boxes or a parameter requires grad: through _BEVSamplingCore (the same forward kernel, and
+        rac_bev_sampling_bwd behind it) where the fused backward applies -- float32 values, B == 1 -- and through
+        forward_unfused otherwise (B > 1: the reference's frame / batch pairing; bf16 and int16 value streams)."""
+        given = linear_out is not None
+        if not given:
             linear_out = (self.sampling_offset(query_feat), self.ray_points_offset(query_feat),
                           self.scale_weights(query_feat), self.attention.bev_queue_weight(query_feat))
         off, ray, sc, qu = linear_out
+        plain = torch.is_tensor(value)
+        if torch.is_grad_enabled() and ((plain and value.requires_grad) or query_feat.requires_grad or query_ray.requires_grad
+                                        or any(t_.requires_grad for t_ in linear_out)
+                                        or any(p.requires_grad for p in self.parameters())):
+            if not plain:
+                raise RuntimeError("BEVSampling.attend_prepared: an int16 block-stored value stream has no gradient path; "
+                                   "prepare the value stream in float32 under autograd")
+            if query_ray.shape[0] != 1 or value.dtype != torch.float32 or value.shape[-1] != 64:
+                return self.forward_unfused(query_ray, query_feat, value, hw, time_diff, d_region, linear_out=linear_out if given else None)
+            box_graph = box_table_torch(query_ray, self.pc_range) if query_ray.requires_grad else None
+            fused = _BEVSamplingCore.apply(value, off, ray, sc, qu, query_ray.contiguous(), box_graph, box_table, time_diff, hw,
+                                           self.num_frames, self.num_heads, self.num_points, self.depth_num, self.pc_range, d_region)
+            return self.attention.output_proj(fused) + query_feat
         fused = bev_sampling_fused(value, hw, query_ray.contiguous(), off, ray, sc, qu, time_diff, self.num_frames,
                                    self.num_heads, self.num_points, self.depth_num, self.pc_range, d_region,
                                    box_table=box_table)
         return self.attention.output_proj(fused) + query_feat
+
+    def keypoints(self, query_ray, query_feat, time_diff, d_region, linear_out=None):
+        """The keypoint chain in torch (racformer_transformer.py:490-529) -> loc [B,Q,heads,T,P,2] in [0,1], weights
+        [B,Q,heads,T,1,P]; differentiable in query_ray (not through the velocity, which the reference detaches), query_feat and
+        the three Linears."""
+        B, Q, _ = query_ray.shape
+        T, Hn, NP, D = self.num_frames, self.num_heads, self.num_points, self.depth_num
+        pc = self.pc_range
+        off, ray, sc = linear_out[:3] if linear_out is not None else \
+            (self.sampling_offset(query_feat), self.ray_points_offset(query_feat), self.scale_weights(query_feat))
+        qb = theta_d2xy_coods(query_ray)
+        off = off.reshape(B, Q, Hn * NP * D, 2)
+        off = torch.cat([off, torch.zeros_like(off[..., 0:1])], dim=-1)
+        pts = make_sample_points(qb, off, pc).view(B, Q, 1, Hn, NP * D, 3)
+        theta, dist = _warp_to_polar(pts[..., 0:2], query_ray[..., 8:].detach(), time_diff, pc)
+        base = torch.linspace(-d_region, d_region, D, device=query_feat.device, dtype=query_feat.dtype)
+        d_off = base + (torch.sigmoid(ray) * 2 - 1) * d_region / D / 2
+        dist = (dist.view(B, Q, T, Hn, NP, D) + d_off[:, :, None, None, None, :]).reshape(B, Q, T, Hn, NP * D, 1)
+        loc = theta_d2xy_coods(torch.cat([theta, dist], dim=-1)).permute(0, 1, 3, 2, 4, 5).contiguous()
+        sw = sc.reshape(B, Q, Hn, 1, self.num_levels, D * NP)
+        sw = torch.softmax(sw, dim=-1).expand(B, Q, Hn, T, self.num_levels, D * NP).contiguous()
+        return loc, sw
+
+    def forward_unfused(self, query_ray, query_feat, value, hw, time_diff, d_region, linear_out=None):
+        """The reference's decomposition: torch keypoint chain, the MSDA operator (rac_msda_fwd / rac_msda_bwd through
+        BEVSelfAttention.attend, which pairs frames and batches as the reference does for B > 1), torch frame fusion.
+        Differentiable everywhere; the comparator of the fused path and the autograd route for what rac_bev_sampling_bwd does
+        not cover (B > 1, bf16 values).  ``linear_out``: (offsets, ray logits, scale logits[, frame logits]) computed by the
+        caller; the frame logits are always formed by attend itself."""
+        loc, sw = self.keypoints(query_ray, query_feat, time_diff, d_region, linear_out)
+        return self.attention.attend(query_feat, value, loc, sw, hw)
 
     def forward(self, query_ray, query_feat, bev_feats, img_metas, d_region=0.1):
         value, hw = self.prepare_value(bev_feats)

@@ -1,6 +1,5 @@
-// s4d_device.h -- the keypoint / projection / tap arithmetic of the adaptive 4D sampling, shared by the stand-alone fused
-// sampling kernel (sampling_fused.hip) and the sampling + AdaptiveMixing kernel (mixing.hip): ONE definition, so that both
-// compute a sampling point, its camera choice and its bilinear taps with the same instructions in the same order.
+// s4d_device.h -- the keypoint / projection / tap arithmetic of the adaptive 4D sampling of the fused sampling kernel
+// (sampling_fused.hip): ONE definition of how a sampling point, its camera choice and its bilinear taps are computed.
 //   RaCFormerSampling.inner_forward  models/racformer_transformer.py:361-408  (keypoints)
 //   sampling_4d                      models/sparsebev_sampling.py:45-131      (projection, validity, first-valid-view selection)
 //   msmv op                          models/csrc/msmv_sampling/msmv_sampling_forward.cu:75-164   (bilinear footprint)

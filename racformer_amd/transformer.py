@@ -17,7 +17,6 @@ What is different is the execution plan, designed for one MI355X per sample:
 There is no CPU fallback: inputs must live on the GPU and the HIP library must be built.
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -26,10 +25,10 @@ import torch.nn.functional as F
 
 from . import _lib
 from .bbox_utils import decode_bbox, inverse_sigmoid, theta_d2xy_coods, xy2theta_d_coods
-from .fused import (SPLIT_ACT_SCALE, SPLIT_BIAS_PAD, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_sampling_backward, bev_sampling_fused,
+from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_sampling_backward, bev_sampling_fused,
                     bev_sampling_multi_fused,
                     box_prep, conv_direct, quantize_values_i16, upsample2x_image,
-                    generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, mixing_sampled_fused, mixing_sampled_supported, outproj_fused,
+                    generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, outproj_fused,
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
                     pe_head, refine_fused, row_gemm,
@@ -247,10 +246,8 @@ class RaCFormerSampling(nn.Module):
         # what a captured plan needs, whose warm-up and capture forwards all have to see the imposed choices)
         self.force_views_cyclic = False
         self._force_i = 0
-        self._last_forced = None
 
     def _next_forced(self):
-        self._last_forced = None
         if not self.force_views:
             return None
         if self.force_views_cyclic:
@@ -258,7 +255,6 @@ class RaCFormerSampling(nn.Module):
             self._force_i += 1
         else:
             v = self.force_views.pop(0)
-        self._last_forced = v
         return v
 
     def init_weights(self):
@@ -283,21 +279,6 @@ class RaCFormerSampling(nn.Module):
         if self.capture_loc is not None:
             self.capture_loc.append(res[1])
             return res if debug else res[0]
-        return res
-
-
-    def forward_into_mixing(self, query_ray, mlvl_feats, img_metas, d_region, linear_out, box_table, params, out_points=128):
-        """The sampling of forward() inside the AdaptiveMixing kernel (rac_mixing_sampled_fwd): -> the mixing output's f16 line
-        image for outproj_fused; the sampled features stay on chip.  Same hooks as forward() (capture_loc, force_views)."""
-        image_h, image_w, _ = img_metas[0]["img_shape"][0]
-        off, ray, sc = linear_out
-        res = mixing_sampled_fused(mlvl_feats, query_ray.contiguous(), off, ray, sc, img_metas[0]["time_diff"], img_metas[0]["lidar2img"],
-                                   self.num_frames, self.num_groups, self.num_points, self.depth_num, self.pc_range, d_region, image_h,
-                                   image_w, params, out_points=out_points, debug=self.capture_loc is not None, box_table=box_table,
-                                   view_in=self._next_forced())
-        if self.capture_loc is not None:
-            self.capture_loc.append(res[1])
-            return res[0]
         return res
 
 
@@ -1171,14 +1152,10 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         # producer's normalisation runs as the prologue of its consumer GEMM): 21 launches per layer instead of ~50.
         # False: library GEMMs + rac_add_ln_fwd launches (the "library_chain" plan of tests/plans.py).
         self.rowgemm = True
-        # parameter generator on the hand-written split-precision GEMM (rac_generator_fwd); False: hipBLASLt over K-concatenated images
-        self.own_generator = True
         # ((next layer index, box pointer, shape, version), pe_head output, box table, the box tensor) handed from a layer's
         # boundary launch to the next call; the decoder clears it before layer 0, and it is only honoured for the matching
         # layer index and (live, unmodified) tensor
         self._carry = None
-        # radar stream: value_proj composed into the temporal-fusion convolution (BEVSampling.composed_value_pack)
-        self.compose_radar_value = True
         # storage of the two hoisted BEV value streams (value_proj's outputs): "f32" (default, the reference's fp32 maps,
         # bev_self_attention.py:162-174), or "i16" -- int16 mantissas with one power-of-two scale per (pixel, head) block of 64
         # channels (csrc/quant.hip), written by the two producers' own epilogues (rac_conv3x3_q16_fwd, rac_value_proj_q16_fwd): half
@@ -1188,13 +1165,6 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         # 30-query head fixture misses the literal 1e-3 on one query (1.1e-3; fp32: 5.5e-4) -- so the product keeps the reference's
         # storage and bench.py reports the int16 mode beside the headline.
         self.value_storage = "f32"
-        # True: the adaptive sampling runs INSIDE the mixing kernel (rac_mixing_sampled_fwd: the mixing workgroup of an item gathers its
-        # own 96 points, bit for bit what rac_sampling4d_fwd writes; the 88 MB [B,Q,G,T*P,C] tensor of a layer is never written).
-        # Correct (tests/test_fused_gpu.py::test_mixing_sampled_equals_sampling_then_mixing, every decoder-level parity test), but NOT
-        # faster: 181 us against 88 + 92 us for the two kernels -- a workgroup that also holds the mixing's operands can keep 8 taps
-        # in flight per lane on three workgroups per CU, the stand-alone gather 16 on five, and the texture path is
-        # latency x concurrency bound -- so the default stays False; the environment variable is the A/B switch of bench.py.
-        self.fuse_sampling_mixing = os.environ.get("RAC_FUSE_SAMPLING_MIXING", "0") == "1"
         # with "i16": the producers' own epilogues quantise (True) / separate rac_quant_i16_fwd launches over fp32 streams (False: tests)
         self.fused_q16_producers = True
         self._pack_cache = {}
@@ -1235,13 +1205,9 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
              2.0 * Qn * G_ * (Pin * C_ * C_ + 128 * Pin * C_),
              2.0 * Qn * G_ * (6 * 96 * C_ * C_ + 3 * 128 * 96 * C_) if split else 2.0 * Qn * G_ * (96 * C_ * C_ + 128 * 96 * C_),
              16 if split else 32),
-            ("mixing_sampled_fwd", "mixing_c64_f16x3_kernel<4> (the same two products; the workgroup gathers its own sampled features first: "
-             "rac_mixing_sampled_fwd)", 2.0 * Qn * G_ * (Pin * C_ * C_ + 128 * Pin * C_),
-             2.0 * Qn * G_ * (6 * 96 * C_ * C_ + 3 * 128 * 96 * C_), 16),
-            ("mixing_generator_gemm", ("gemm_split_kernel (hand-written, 3 f16 products, loader waves + LDS-DMA ring)" if self.own_generator
-                                       else "parameter_generator GEMM (hipBLASLt f16, K-concatenated hi/lo operands)") if split
+            ("mixing_generator_gemm", "gemm_split_kernel (hand-written, 3 f16 products, loader waves + LDS-DMA ring)" if split
              else "parameter_generator GEMM (rocBLAS fp32)",
-             2.0 * Qn * E * gen_cols, 2.0 * Qn * gen_cols * ((3 * E + (0 if self.own_generator else 64)) if split else E),
+             2.0 * Qn * E * gen_cols, 2.0 * Qn * gen_cols * (3 * E if split else E),
              16 if split else 32),
             ("mixing_out_proj_gemm", "gemm_split_kernel (hand-written split-K GEMM, 3 f16 products, LDS-DMA staging)" if split
              else "out_proj split-K batched GEMM (rocBLAS fp32)",
@@ -1292,11 +1258,11 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
             conv_params = [te.temporal_fusion.weight, up.weight, te.downsample.weight, cell.gates_conv.weight,
                            cell.matching_layer.weight] + \
                 [m.bias for m in (te.temporal_fusion, up, cell.gates_conv, cell.matching_layer, te.downsample) if m.bias is not None]
-            if self.compose_radar_value:
-                pe_, vp = rbs.positional_encoding, rbs.attention.value_proj
-                conv_pack = self._cached(f"conv_value_pack_{Hr}x{Wr}", conv_params + [vp.weight, vp.bias, pe_.row_embed.weight,
-                                                                                     pe_.col_embed.weight],
-                                         lambda: rbs.composed_value_pack(Hr, Wr))
+            # value_proj composed into the temporal-fusion convolution (BEVSampling.composed_value_pack; {}: not for these shapes)
+            pe_, vp = rbs.positional_encoding, rbs.attention.value_proj
+            conv_pack = self._cached(f"conv_value_pack_{Hr}x{Wr}", conv_params + [vp.weight, vp.bias, pe_.row_embed.weight,
+                                                                                 pe_.col_embed.weight],
+                                     lambda: rbs.composed_value_pack(Hr, Wr))
             if not conv_pack:
                 def plain_pack():
                     ws, alpha = pack_conv3x3_weight(te.temporal_fusion.weight)
@@ -1355,7 +1321,7 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
                                                  mix.out_proj.weight, self.norm1.weight, self.norm1.bias], lambda: mix.split_packs(
                 float(self.norm1.weight.abs().max()) * math.sqrt(self.embed_dims) + float(self.norm1.bias.abs().max())))
         # the wide Linear on the same split-precision kernel as the generator (it reads the same f16 image of norm1's output)
-        wide_img = self._cached("wide_img", [w], lambda: pack_gemm_split_weight(w)) if packs and self.own_generator else (None, None)
+        wide_img = self._cached("wide_img", [w], lambda: pack_gemm_split_weight(w)) if packs else (None, None)
         out_proj_split = None if packs else self._cached("out_proj_split", [mix.out_proj.weight], mix.split_out_proj)
         value_scales = None
         if i16:
@@ -1403,11 +1369,10 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         rowgemm_launch([row_gemm([row_seg(o)], p.out_proj.weight, p.out_proj.bias, attn)], n)
         # x1 = norm1(x + attn) (+ its f16 image for the generator GEMM);  the eleven Linears of the three sampling modules
         x1 = new(B, Q, E)
-        own_gen = bool(packs) and self.own_generator
-        x1_split = torch.empty(n, 2 * E if own_gen else 3 * E + SPLIT_BIAS_PAD, device=dev, dtype=torch.float16) if packs else None
+        x1_split = torch.empty(n, 2 * E, device=dev, dtype=torch.float16) if packs else None
         wide_n = prepared["wide_w"].shape[0]
         wimg, walpha = prepared.get("wide_img", (None, None))
-        if own_gen and wimg is not None:
+        if packs and wimg is not None:
             # norm1 as its own row-wise launch (fp32 rows + f16 line image), then the 2189 outputs on the weights-stationary
             # split-precision kernel: 6 + 7 us against 30 for the fp32-MFMA row GEMM, whose 57 row tiles each re-read all weights
             add_ln(attn.view(B, Q, E), self.norm1, residual=x, out=x1, split=True, split_lines=True, split_out=x1_split)
@@ -1415,7 +1380,7 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
             wide = wide.view(B, Q, -1)[..., :wide_n]
         else:
             wide = new(B, Q, wide_n)
-            rowgemm_launch([row_gemm([row_seg(attn, residual=x, norm=self.norm1, x_out=x1, split_out=x1_split, split_lines=own_gen)],
+            rowgemm_launch([row_gemm([row_seg(attn, residual=x, norm=self.norm1, x_out=x1, split_out=x1_split, split_lines=bool(packs))],
                                      prepared["wide_w"], prepared["wide_b"], wide)], n)
         lin = wide.split(prepared["wide_widths"], dim=-1)
         rb, lb = self.sampling_radar_bev, self.sampling_lss_bev
@@ -1439,24 +1404,8 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
             bev_sampling_fused(prepared["lss_value"], prepared["lss_hw"], qb, l_off, l_ray, l_sc, l_qu, time_diff,
                                lb.num_frames, lb.num_heads, lb.num_points, lb.depth_num, lb.pc_range, d_region,
                                box_table=table, out=bev[1])
-        smp, mix = self.sampling, self.mixing
-        if (self.fuse_sampling_mixing and own_gen and mix.out_points == 128 and mix.eff_in_dim == 64 and mix.eff_out_dim == 64
-                and mix.in_points == smp.num_frames * smp.num_points * smp.depth_num and smp.num_groups == mix.n_groups
-                and mixing_sampled_supported(mlvl_feats, smp.num_frames, smp.num_points * smp.depth_num)):
-            # generator -> ONE kernel for the adaptive sampling and both mixings (the mixing workgroup gathers its own item while its
-            # parameters stream in: the [B,Q,G,T*P,C] tensor is never written) -> out_proj
-            params = generator_fused(x1_split, packs["gen_img"], mix.parameter_generator.bias, packs["gen_img_alpha"]).view(B, Q, -1)
-            img = smp.forward_into_mixing(qb, mlvl_feats, img_metas, d_region, lin[0:3], table, params, out_points=mix.out_points)
-            partials = outproj_fused(img, packs["out_w"], packs["out_slices"])
-            sampled_feat = None
-            if stages is not None:      # (the parity probes want the sampled features themselves: the stand-alone kernel, same choices)
-                image_h, image_w, _ = img_metas[0]["img_shape"][0]
-                sampled_feat = sampling4d_fused(mlvl_feats, qb, *lin[0:3], img_metas[0]["time_diff"], img_metas[0]["lidar2img"], smp.num_frames,
-                                                smp.num_groups, smp.num_points, smp.depth_num, smp.pc_range, d_region, image_h, image_w,
-                                                box_table=table, view_in=smp._last_forced)
-        else:
-            sampled_feat = self._sample(qb, x1, mlvl_feats, img_metas, d_region, lin[0:3], table)
-            partials = self.mixing.out_proj_partials(sampled_feat, x1, prepared["out_proj_split"], None, packs, x1_split)
+        sampled_feat = self._sample(qb, x1, mlvl_feats, img_metas, d_region, lin[0:3], table)
+        partials = self.mixing.out_proj_partials(sampled_feat, x1, prepared["out_proj_split"], None, packs, x1_split)
         p_scale = packs["out_alpha"] if packs else 1.0
         # both BEV output projections in one launch
         proj = new(2, n, E)

@@ -51,6 +51,7 @@
  *   rac_bev_sampling_fwd <- BEVSampling keypoints + BEVSelfAttention's MSDA + frame fusion, fused
  *                        models/racformer_transformer.py:490-529, models/bev_self_attention.py:176-213
  *   rac_bev_sampling_bwd <- autograd of the same chain (keypoints, MSDA, frame fusion) in one launch
+ *   rac_sampling4d_bwd <- autograd of RaCFormerSampling.inner_forward + sampling_4d + msmv op in one launch
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -61,7 +62,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 14
+#define RAC_ABI_VERSION 15
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -161,6 +162,38 @@ int rac_sampling4d_fwd(const void *const *feats, const int32_t *hw, int L, const
                        int G, int Q,
                        int NP, int D, int C, const float *pc_range, const float *depth_base, float d_region,
                        float image_h, float image_w, float eps, int dtype, int compact, void *stream);
+
+/* Backward of rac_sampling4d_fwd in one launch: float32 features, 64 channels per group.  Nothing of the forward is saved:
+ * location, camera choice, level weights and bilinear taps are recomputed from the forward's inputs with the forward's own
+ * device functions (the same bits).  Inputs as rac_sampling4d_fwd (the same pointers, row strides and host arrays, view_in
+ * included), plus
+ *   grad_out     : device f32 [B,Q,G,T*NP*D,64]
+ * Outputs, all device f32:
+ *   grad_feats[l]: HOST array of L device pointers, each of the shape of feats[l], ZERO-FILLED BY THE CALLER; float atomics
+ *                  (sums in arrival order).  NULL array: no feature gradient wanted, the scatter is skipped.
+ *   grad_offsets : rows of G*NP*D*3 (stride gld_off);  grad_ray: rows of D (gld_ray);
+ *   grad_scale   : rows of G*T*NP*D*L (gld_scale): gradient of the LOGITS (softmax backward over L), written at the (g', t')
+ *                  slot the forward reads a keypoint's weights from (sparsebev_sampling.py:113-120; a bijection)
+ *                  -- the three may be column slices of one gradient of a fused Linear output
+ *   grad_box     : [B,Q,8] gradient of all eight box-table entries (z, h and the rotation act through the projection)
+ *   grad_loc_out, grad_w_out : optional debug outputs [S,Q,P,2] / [S,Q,P,L] (NULL to skip): per keypoint the gradient of its
+ *                  image location (u, v) and of its softmaxed level weights, before the chain tail
+ *   loc_out, w_out : optional debug outputs [S,Q,P,3] / [S,Q,P,L] (NULL, NULL to skip): the keypoints as THIS kernel recomputed
+ *                  them, in the forward's loc_out / w_out format (bit-equal to the forward's)
+ * Every element of every output except grad_feats has one writer and a fixed summation order (bit-reproducible).  homo passes
+ * the gradient where homo > eps; the two clamps to [0,1] inside [0,1] inclusive; a point no camera sees is sampled (and
+ * differentiated) in camera 0, as in the reference; velocity, time_diff and lidar2img get no gradient.  Refused before any
+ * launch: dtype other than RAC_F32, C != 64, L outside {1, 2, 4, 5}, NP*D > 128, T*G*NP*D keypoints per query beyond the 64 KB
+ * LDS staging ((5 + 2 L) floats each). */
+int rac_sampling4d_bwd(const void *const *feats, const int32_t *hw, int L, const float *query_bbox,
+                       const float *box_table, const float *offsets, const float *ray_logits,
+                       const float *scale_logits, const float *time_diff, const float *lidar2img,
+                       const unsigned char *view_in, const float *grad_out, void *const *grad_feats,
+                       float *grad_offsets, float *grad_ray, float *grad_scale, float *grad_box, float *grad_loc_out,
+                       float *grad_w_out, float *loc_out, float *w_out, int ld_off, int ld_ray, int ld_scale,
+                       int gld_off, int gld_ray, int gld_scale, int B, int T, int N, int G, int Q, int NP, int D, int C,
+                       const float *pc_range, const float *depth_base, float d_region, float image_h, float image_w,
+                       float eps, int dtype, void *stream);
 
 /* BEV deformable cross-attention of one decoder layer, fully fused (keypoints -> per-frame
  * deformable attention -> softmax-over-frames fusion).  Replaces BEVSampling.inner_forward's keypoint

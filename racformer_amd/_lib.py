@@ -28,6 +28,7 @@ SIGNATURES = {
     "rac_regroup_multi_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "rac_box_prep_fwd": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rac_sampling4d_fwd": (_i, [_vp, _vp, _i] + [_vp] * 11 + [_i] * 3 + [_i] * 8 + [_vp, _vp] + [_f] * 4 + [_i, _i, _vp]),
+    "rac_sampling4d_bwd": (_i, [_vp, _vp, _i] + [_vp] * 18 + [_i] * 6 + [_i] * 8 + [_vp, _vp] + [_f] * 4 + [_i, _vp]),
     "rac_msmv_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
     "rac_msmv_v2_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
     "rac_msmv_v2_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),

@@ -97,6 +97,75 @@ def sampling4d_fused(mlvl_feats, query_bbox, offsets, ray_logits, scale_logits, 
     return (out, loc_out, w_out) if want_debug else out
 
 
+def sampling4d_backward(mlvl_feats, query_bbox, offsets, ray_logits, scale_logits, time_diff, lidar2img, grad_out,
+                        num_frames, num_groups, num_points, depth_num, pc_range, d_region, image_h, image_w, eps=1e-5,
+                        box_table=None, view_in=None, grad_offsets=None, grad_ray=None, grad_scale=None, want_feats=True,
+                        debug=False):
+    """Backward of sampling4d_fused (rac_sampling4d_bwd): the forward's arguments and grad_out [B,Q,G,T*P,64] ->
+    (grad_feats (a list shaped as mlvl_feats; None with ``want_feats=False``: the scatter is skipped), grad_offsets, grad_ray,
+    grad_scale (of the logits), grad_box [B,Q,8]); with ``debug`` also the kernel's per-keypoint gradients and its recomputed
+    keypoints (grad_loc [S,Q,P,2], grad_w [S,Q,P,L], loc [S,Q,P,3], w [S,Q,P,L]).  ``grad_offsets`` .. ``grad_scale``:
+    destinations with unit inner stride and a row stride of their own (column slices of one gradient of a fused Linear
+    output); allocated when not given.  Every element of them is written.  ``view_in``: what the forward was given.
+    float32 features only."""
+    feats = list(mlvl_feats)
+    L = len(feats)
+    _lib.require_gpu(*feats, query_bbox, time_diff, lidar2img, grad_out, what="sampling4d_backward")
+    if any(f.dtype != torch.float32 for f in feats):
+        raise RuntimeError("sampling4d_backward: float32 features only")
+    B, Q, _ = query_bbox.shape
+    T, G, NP, D = num_frames, num_groups, num_points, depth_num
+    P = NP * D
+    S, N, _, _, C = feats[0].shape
+    if S != B * T * G or lidar2img.shape[1] != T * N:
+        raise RuntimeError("sampling4d_backward: feature slots / lidar2img do not match B*T*G / T*N")
+    if tuple(grad_out.shape) != (B, Q, G, T * P, C) or grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
+        raise RuntimeError(f"sampling4d_backward: grad_out must be a contiguous float32 [{B},{Q},{G},{T * P},{C}]")
+    p_off, ld_off = _rows(offsets, G * P * 3, "sampling4d_backward(offsets)")
+    p_ray, ld_ray = _rows(ray_logits, D, "sampling4d_backward(ray_logits)")
+    p_sc, ld_sc = _rows(scale_logits, G * T * P * L, "sampling4d_backward(scale_logits)")
+    if box_table is None:
+        box_table = box_prep(query_bbox, pc_range)
+    if view_in is not None and (view_in.dtype != torch.uint8 or tuple(view_in.shape) != (S, Q, P) or not view_in.is_cuda
+                                or not view_in.is_contiguous()):
+        raise RuntimeError(f"sampling4d_backward: view_in must be a contiguous CUDA uint8 [{S},{Q},{P}] tensor")
+    dev = query_bbox.device
+
+    def dest(t_, width):
+        return torch.empty(B, Q, width, device=dev, dtype=torch.float32) if t_ is None else t_
+
+    grad_offsets, grad_ray, grad_scale = dest(grad_offsets, G * P * 3), dest(grad_ray, D), dest(grad_scale, G * T * P * L)
+    p_goff, gld_off = _rows(grad_offsets, G * P * 3, "sampling4d_backward(grad_offsets)")
+    p_gray, gld_ray = _rows(grad_ray, D, "sampling4d_backward(grad_ray)")
+    p_gsc, gld_sc = _rows(grad_scale, G * T * P * L, "sampling4d_backward(grad_scale)")
+    grad_feats = [torch.zeros_like(f) for f in feats] if want_feats else None
+    grad_box = torch.empty(B, Q, 8, device=dev, dtype=torch.float32)
+    grad_loc = grad_w = loc = w = None
+    if debug:
+        grad_loc = torch.empty(S, Q, P, 2, device=dev, dtype=torch.float32)
+        grad_w = torch.empty(S, Q, P, L, device=dev, dtype=torch.float32)
+        loc = torch.empty(S, Q, P, 3, device=dev, dtype=torch.float32)
+        w = torch.empty(S, Q, P, L, device=dev, dtype=torch.float32)
+    ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
+    gptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in grad_feats]) if want_feats else None
+    hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[2:4]])
+    pc = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
+    ev = _lib.timer.record("sampling4d_bwd") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_sampling4d_bwd(
+        ptrs, hw, L, _lib.ptr(query_bbox), _lib.ptr(box_table), p_off, p_ray, p_sc, _lib.ptr(time_diff), _lib.ptr(lidar2img),
+        _lib.ptr(view_in) if view_in is not None else None, _lib.ptr(grad_out), gptrs, p_goff, p_gray, p_gsc, _lib.ptr(grad_box),
+        _lib.ptr(grad_loc) if debug else None, _lib.ptr(grad_w) if debug else None, _lib.ptr(loc) if debug else None,
+        _lib.ptr(w) if debug else None, ld_off, ld_ray, ld_sc, gld_off, gld_ray, gld_sc, B, T, N, G, Q, NP, D, C, pc,
+        _depth_base(float(d_region), D), float(d_region), float(image_h), float(image_w), float(eps), _lib.RAC_F32, _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_sampling4d_bwd")
+    res = (grad_feats, grad_offsets, grad_ray, grad_scale, grad_box)
+    return res + (grad_loc, grad_w, loc, w) if debug else res
+
+
 def bev_sampling_fused(value, hw, query_bbox, offsets, ray_logits, scale_logits, queue_logits, time_diff,
                        num_frames, num_heads, num_points, depth_num, pc_range, d_region, debug=False, box_table=None,
                        out=None):

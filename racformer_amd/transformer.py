@@ -32,7 +32,7 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, 
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
                     pe_head, refine_fused, row_gemm,
-                    row_seg, rowgemm_launch, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
+                    row_seg, rowgemm_launch, sampling4d_backward, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
 from .msda import msda_backward, msda_forward
 from .msmv import msmv_backward, msmv_forward, msmv_v2_backward, msmv_v2_forward
 
@@ -265,17 +265,29 @@ class RaCFormerSampling(nn.Module):
     def forward(self, query_ray, query_feat, mlvl_feats, img_metas, d_region=0.1, linear_out=None, debug=False,
                 box_table=None):
         """One fused HIP kernel (rac_sampling4d_fwd).  ``linear_out`` = (offsets, ray logits, scale
-        logits) if the caller already ran the three Linears as part of a wider GEMM."""
+        logits) if the caller already ran the three Linears as part of a wider GEMM.  When autograd is recording and a
+        feature level, the boxes or a Linear output (its own, from query_feat and the parameters, or a given one) requires grad: through
+        _Sampling4DCore (the same forward launch with the same arguments, and rac_sampling4d_bwd behind it; bf16 features
+        keep this forward and raise at backward time)."""
         image_h, image_w, _ = img_metas[0]["img_shape"][0]
         if linear_out is None:
             linear_out = (self.sampling_offset(query_feat), self.ray_points_offset(query_feat),
                           self.scale_weights(query_feat))
         off, ray, sc = linear_out
-        res = sampling4d_fused(mlvl_feats, query_ray.contiguous(), off, ray, sc, img_metas[0]["time_diff"],
-                               img_metas[0]["lidar2img"], self.num_frames, self.num_groups, self.num_points,
-                               self.depth_num, self.pc_range, d_region, image_h, image_w,
-                               debug=debug or self.capture_loc is not None, box_table=box_table, view_in=self._next_forced(),
-                               compact=compact_variant(img_metas[0].get("_rac_coverage")))
+        want_debug = debug or self.capture_loc is not None
+        view_in, compact = self._next_forced(), compact_variant(img_metas[0].get("_rac_coverage"))
+        # (query_feat and the parameters reach the kernel only through the Linear outputs, which then require grad themselves)
+        if torch.is_grad_enabled() and (any(f.requires_grad for f in mlvl_feats) or query_ray.requires_grad
+                                        or any(t_.requires_grad for t_ in linear_out)):
+            box_graph = box_table_torch(query_ray, self.pc_range) if query_ray.requires_grad else None
+            cfg = (self.num_frames, self.num_groups, self.num_points, self.depth_num, self.pc_range, d_region, image_h, image_w)
+            res = _Sampling4DCore.apply(off, ray, sc, query_ray.contiguous(), box_graph, box_table, view_in,
+                                        img_metas[0]["time_diff"], img_metas[0]["lidar2img"], cfg, want_debug, compact, *mlvl_feats)
+        else:
+            res = sampling4d_fused(mlvl_feats, query_ray.contiguous(), off, ray, sc, img_metas[0]["time_diff"],
+                                   img_metas[0]["lidar2img"], self.num_frames, self.num_groups, self.num_points,
+                                   self.depth_num, self.pc_range, d_region, image_h, image_w,
+                                   debug=want_debug, box_table=box_table, view_in=view_in, compact=compact)
         if self.capture_loc is not None:
             self.capture_loc.append(res[1])
             return res if debug else res[0]
@@ -381,6 +393,46 @@ class _BEVSamplingCore(torch.autograd.Function):
         need = ctx.needs_input_grad
         return (grad_value if need[0] else None, grad_off, grad_ray, grad_sc, grad_qu, None, grad_box if need[6] else None,
                 None, None, None, None, None, None, None, None, None)
+
+
+class _Sampling4DCore(torch.autograd.Function):
+    """The RaCFormerSampling core: apply(lin_off, lin_ray, lin_sc (the three Linear outputs), query_ray [B,Q,10], box_graph,
+    box_table, view_in, time_diff, lidar2img, (T, G, NP, D, pc_range, d_region, image_h, image_w), debug, compact, *feats) ->
+    [B,Q,G,T*P,64] (with ``debug``: also the kernel's loc_out and w_out, marked non-differentiable).  The forward is
+    sampling4d_fused exactly as RaCFormerSampling.forward calls it under no_grad (same kernel, same arguments); the backward
+    rac_sampling4d_bwd, which recomputes the keypoints, so only the inputs are saved.  ``box_graph``:
+    box_table_torch(query_ray) when the boxes need a gradient, else None -- the kernels never read it; it receives grad_box, and
+    plain autograd carries that on to query_ray (not through the velocity, which the reference detaches).  time_diff and
+    lidar2img get no gradient.  The launchers are looked up as this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, lin_off, lin_ray, lin_sc, query_ray, box_graph, box_table, view_in, time_diff, lidar2img, cfg, debug,
+                compact, *feats):
+        num_frames, num_groups, num_points, depth_num, pc_range, d_region, image_h, image_w = cfg
+        res = sampling4d_fused(list(feats), query_ray, lin_off, lin_ray, lin_sc, time_diff, lidar2img, num_frames, num_groups,
+                               num_points, depth_num, pc_range, d_region, image_h, image_w, debug=debug, box_table=box_table,
+                               view_in=view_in, compact=compact)
+        ctx.cfg = cfg
+        ctx.has = (box_table is not None, view_in is not None)
+        ctx.save_for_backward(lin_off, lin_ray, lin_sc, query_ray, time_diff, lidar2img,
+                              *((box_table,) if ctx.has[0] else ()), *((view_in,) if ctx.has[1] else ()), *feats)
+        if debug:
+            ctx.mark_non_differentiable(res[1], res[2])
+        return res
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        lin_off, lin_ray, lin_sc, query_ray, time_diff, lidar2img, *rest = ctx.saved_tensors
+        table = rest.pop(0) if ctx.has[0] else None
+        view_in = rest.pop(0) if ctx.has[1] else None
+        num_frames, num_groups, num_points, depth_num, pc_range, d_region, image_h, image_w = ctx.cfg
+        need = ctx.needs_input_grad
+        want_feats = any(need[12:])
+        grad_feats, grad_off, grad_ray, grad_sc, grad_box = sampling4d_backward(
+            rest, query_ray, lin_off, lin_ray, lin_sc, time_diff, lidar2img, grad_out.contiguous(), num_frames, num_groups,
+            num_points, depth_num, pc_range, d_region, image_h, image_w, box_table=table, view_in=view_in, want_feats=want_feats)
+        gf = [g if n else None for g, n in zip(grad_feats, need[12:])] if want_feats else [None] * len(rest)
+        return (grad_off, grad_ray, grad_sc, None, grad_box if need[4] else None, None, None, None, None, None, None, None, *gf)
 
 
 def box_table_torch(query_ray, pc_range):

@@ -52,6 +52,8 @@
  *                        models/racformer_transformer.py:490-529, models/bev_self_attention.py:176-213
  *   rac_bev_sampling_bwd <- autograd of the same chain (keypoints, MSDA, frame fusion) in one launch
  *   rac_sampling4d_bwd <- autograd of RaCFormerSampling.inner_forward + sampling_4d + msmv op in one launch
+ *   rac_regroup_bwd / rac_regroup_multi_bwd <- autograd of the regroup's permute().contiguous(), models/racformer_transformer.py:112-124
+ *   rac_refine_bwd    <- autograd of refine_bbox + velocity scaling + theta_d2xy_coods (the ops rac_refine_fwd replaces)
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -62,7 +64,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 15
+#define RAC_ABI_VERSION 16
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -128,6 +130,16 @@ int rac_regroup_fwd(const float *in, void *out, int B, int T, int N, int G, int 
  * of L device pointers, hw HOST L x (H, W); C % 4 == 0 and H*W % 4 == 0 on every level. */
 int rac_regroup_multi_fwd(int L, const float *const *ins, void *const *outs, const int32_t *hw, int B, int T, int N, int G,
                           int C, int out_dtype, void *stream);
+
+/* Backward of the regroup, the inverse transposition: grad_out [B*T*G, N, H, W, C] f32 -> grad_in [B, T*N, G*C, H, W] f32.
+ * A pure permutation: every element of grad_in is written exactly once (no pre-zeroing, no atomics), bit-exact. */
+int rac_regroup_bwd(const float *grad_out, float *grad_in, int B, int T, int N, int G, int C, int H, int W, void *stream);
+
+/* The same backward for L levels in ONE launch (16-byte accesses on both sides): grad_outs / grad_ins HOST arrays of L device
+ * pointers, hw HOST L x (H, W); C % 4 == 0 and H*W % 4 == 0 on every level.  The caller lists only the levels that need a
+ * gradient. */
+int rac_regroup_multi_bwd(int L, const float *const *grad_outs, float *const *grad_ins, const int32_t *hw, int B, int T, int N,
+                          int G, int C, void *stream);
 
 /* Per-query box constants shared by the fused sampling kernels: table[b,q] = (cx, cy, cz, w, l, h,
  * cos yaw, sin yaw) = decode_bbox(theta_d2xy_coods(query_bbox)) (models/bbox/utils.py:66-90), once per
@@ -338,6 +350,17 @@ int rac_pe_head_fwd(const float *x, int ld_x, const float *weight, const float *
  *   bbox_pred [B*Q,10] (polar, next layer's input), bbox_xy [B*Q,10] (normalised xy, the layer's output). */
 int rac_refine_fwd(const float *proposal, const float *delta, const float *time_diff_safe, float *bbox_pred,
                    float *bbox_xy, int B, int Q, int T, float num_ray, void *stream);
+
+/* Backward of rac_refine_fwd, closed form, the forward quantities recomputed from its inputs:
+ *   grad_pred [B*Q,10], grad_xy [B*Q,10] (gradients of bbox_pred / bbox_xy; either may be NULL = absent, it is then not read)  ->
+ *   grad_delta [B*Q,10], grad_proposal [B*Q,10] (every element written; components 3..9 of grad_proposal are zero).
+ * Gates as torch's autograd of the reference's ops: clamp passes the gradient on the closed interval and blocks it outside
+ * (the [0,1] clamp of theta_d2xy_coods and of inverse_sigmoid); inverse_sigmoid's clamp(min=eps) of x and of 1-x each gate their
+ * own factor; the velocity division by time_diff_safe[:,1] applies only when T > 1; theta receives gradient from bbox_pred[0]
+ * and, through cos / sin, from bbox_xy[0:2]. */
+int rac_refine_bwd(const float *proposal, const float *delta, const float *time_diff_safe, const float *grad_pred,
+                   const float *grad_xy, float *grad_delta, float *grad_proposal, int B, int Q, int T, float num_ray,
+                   void *stream);
 
 /* Boundary between two decoder layers in one launch: rac_refine_fwd for the finished layer and, for the boxes it produces,
  * the first two launches of the next layer -- rac_box_prep_fwd (box_table [B*Q,8]) and rac_pe_head_fwd (pe_out [B*Q,256]

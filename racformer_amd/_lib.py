@@ -26,6 +26,8 @@ SIGNATURES = {
     "rac_msda_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rac_regroup_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rac_regroup_multi_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "rac_regroup_bwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
+    "rac_regroup_multi_bwd": (_i, [_i, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
     "rac_box_prep_fwd": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rac_sampling4d_fwd": (_i, [_vp, _vp, _i] + [_vp] * 11 + [_i] * 3 + [_i] * 8 + [_vp, _vp] + [_f] * 4 + [_i, _i, _vp]),
     "rac_sampling4d_bwd": (_i, [_vp, _vp, _i] + [_vp] * 18 + [_i] * 6 + [_i] * 8 + [_vp, _vp] + [_f] * 4 + [_i, _vp]),
@@ -41,6 +43,7 @@ SIGNATURES = {
     "rac_pe_head_fwd": (_i, [_vp, _i] + [_vp] * 5 + [_i, _i, _f, _vp]),
     "rac_layer_boundary_fwd": (_i, [_vp] * 12 + [_i] * 4 + [_f, _f, _vp]),
     "rac_refine_fwd": (_i, [_vp] * 5 + [_i] * 3 + [_f, _vp]),
+    "rac_refine_bwd": (_i, [_vp] * 7 + [_i] * 3 + [_f, _vp]),
     "rac_head_finish_fwd": (_i, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _i, _vp, _vp]),
     "rac_mixing_fwd": (_i, [_vp, _vp, _f, _vp, _vp, _f] + [_i] * 6 + [_f, _i, _vp]),
     "rac_mixing_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp] + [_i] * 5 + [_f, _vp]),

@@ -64,6 +64,90 @@ extern "C" int rac_refine_fwd(const float *proposal, const float *delta, const f
     return rac_launch_status("rac_refine_fwd");
 }
 
+// ------------------------------------------------------------------------------------------------ backward
+// Closed-form backward of refine_kernel: (grad_pred, grad_xy) -> (grad_delta, grad_proposal), one thread per query, the forward
+// quantities recomputed from proposal, delta and time_diff_safe.  The gates are torch's for the ops the reference uses: clamp
+// passes the gradient on the closed interval and blocks it outside (the [0,1] clamp of theta_d2xy_coods on the value the forward
+// kernel computes, the [0,1] clamp of inverse_sigmoid), and inverse_sigmoid's clamp(min=eps) of x and of 1-x each gate their
+// own factor of d log(x1/x2) = dx1/x1 - dx2/x2.  A null grad_pred or grad_xy is skipped, not read.
+__device__ __forceinline__ float ref_inverse_sigmoid_grad(float x)
+{
+    if (!(x >= 0.f && x <= 1.f))
+        return 0.f;
+    const float y = 1.f - x;
+    return (x >= 1e-5f ? 1.f / x : 0.f) + (y >= 1e-5f ? 1.f / y : 0.f);
+}
+
+__global__ __launch_bounds__(256) void refine_bwd_kernel(const float *__restrict__ prop, const float *__restrict__ delta,
+                                                         const float *__restrict__ td_safe, const float *__restrict__ gpred,
+                                                         const float *__restrict__ gxy, float *__restrict__ gdelta,
+                                                         float *__restrict__ gprop, int n, int Q, int T, float num_ray)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    const float *p = prop + (size_t)i * 10, *d = delta + (size_t)i * 10;
+    float go[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+        go[k] = gpred ? gpred[(size_t)i * 10 + k] : 0.f;
+    const float s0 = ref_sigmoid(d[0]);
+    const float o1 = ref_sigmoid(d[1] + ref_inverse_sigmoid(p[1]));
+    const float o2 = ref_sigmoid(d[2] + ref_inverse_sigmoid(p[2]));
+    if (gxy) {
+        const float *gx = gxy + (size_t)i * 10;
+        const float o0 = p[0] + (s0 * 2.f - 1.f) / num_ray;
+        const float ang = o0 * REF_TWO_PI, rad = o1 * 65.0f;
+        const float cs = cosf(ang), sn = sinf(ang);
+        const float ux = (51.2f + rad * cs) / 102.4f, uy = (51.2f + rad * sn) / 102.4f;
+        const float gux = (ux >= 0.f && ux <= 1.f) ? gx[0] / 102.4f : 0.f;
+        const float guy = (uy >= 0.f && uy <= 1.f) ? gx[1] / 102.4f : 0.f;
+        go[0] += (guy * cs - gux * sn) * rad * REF_TWO_PI;
+        go[1] += (gux * cs + guy * sn) * 65.0f;
+#pragma unroll
+        for (int k = 2; k < 10; ++k)
+            go[k] += gx[k];
+    }
+    float gd[10], gp[10];
+    gd[0] = go[0] * (2.f * s0 * (1.f - s0) / num_ray);
+    gp[0] = go[0];
+    const float gs1 = go[1] * (o1 * (1.f - o1)), gs2 = go[2] * (o2 * (1.f - o2));
+    gd[1] = gs1;
+    gd[2] = gs2;
+    gp[1] = gs1 * ref_inverse_sigmoid_grad(p[1]);
+    gp[2] = gs2 * ref_inverse_sigmoid_grad(p[2]);
+#pragma unroll
+    for (int k = 3; k < 10; ++k) {
+        gd[k] = go[k];
+        gp[k] = 0.f;
+    }
+    if (T > 1) {
+        const float td = td_safe[(i / Q) * T + 1];
+        gd[8] = go[8] / td;
+        gd[9] = go[9] / td;
+    }
+    float *pd = gdelta + (size_t)i * 10, *pp = gprop + (size_t)i * 10;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+        pd[k] = gd[k];
+        pp[k] = gp[k];
+    }
+}
+
+extern "C" int rac_refine_bwd(const float *proposal, const float *delta, const float *time_diff_safe, const float *grad_pred,
+                              const float *grad_xy, float *grad_delta, float *grad_proposal, int B, int Q, int T, float num_ray,
+                              void *stream)
+{
+    RAC_CHECK_ARG(B >= 0 && Q >= 0 && T >= 1 && num_ray > 0.f, "rac_refine_bwd: bad sizes B=%d Q=%d T=%d", B, Q, T);
+    if (B * Q == 0)
+        return 0;
+    RAC_CHECK_ARG(proposal && delta && time_diff_safe && grad_delta && grad_proposal, "rac_refine_bwd: null pointer");
+    const int n = B * Q;
+    hipLaunchKernelGGL(refine_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, proposal, delta, time_diff_safe,
+                       grad_pred, grad_xy, grad_delta, grad_proposal, n, Q, T, num_ray);
+    return rac_launch_status("rac_refine_bwd");
+}
+
 // ------------------------------------------------------------------------------------------------ head outputs
 // What RaCFormerTransformer.forward and RaCFormer_head.forward do to the stacked decoder outputs, one launch instead of five:
 //   cls  <- nan_to_num(cls)                                      (racformer_transformer.py:58)

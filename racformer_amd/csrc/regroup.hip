@@ -185,3 +185,127 @@ extern "C" int rac_regroup_fwd(const float *in, void *out, int B, int T, int N, 
                            (unsigned short *)out, T, N, G, C, HW);
     return rac_launch_status("rac_regroup_fwd");
 }
+
+// ---- backward: the inverse transposition ---------------------------------------------------------------------------------------
+//     grad_out [B*T*G, N, H, W, C]  ->  grad_in [B, T*N, G*C, H, W]      (both f32)
+// i.e. for every (b,t,n,g) a [H*W][C] -> [C][H*W] transpose: a pure permutation (every element of grad_in written exactly once,
+// no atomics, bit-exact), with the tile structure of the forward kernels.
+__global__ __launch_bounds__(256) void regroup_bwd_kernel(const float *__restrict__ gout, float *__restrict__ gin, int T, int N,
+                                                          int G, int C, int HW)
+{
+    __shared__ float tile[64][65];                       // [pixel][channel]
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 64 x 4
+    const int hw0 = blockIdx.x * 64;
+    const int c0 = blockIdx.y * 64;
+    int z = blockIdx.z;  // ((b*T+t)*N+n)*G+g
+    const int g = z % G; z /= G;
+    const int n = z % N; z /= N;
+    const int t = z % T;
+    const int b = z / T;
+    const float *src = gout + ((((size_t)b * T + t) * G + g) * N + n) * (size_t)HW * C;
+    float *dst = gin + ((((size_t)b * T + t) * N + n) * G + g) * (size_t)C * HW;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int hw = hw0 + ty * 16 + r, c = c0 + tx;
+        if (c < C && hw < HW)
+            tile[ty * 16 + r][tx] = src[(size_t)hw * C + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int c = c0 + ty * 16 + r, hw = hw0 + tx;
+        if (c < C && hw < HW)
+            dst[(size_t)c * HW + hw] = tile[tx][ty * 16 + r];
+    }
+}
+
+// All levels in one launch, as regroup_multi_kernel with the roles of the two sides exchanged: every thread loads a 4 (pixels) x
+// 4 (channels) block with the channels contiguous (the 16 lanes of a pixel row cover 256 contiguous bytes), transposes it in
+// registers, parks it in LDS ([channel][pixel], padded rows) and the workgroup writes the tile back with the pixels contiguous.
+// RegroupLevel.in is the level's grad_out, RegroupLevel.out its grad_in.
+__global__ __launch_bounds__(256) void regroup_multi_bwd_kernel(const RegroupArgs a)
+{
+    __shared__ float tile[64][68];                       // [channel][pixel], row stride 68 floats (16-byte aligned rows)
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < RG_MAX_LEVELS; ++i)
+        if (i < a.L && (int)blockIdx.x >= a.lv[i].tile0)
+            l = i;
+    const RegroupLevel &lv = a.lv[l];
+    int r = blockIdx.x - lv.tile0;
+    const int thw = r % lv.tiles_hw; r /= lv.tiles_hw;
+    const int tc = r % a.tiles_c;
+    long z = r / a.tiles_c;                              // ((b*T+t)*N+n)*G+g
+    const int g = (int)(z % a.G); z /= a.G;
+    const int n = (int)(z % a.N); z /= a.N;
+    const int t = (int)(z % a.T);
+    const long b = z / a.T;
+    const int HW = lv.HW, C = a.C;
+    const float *src = lv.in + ((((size_t)b * a.T + t) * a.G + g) * a.N + n) * (size_t)HW * C;
+    float *dst = reinterpret_cast<float *>(lv.out) + ((((size_t)b * a.T + t) * a.N + n) * a.G + g) * (size_t)C * HW;
+    const int hw0 = thw * 64, c0 = tc * 64;
+    // load: thread (pq, cq) = 4 pixels x 4 channels; cq fastest over the lanes
+    const int cq = threadIdx.x & 15, pq = threadIdx.x >> 4;
+    rac_f4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int hw = hw0 + 4 * pq + i, c = c0 + 4 * cq;
+        v[i] = (rac_f4){0.f, 0.f, 0.f, 0.f};
+        if (c < C && hw < HW)                            // (C % 4 == 0: a float4 never straddles the end)
+            v[i] = rac_ld4_stream(src + (size_t)hw * C + c);
+    }
+    // 4 x 4 register transpose -> LDS rows = channels
+    *reinterpret_cast<rac_f4 *>(&tile[4 * cq + 0][4 * pq]) = (rac_f4){v[0].x, v[1].x, v[2].x, v[3].x};
+    *reinterpret_cast<rac_f4 *>(&tile[4 * cq + 1][4 * pq]) = (rac_f4){v[0].y, v[1].y, v[2].y, v[3].y};
+    *reinterpret_cast<rac_f4 *>(&tile[4 * cq + 2][4 * pq]) = (rac_f4){v[0].z, v[1].z, v[2].z, v[3].z};
+    *reinterpret_cast<rac_f4 *>(&tile[4 * cq + 3][4 * pq]) = (rac_f4){v[0].w, v[1].w, v[2].w, v[3].w};
+    __syncthreads();
+    // store: thread (channel row k, pixel quad pw); pw fastest over the lanes: 16 lanes write 256 contiguous bytes
+    const int pw = threadIdx.x & 15, k0 = threadIdx.x >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = k0 + 16 * i, c = c0 + k, hw = hw0 + 4 * pw;
+        if (c < C && hw < HW)                            // (HW % 4 == 0)
+            rac_st4_stream(dst + (size_t)c * HW + hw, *reinterpret_cast<const rac_f4 *>(&tile[k][4 * pw]));
+    }
+}
+
+extern "C" int rac_regroup_multi_bwd(int L, const float *const *grad_outs, float *const *grad_ins, const int32_t *hw, int B, int T,
+                                     int N, int G, int C, void *stream)
+{
+    RAC_CHECK_ARG(grad_outs && grad_ins && hw && L >= 1 && L <= RG_MAX_LEVELS, "rac_regroup_multi_bwd: L=%d", L);
+    RAC_CHECK_ARG(B >= 0 && T >= 1 && N >= 1 && G >= 1 && C >= 4 && C % 4 == 0, "rac_regroup_multi_bwd: bad sizes (C %% 4 must be 0)");
+    RegroupArgs a;
+    a.L = L; a.T = T; a.N = N; a.G = G; a.C = C; a.tiles_c = (C + 63) / 64;
+    a.nz = (long)B * T * N * G;
+    if (a.nz == 0)
+        return 0;
+    long total = 0;
+    for (int l = 0; l < L; ++l) {
+        const int HW = hw[2 * l] * hw[2 * l + 1];
+        RAC_CHECK_ARG(grad_outs[l] && grad_ins[l] && HW >= 4 && HW % 4 == 0, "rac_regroup_multi_bwd: level %d (H*W %% 4 must be 0)", l);
+        a.lv[l].in = grad_outs[l]; a.lv[l].out = grad_ins[l]; a.lv[l].HW = HW; a.lv[l].tiles_hw = (HW + 63) / 64;
+        RAC_CHECK_ARG(total < 2147483647L, "rac_regroup_multi_bwd: grid too large");
+        a.lv[l].tile0 = (int)total;
+        total += (long)a.lv[l].tiles_hw * a.tiles_c * a.nz;
+    }
+    RAC_CHECK_ARG(total < 2147483647L, "rac_regroup_multi_bwd: grid too large");
+    for (int l = L; l < RG_MAX_LEVELS; ++l)
+        a.lv[l] = a.lv[0];
+    hipLaunchKernelGGL(regroup_multi_bwd_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, a);
+    return rac_launch_status("rac_regroup_multi_bwd");
+}
+
+extern "C" int rac_regroup_bwd(const float *grad_out, float *grad_in, int B, int T, int N, int G, int C, int H, int W, void *stream)
+{
+    RAC_CHECK_ARG(grad_out && grad_in, "rac_regroup_bwd: null pointer");
+    RAC_CHECK_ARG(B >= 0 && T >= 1 && N >= 1 && G >= 1 && C >= 1 && H >= 1 && W >= 1, "rac_regroup_bwd: bad sizes");
+    const long nz = (long)B * T * N * G;
+    RAC_CHECK_ARG(nz <= 65535, "rac_regroup_bwd: B*T*N*G=%ld exceeds grid.z", nz);
+    if (nz == 0)
+        return 0;
+    const int HW = H * W;
+    dim3 grid((HW + 63) / 64, (C + 63) / 64, (unsigned)nz);
+    hipLaunchKernelGGL(regroup_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, grad_out, grad_in, T, N, G, C, HW);
+    return rac_launch_status("rac_regroup_bwd");
+}

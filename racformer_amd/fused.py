@@ -484,6 +484,72 @@ def refine_fused(proposal, delta, time_diff_safe, num_ray):
     return pred, xy
 
 
+def refine_backward(proposal, delta, time_diff_safe, num_ray, grad_pred=None, grad_xy=None):
+    """Backward of refine_fused in one launch (rac_refine_bwd): (grad_pred, grad_xy) [B,Q,10] each, either may be None (absent: not
+    allocated, not read) -> (grad_delta, grad_proposal) [B,Q,10]."""
+    proposal, delta = proposal.contiguous(), delta.contiguous()
+    grad_pred, grad_xy = (g.contiguous() if g is not None else None for g in (grad_pred, grad_xy))
+    grads = [g for g in (grad_pred, grad_xy) if g is not None]
+    _lib.require_gpu(proposal, delta, time_diff_safe, *grads, what="refine_backward")
+    for g in grads:
+        if g.dtype != torch.float32 or tuple(g.shape) != tuple(proposal.shape):
+            raise RuntimeError("refine_backward: gradients must be float32 tensors shaped like the boxes")
+    B, Q, _ = proposal.shape
+    grad_delta, grad_proposal = torch.empty_like(delta), torch.empty_like(proposal)
+    gp = _lib.ptr(grad_pred) if grad_pred is not None else None
+    gx = _lib.ptr(grad_xy) if grad_xy is not None else None
+    rc = _lib.lib().rac_refine_bwd(_lib.ptr(proposal), _lib.ptr(delta), _lib.ptr(time_diff_safe), gp, gx, _lib.ptr(grad_delta),
+                                   _lib.ptr(grad_proposal), B, Q, time_diff_safe.shape[1], float(num_ray), _lib.stream_ptr())
+    _lib.check(rc, "rac_refine_bwd")
+    return grad_delta, grad_proposal
+
+
+def regroup_fused(feats, dims, groups, out_dtype=torch.float32):
+    """feats[l] contiguous float32 [B,T*N,G*C,H,W] -> [B*T*G,N,H,W,C] of ``out_dtype``, dims = (B, T, N, C): ONE launch over all
+    levels (rac_regroup_multi_fwd); levels whose sizes are not multiples of 4 go through the scalar per-level kernel
+    (rac_regroup_fwd)."""
+    B, T, N, C = dims
+    _lib.require_gpu(*feats, what="regroup_pyramid")
+    outs = [torch.empty(B * T * groups, N, f.shape[3], f.shape[4], C, device=f.device, dtype=out_dtype) for f in feats]
+    code = _lib.RAC_F32 if out_dtype == torch.float32 else _lib.RAC_BF16
+    if C % 4 == 0 and all((f.shape[3] * f.shape[4]) % 4 == 0 for f in feats) and len(feats) <= 8:
+        L = len(feats)
+        ins = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
+        dst = (ctypes.c_void_p * L)(*[o.data_ptr() for o in outs])
+        hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[3:5]])
+        _lib.check(_lib.lib().rac_regroup_multi_fwd(L, ins, dst, hw, B, T, N, groups, C, code, _lib.stream_ptr()), "rac_regroup_multi_fwd")
+        return outs
+    for feat, dst in zip(feats, outs):
+        H, W = feat.shape[3:5]
+        _lib.check(_lib.lib().rac_regroup_fwd(_lib.ptr(feat), _lib.ptr(dst), B, T, N, groups, C, H, W, code, _lib.stream_ptr()),
+                   "rac_regroup_fwd")
+    return outs
+
+
+def regroup_backward(grads, dims, groups):
+    """Backward of regroup_fused, the inverse transposition: grads[l] float32 [B*T*G,N,H,W,C] (the levels that need a gradient
+    only) -> [B,T*N,G*C,H,W], bit-exact, ONE launch (rac_regroup_multi_bwd; rac_regroup_bwd per level for sizes that are not
+    multiples of 4)."""
+    B, T, N, C = dims
+    grads = [g.contiguous() for g in grads]
+    _lib.require_gpu(*grads, what="regroup_backward")
+    for g in grads:
+        if g.dtype != torch.float32 or g.dim() != 5 or (g.shape[0], g.shape[1], g.shape[4]) != (B * T * groups, N, C):
+            raise RuntimeError("regroup_backward: float32 features only, [B*T*G, N, H, W, C]")
+    outs = [torch.empty(B, T * N, groups * C, g.shape[2], g.shape[3], device=g.device, dtype=torch.float32) for g in grads]
+    if C % 4 == 0 and all((g.shape[2] * g.shape[3]) % 4 == 0 for g in grads) and len(grads) <= 8:
+        L = len(grads)
+        src = (ctypes.c_void_p * L)(*[g.data_ptr() for g in grads])
+        dst = (ctypes.c_void_p * L)(*[o.data_ptr() for o in outs])
+        hw = (ctypes.c_int32 * (2 * L))(*[int(x) for g in grads for x in g.shape[2:4]])
+        _lib.check(_lib.lib().rac_regroup_multi_bwd(L, src, dst, hw, B, T, N, groups, C, _lib.stream_ptr()), "rac_regroup_multi_bwd")
+        return outs
+    for g, dst in zip(grads, outs):
+        H, W = g.shape[2:4]
+        _lib.check(_lib.lib().rac_regroup_bwd(_lib.ptr(g), _lib.ptr(dst), B, T, N, groups, C, H, W, _lib.stream_ptr()), "rac_regroup_bwd")
+    return outs
+
+
 SPLIT_ACT_SCALE = 16.0   # power of two applied to activations before the f16 hi/lo split (keeps lo out of f16 subnormals)
 SPLIT_BIAS_PAD = 64      # extra K columns of a split image that carry the bias ([1, 1, 0...] against [b_hi, b_lo, 0...]);
                          # 3*256 + 64 = 832 = 13 x 64 keeps hipBLASLt on its fast kernels (776: 187 us, 832: 134 us)

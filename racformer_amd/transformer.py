@@ -14,6 +14,9 @@ What is different is the execution plan, designed for one MI355X per sample:
   * the pyramid regroup is one HIP transpose kernel (``rac_regroup_fwd``);
   * no host<->device traffic inside the layer loop (the reference uploads ``linspace`` and shape
     tensors every layer, racformer_transformer.py:395,515, bev_self_attention.py:189-190).
+Under autograd (a parameter or an input requires grad) a decoder layer takes its training route, ``forward_train``: the same
+modules through their autograd Functions (a fused HIP forward and a fused HIP backward each) with torch layers between them, so the
+transformer is differentiable end to end; under no_grad every call launches what it always launched.
 There is no CPU fallback: inputs must live on the GPU and the HIP library must be built.
 """
 import math
@@ -31,7 +34,7 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, 
                     generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, outproj_fused,
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
-                    pe_head, refine_fused, row_gemm,
+                    pe_head, refine_backward, refine_fused, regroup_backward, regroup_fused, row_gemm,
                     row_seg, rowgemm_launch, sampling4d_backward, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
 from .msda import msda_backward, msda_forward
 from .msmv import msmv_backward, msmv_forward, msmv_v2_backward, msmv_v2_forward
@@ -433,6 +436,53 @@ class _Sampling4DCore(torch.autograd.Function):
             num_points, depth_num, pc_range, d_region, image_h, image_w, box_table=table, view_in=view_in, want_feats=want_feats)
         gf = [g if n else None for g, n in zip(grad_feats, need[12:])] if want_feats else [None] * len(rest)
         return (grad_off, grad_ray, grad_sc, None, grad_box if need[4] else None, None, None, None, None, None, None, None, *gf)
+
+
+class _RefineCore(torch.autograd.Function):
+    """The refinement tail of a decoder layer: apply(proposal [B,Q,10], delta [B,Q,10], time_diff_safe [B,T], num_ray) ->
+    (bbox_pred, bbox_xy).  The forward is refine_fused as the layer calls it under no_grad; the backward rac_refine_bwd, which
+    recomputes the forward quantities, so only the inputs are saved.  A gradient that is absent (the decoder detaches bbox_pred)
+    is not materialised: the kernel skips it.  The launchers are looked up as this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, proposal, delta, time_diff_safe, num_ray):
+        ctx.set_materialize_grads(False)
+        ctx.num_ray = num_ray
+        ctx.save_for_backward(proposal, delta, time_diff_safe)
+        return refine_fused(proposal, delta, time_diff_safe, num_ray)
+
+    @staticmethod
+    def backward(ctx, grad_pred, grad_xy):
+        if grad_pred is None and grad_xy is None:
+            return None, None, None, None
+        proposal, delta, time_diff_safe = ctx.saved_tensors
+        grad_delta, grad_proposal = refine_backward(proposal, delta, time_diff_safe, ctx.num_ray, grad_pred, grad_xy)
+        need = ctx.needs_input_grad
+        return grad_proposal if need[0] else None, grad_delta if need[1] else None, None, None
+
+
+class _RegroupPyramid(torch.autograd.Function):
+    """The pyramid regroup: apply((B, T, N, C), groups, out_dtype, *feats [B,T*N,G*C,H,W] contiguous float32) -> the levels as
+    [B*T*G,N,H,W,C].  The forward is the launch regroup_pyramid makes under no_grad; the backward ONE launch of the inverse
+    transposition (rac_regroup_multi_bwd) over the levels that need a gradient, bit-exact; the others get None.  bf16 outputs keep
+    this forward and raise at backward time.  The launchers are looked up as this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, dims, groups, out_dtype, *feats):
+        ctx.set_materialize_grads(False)
+        ctx.dims, ctx.groups, ctx.out_dtype = dims, groups, out_dtype
+        return tuple(regroup_fused(list(feats), dims, groups, out_dtype))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if ctx.out_dtype != torch.float32:
+            raise RuntimeError("regroup_pyramid backward: float32 features only")
+        live = [l for l, g in enumerate(grads) if g is not None and ctx.needs_input_grad[3 + l]]
+        out = [None] * len(grads)
+        if live:
+            for l, g in zip(live, regroup_backward([grads[l] for l in live], ctx.dims, ctx.groups)):
+                out[l] = g
+        return (None, None, None, *out)
 
 
 def box_table_torch(query_ray, pc_range):
@@ -1286,10 +1336,39 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         widths = [m.weight.shape[0] for m in mods]
         return w, b, widths
 
+    def records_grad(self, *tensors):
+        """The gate of the training route: autograd is recording and one of ``tensors`` (None entries skipped) or a parameter of
+        the layer requires grad."""
+        return torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors)
+                                            or any(p.requires_grad for p in self.parameters()))
+
+    def prepare_train(self, lss_bev_feats, radar_bev_feats):
+        """prepare() for the training route (forward_train): nothing it hands out cuts a gradient.  The weight-derived operands
+        the route uses are built from the live parameters with autograd history (never taken from, or put into, _pack_cache);
+        both value streams go through the modules' torch branch (value_proj + positional encoding, the radar stream's temporal
+        encoder in torch); the operands only forward_fused reads (split-precision packs, K-slices, the stacked BEV output
+        projections, the cls / reg stem) are not built."""
+        if self.value_storage == "i16":
+            raise RuntimeError("BEVSampling.attend_prepared: an int16 block-stored value stream has no gradient path; "
+                               "prepare the value stream in float32 under autograd")
+        lss_value, lss_hw = self.sampling_lss_bev.prepare_value(lss_bev_feats)
+        # (the library's default convolution algorithms are not reproducible from run to run -- measured: 7e-7 on the temporal encoder's
+        #  output, which every stage downstream of the radar stream then inherits; the training route asks for the deterministic ones
+        #  in the FORWARD.  The convolutions' backwards run later, outside this context, under the caller's own global flag.)
+        with torch.backends.cudnn.flags(enabled=torch.backends.cudnn.enabled, deterministic=True):
+            radar_value, radar_hw = self.sampling_radar_bev.prepare_value(radar_bev_feats, None)
+        w, b, widths = self._wide_linears()
+        return dict(radar_value=radar_value, radar_hw=radar_hw, lss_value=lss_value, lss_hw=lss_hw, value_scales=None,
+                    wide_w=w, wide_b=b, wide_widths=widths, wide_img=(None, None), out_proj_split=self.mixing.split_out_proj(),
+                    split_packs={}, sasa_w=self.self_attn.wide_in_proj(), train=True)
+
     def prepare(self, lss_bev_feats, radar_bev_feats):
-        """Layer-invariant tensors (computed once per forward)."""
+        """Layer-invariant tensors (computed once per forward).  When autograd is recording and a BEV stack or a parameter requires
+        grad: the training route's operands (prepare_train; a caller that knows of other inputs requiring grad calls that itself)."""
         if self.value_storage not in ("f32", "i16"):
             raise RuntimeError(f"value_storage must be 'f32' or 'i16', got {self.value_storage!r}")
+        if self.records_grad(lss_bev_feats, radar_bev_feats):
+            return self.prepare_train(lss_bev_feats, radar_bev_feats)
         # "i16": the two producers of the value streams quantise in their epilogues where they are the hand-written kernels
         # (rac_conv3x3_q16_fwd, rac_value_proj_q16_fwd); a stream that arrives as fp32 anyway goes through rac_quant_i16_fwd below
         # ("i16" is a preference: shapes the int16 BEV kernel is not built for -- streams of different geometry, heads of other than
@@ -1511,20 +1590,43 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         self.last_bbox_xy = bbox_xy
         return x3, cls_score, bbox_pred
 
+    def fused_plan_applies(self, query_feat, attn_mask):
+        """shapes the one-launch-per-stage plan (forward_fused) is built for"""
+        return attn_mask is None and query_feat.is_cuda and self.embed_dims == 256 and self.mixing.in_points <= 96
+
     def forward(self, query_bbox, query_feat, mlvl_feats, lss_bev_feats, radar_bev_feats, attn_mask, img_metas,
-                layer=0, prepared=None, stages=None, out_slots=None):
+                layer=0, prepared=None, stages=None, out_slots=None, train=None):
         """``out_slots``: optional (cls_score [B,Q,classes], bbox_xy [B,Q,code]) destinations -- slices of the decoder's stacked
-        outputs -- that the fused plan writes directly (no torch.stack afterwards)."""
-        if prepared is None:
-            prepared = self.prepare(lss_bev_feats, radar_bev_feats)
+        outputs -- that the fused plan writes directly (no torch.stack afterwards).  ``train``: the verdict of records_grad over
+        this call's inputs if the caller has it already (the decoder judges once for its six calls); None: judged here."""
+        if train is None:
+            train = self.records_grad(query_feat, query_bbox, lss_bev_feats, radar_bev_feats, *mlvl_feats)
+        if prepared is None or (train and not prepared.get("train")):
+            prepared = self.prepare_train(lss_bev_feats, radar_bev_feats) if train else self.prepare(lss_bev_feats, radar_bev_feats)
+        if train:
+            # autograd is recording and an input or a parameter requires grad: forward_fused (raw launches, no autograd history) and
+            # the alternate plans are skipped
+            return self.forward_train(query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, layer, prepared, stages)
         if not self.fused:
             # the reference's op decomposition (torch keypoint chains + the msmv / MSDA operators + torch layers): a cross-check plan
             # of the parity tests, which register it (tests/plans.py) -- not product code
             return alternate_plan("reference_ops")(self, query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, layer, prepared, stages)
-        if attn_mask is None and query_feat.is_cuda and self.embed_dims == 256 and self.mixing.in_points <= 96:
+        if self.fused_plan_applies(query_feat, attn_mask):
             return self.forward_fused(query_bbox, query_feat, mlvl_feats, img_metas, layer, prepared, stages, out_slots)
         # shapes the one-launch-per-stage plan is not built for (another embedding width, an attention mask, more than 96 sampling
         # points): the fused gather kernels with torch layers around them
+        return self.forward_train(query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, layer, prepared, stages)
+
+    def forward_train(self, query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, layer, prepared, stages=None):
+        """The layer as a composition of its modules with torch layers around them (racformer_transformer.py:239-279): the
+        training route.  Every heavy module takes its own autograd Function where a gradient is wanted -- _SASACore,
+        _BEVSamplingCore (forward_unfused for B > 1), _Sampling4DCore, _MixingCore, _RefineCore, each a fused HIP forward with a
+        fused HIP backward --, the eleven 256 -> . Linears are ONE F.linear over the wide operand (concatenated from the live
+        parameters by prepare_train, so each of the eleven weights and biases receives its gradient), the norms, fusion, FFN
+        and the cls / reg branches are torch modules.  One rac_box_prep_fwd table serves the three sampling modules; where
+        query_bbox requires grad they build their own box_table_torch graph beside it.  Neither reads nor writes _carry and
+        does not write output slots (wrote_slots stays False: the decoder stacks).  Without autograd the same composition
+        serves the shapes forward_fused is not built for."""
         meta = img_metas[0]
         time_diff, d_region = meta["time_diff"], self.d_region_list[layer]
         query_pos = self.position_encoder(query_bbox[..., :3])
@@ -1547,7 +1649,11 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         ffn_out = self.ffn(query_feat)
         query_feat = self.norm3(ffn_out)
         cls_score = self.cls_branch(query_feat)
-        bbox_pred, bbox_xy = refine_fused(query_bbox, self.reg_branch(query_feat), meta["time_diff_safe"], self.num_ray)
+        delta = self.reg_branch(query_feat)
+        if torch.is_grad_enabled() and (query_bbox.requires_grad or delta.requires_grad):
+            bbox_pred, bbox_xy = _RefineCore.apply(query_bbox.contiguous(), delta.contiguous(), meta["time_diff_safe"], self.num_ray)
+        else:
+            bbox_pred, bbox_xy = refine_fused(query_bbox, delta, meta["time_diff_safe"], self.num_ray)
         if stages is not None:
             stages.update(position_encoder=query_pos, self_attn=sa, sampling_radar_bev=radar_raw,
                           sampling_lss_bev=lss_raw, sampling=sampled_feat, mixing=mixed, ffn=ffn_out)
@@ -1558,9 +1664,10 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
 def regroup_pyramid(mlvl_feats, num_cams, groups=4, out_dtype=torch.float32):
     """racformer_transformer.py:112-124 as ONE HIP transpose launch over all levels:
     [B,T*N,G*C,H,W] -> [B*T*G, N, H, W, C]  (rac_regroup_multi_fwd; levels whose sizes are not multiples of 4 go through
-    the scalar per-level kernel rac_regroup_fwd)."""
-    import ctypes
-    feats, outs, dims = [], [], None
+    the scalar per-level kernel rac_regroup_fwd).  When autograd is recording and a level requires grad: the same launch through
+    _RegroupPyramid, with the inverse transposition (rac_regroup_multi_bwd) behind it; the cast / compaction of a half-precision
+    or non-contiguous level stays a torch op, so its producer still gets its gradient."""
+    feats, dims = [], None
     for feat in mlvl_feats:
         B, TN, GC, H, W = feat.shape
         if TN % num_cams != 0 or GC % groups != 0:
@@ -1570,26 +1677,12 @@ def regroup_pyramid(mlvl_feats, num_cams, groups=4, out_dtype=torch.float32):
             dims = (B, T, N, C)
         elif dims != (B, T, N, C):
             raise RuntimeError("regroup_pyramid: levels must share B, T*N and G*C")
-        feat = feat.float().contiguous()
-        _lib.require_gpu(feat, what="regroup_pyramid")
-        feats.append(feat)
-        outs.append(torch.empty(B * T * groups, N, H, W, C, device=feat.device, dtype=out_dtype))
+        feats.append(feat.float().contiguous())
     if not feats:
         return []
-    B, T, N, C = dims
-    code = _lib.RAC_F32 if out_dtype == torch.float32 else _lib.RAC_BF16
-    if C % 4 == 0 and all((f.shape[3] * f.shape[4]) % 4 == 0 for f in feats) and len(feats) <= 8:
-        L = len(feats)
-        ins = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-        dst = (ctypes.c_void_p * L)(*[o.data_ptr() for o in outs])
-        hw = (ctypes.c_int32 * (2 * L))(*[int(x) for f in feats for x in f.shape[3:5]])
-        _lib.check(_lib.lib().rac_regroup_multi_fwd(L, ins, dst, hw, B, T, N, groups, C, code, _lib.stream_ptr()), "rac_regroup_multi_fwd")
-        return outs
-    for feat, dst in zip(feats, outs):
-        H, W = feat.shape[3:5]
-        _lib.check(_lib.lib().rac_regroup_fwd(_lib.ptr(feat), _lib.ptr(dst), B, T, N, groups, C, H, W, code, _lib.stream_ptr()),
-                   "rac_regroup_fwd")
-    return outs
+    if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
+        return list(_RegroupPyramid.apply(dims, groups, out_dtype, *feats))
+    return regroup_fused(feats, dims, groups, out_dtype)
 
 
 class RaCFormerTransformerDecoder(nn.Module):
@@ -1667,14 +1760,16 @@ class RaCFormerTransformerDecoder(nn.Module):
             grouped = regroup_pyramid(mlvl_feats, self.num_cams, 4, self.feature_dtype)
             for lvl, g in enumerate(grouped):
                 mlvl_feats[lvl] = g  # the reference mutates the caller's list too (:124)
-        prepared = self.decoder_layer.prepare(lss_bev_feats, radar_bev_feats)
+        dl = self.decoder_layer
+        # (the gate of the training route is judged over ALL inputs of the layer here; prepare() alone sees the BEV stacks only)
+        train = dl.records_grad(query_feat, query_bbox, lss_bev_feats, radar_bev_feats, *mlvl_feats)
+        prepared = dl.prepare_train(lss_bev_feats, radar_bev_feats) if train else dl.prepare(lss_bev_feats, radar_bev_feats)
         self.decoder_layer._carry = None
         cls_scores, bbox_preds = [], []
         # the stacked outputs are allocated up front and every layer of the fused plan writes its slice (no torch.stack launches)
         stacked = None
         if query_feat.is_cuda and not torch.is_grad_enabled():
             B, Q = query_bbox.shape[:2]
-            dl = self.decoder_layer
             stacked = (torch.empty(self.num_layers, B, Q, dl.num_classes, device=query_feat.device, dtype=torch.float32),
                        torch.empty(self.num_layers, B, Q, dl.code_size, device=query_feat.device, dtype=torch.float32))
         for i in range(self.num_layers):
@@ -1682,7 +1777,7 @@ class RaCFormerTransformerDecoder(nn.Module):
             self.decoder_layer.wrote_slots = False
             query_feat, cls_score, bbox_pred = self.decoder_layer(
                 query_bbox, query_feat, mlvl_feats, lss_bev_feats, radar_bev_feats, attn_mask, img_metas,
-                layer=i, prepared=prepared, stages=st, out_slots=(stacked[0][i], stacked[1][i]) if stacked is not None else None)
+                layer=i, prepared=prepared, stages=st, out_slots=(stacked[0][i], stacked[1][i]) if stacked is not None else None, train=train)
             if stacked is not None and not self.decoder_layer.wrote_slots:
                 stacked = None                      # (a plan that does not write in place: fall back to stacking)
             if stages_per_layer is not None:

@@ -38,6 +38,8 @@
  *                        models/racformer_transformer.py:296-335
  *   rac_sasa_fwd_ex / rac_sasa_bwd <- the same forward saving each row's log-sum-exp, and its backward (autograd of the
  *                        reference's float-mask nn.MultiheadAttention in q, k, v and tau; the distances are no_grad there)
+ *   rac_sasa_fwd_mask / rac_sasa_bwd_mask <- the same pair with the boolean [Q,Q] attn_mask of query denoising
+ *                        (models/racformer_head.py:220-232, models/racformer_transformer.py:311-312), bit-packed
  *   rac_decode_fwd    <- NMSFreeCoder.decode_single + get_bboxes, models/bbox/coders/nms_free_coder.py:37-88,
  *                        models/racformer_head.py:488-507
  *   rac_outproj_fwd / rac_gemm_split_pack_fwd <- AdaptiveMixing.out_proj (nn.Linear 32768 -> 256), models/racformer_transformer.py:566,606
@@ -64,7 +66,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 16
+#define RAC_ABI_VERSION 17
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -307,6 +309,28 @@ int rac_sasa_fwd_ex(const float *qkv, const float *tau, const float *query_bbox,
 int rac_sasa_bwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table, const float *out,
                  const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau, int ld_qkv, int ld_tau,
                  int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream);
+
+/* rac_sasa_fwd_ex / rac_sasa_bwd under a boolean attention mask shared by all batches and heads (the reference's
+ * pre_attn_mask: mask[:, :, attn_mask] = -inf, models/racformer_transformer.py:311-312).  All other arguments as above.
+ *   mask_bits : device uint32 words [Q][ld_mask], ld_mask >= ceil(Q/32): bit (j & 31) of word [i][j >> 5] set = query i
+ *               does not attend to key j.  Bits at j >= Q are ignored.
+ * A blocked pair has logit -inf: probability exactly 0 and exactly 0 in dq, dk, dv and dtau; lse is over the allowed keys.
+ * Forward: Q <= 1024 the register-resident matrix-core kernel of rac_sasa_fwd_ex (with an all-zero mask, out and lse are
+ * bit-identical to it); larger Q (up to 6144) a streaming matrix-core kernel with online softmax -- box_table is honoured at
+ * every Q.  Backward: the two-role kernel of rac_sasa_bwd with the mask in both roles, one writer per element, no atomics
+ * (bit-reproducible; with an all-zero mask bit-identical to rac_sasa_bwd where the two read the same centres).  A 16 x 16 tile
+ * without an allowed pair is skipped whole (no loads, no MFMAs); the results do not depend on that.  Nothing of size Q x Q
+ * beyond the Q*ld_mask mask words is read or written.
+ * A query row with every key blocked has no softmax: its out row and the gradients it would contribute to are unspecified
+ * (NaN where the tile is computed) and its lse is -inf or NaN.  The query-denoising layout has no such row. */
+int rac_sasa_fwd_mask(const float *qkv, const float *tau, const float *query_bbox, const float *box_table, float *out,
+                      float *lse, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream,
+                      const uint32_t *mask_bits, int ld_mask);
+
+int rac_sasa_bwd_mask(const float *qkv, const float *tau, const float *query_bbox, const float *box_table, const float *out,
+                      const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau, int ld_qkv, int ld_tau,
+                      int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream,
+                      const uint32_t *mask_bits, int ld_mask);
 
 /* Layouts of the f16 hi / lo activation images that rac_add_ln_fwd and rac_rowgemm_fwd can emit beside their fp32 rows */
 enum {

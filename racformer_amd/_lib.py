@@ -50,6 +50,8 @@ SIGNATURES = {
     "rac_sasa_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp, _vp]),
     "rac_sasa_fwd_ex": (_i, [_vp] * 6 + [_i] * 6 + [_vp, _vp]),
     "rac_sasa_bwd": (_i, [_vp] * 9 + [_i] * 8 + [_vp, _vp]),
+    "rac_sasa_fwd_mask": (_i, [_vp] * 6 + [_i] * 6 + [_vp, _vp, _vp, _i]),
+    "rac_sasa_bwd_mask": (_i, [_vp] * 9 + [_i] * 8 + [_vp, _vp, _vp, _i]),
     "rac_decode_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _f, _i, _vp]),
     "rac_rowgemm_fwd": (_i, [_vp, _i, _i, _vp]),
     "rac_gemm_split_pack_fwd": (_i, [_vp, _vp, _i, _i, _f, _vp]),

@@ -46,6 +46,20 @@ def denormalize_bbox(normalized_bboxes):
     return torch.cat(parts, dim=-1)
 
 
+def encode_bbox(bboxes, pc_range=None):
+    """bbox/utils.py:49-63, the inverse of decode_bbox: [x, y, z, w, l, h, yaw, (vx, vy)] in metres -> [x, y, z (normalised to
+    pc_range), log w, log l, log h, sin, cos, (vx, vy)].  The centre is normalised per component as (v - lo) / span with the
+    spans formed on the host, which is the reference's arithmetic bit for bit."""
+    xyz = bboxes[..., 0:3]
+    if pc_range is not None:
+        xyz = torch.stack([(xyz[..., i] - pc_range[i]) / (pc_range[i + 3] - pc_range[i]) for i in range(3)], dim=-1)
+    rot = bboxes[..., 6:7]
+    parts = [xyz, bboxes[..., 3:6].log(), rot.sin(), rot.cos()]
+    if bboxes.shape[-1] > 7:
+        parts.append(bboxes[..., 7:9])
+    return torch.cat(parts, dim=-1)
+
+
 def theta_d2xy_coods(theta_d_coords, map_size=102.4, r=65.0):
     """bbox/utils.py:82-90: polar -> normalised xy, clamped to [0,1]; other dims pass through."""
     center = map_size / 2

@@ -7,6 +7,9 @@
 //   out[b,i,h*d:(h+1)*d] = softmax_j(logits) @ v
 // with c = box centres in metres (decode_bbox(theta_d2xy(query_bbox))[:2], :301-302,:325).
 // in_proj / out_proj stay library GEMMs outside.
+// Under the boolean [Q,Q] attn_mask of query denoising (:311-312; rac_sasa_fwd_mask / rac_sasa_bwd_mask) the mask comes in as
+// bits, 32 keys to a word, shared by all batches and heads: the masked instantiations of the matrix-core kernels below (a
+// template parameter; the unmasked instantiations are the kernels they were) and, for Q > 1024, a streaming matrix-core forward.
 //
 // Mapping: a workgroup = 16 query rows of one (batch, head); a 16-lane group owns a row.  K/V are
 // streamed through LDS in 64-key tiles (next tile prefetched into registers while the current one
@@ -31,6 +34,8 @@ struct SasaArgs {
     float pc[6];
     int B, Q, H, ld_tau, ld_qkv;
     int row_blocks;
+    const unsigned *mask;  // masked instantiations only: [Q][ld_mask] words, bit j&31 of word [i][j>>5] set = query i does not see key j
+    int ld_mask;
 };
 
 #define SASA_TILE 64   /* keys per LDS tile */
@@ -211,6 +216,33 @@ __device__ __forceinline__ void sasa_centres(float *scen, const float *box, cons
     }
 }
 
+// The attention mask (rac_sasa_fwd_mask / rac_sasa_bwd_mask).  A 16-key tile never straddles a 32-bit word, so what a lane needs
+// of one mask row for one tile is a 16-bit field: bit k set = key tile*16 + k is blocked for that row.  The keys past Q are
+// returned as blocked too (the padding bits of the operand are ignored), so a field of 0xffff means "no allowed key in this
+// tile" and a tile whose 16 rows all say so is skipped by the whole wave: the decision comes from the mask words alone.
+// SASA_NO_TILE_SKIP (an A/B build switch): every tile is computed; the results are the same bit for bit, a blocked pair
+// contributes an exact zero either way.
+#ifdef SASA_NO_TILE_SKIP
+#define SASA_TILE_SKIP 0
+#else
+#define SASA_TILE_SKIP 1
+#endif
+
+__device__ __forceinline__ unsigned sasa_mask_field(const unsigned *mask, int ld_mask, int row, int tile, int Q)
+{
+    const unsigned w = mask[(size_t)row * ld_mask + (tile >> 1)];
+    const int nv = Q - tile * 16;   // keys of the tile that exist (>= 1)
+    const unsigned pad = nv >= 16 ? 0u : (0xffffu << nv) & 0xffffu;
+    return ((w >> ((tile & 1) * 16)) & 0xffffu) | pad;
+}
+
+// wave-uniform: no lane of the wave has an allowed pair in its field(s)
+__device__ __forceinline__ bool sasa_all_blocked(unsigned field)
+{
+    return SASA_TILE_SKIP && __builtin_amdgcn_ballot_w64(field != 0xffffu) == 0;
+}
+
+template <bool MASKED>
 __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
 {
     extern __shared__ float smem[];
@@ -255,16 +287,31 @@ __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
         k0 = rac_ld4(kp);
         k1 = rac_ld4(kp + 16);
     };
+    // masked: this lane's 16-bit field of every tile of the wave (two to a register) and, wave-uniform, the tiles that are left
+    // out: past the end, or without an allowed pair -- those load no K / V rows and issue no MFMAs
+    unsigned mfield[MASKED ? SASA_NT / 2 : 1] = {};
+    unsigned skip = 0;
+    if constexpr (MASKED) {
+#pragma unroll
+        for (int jt = 0; jt < SASA_NT; ++jt) {
+            const int tile = wave + 4 * jt;
+            const unsigned f = tile < ntiles ? sasa_mask_field(a.mask, a.ld_mask, qc, tile, Q) : 0xffffu;
+            mfield[jt >> 1] |= f << ((jt & 1) * 16);
+            if (tile >= ntiles || sasa_all_blocked(f))
+                skip |= 1u << jt;
+        }
+    }
     rac_f4 kb[2][2];
-    load_k(0, kb[0][0], kb[0][1]);
+    if (!MASKED || !(skip & 1u))
+        load_k(0, kb[0][0], kb[0][1]);
 #pragma unroll
     for (int jt = 0; jt < SASA_NT; ++jt) {
         const int tile = wave + 4 * jt;
         sc[jt] = (sasa_f4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        if (jt + 1 < SASA_NT)
+        if (jt + 1 < SASA_NT && (!MASKED || !((skip >> (jt + 1)) & 1u)))
             load_k(jt + 1, kb[(jt + 1) & 1][0], kb[(jt + 1) & 1][1]);     // (clamped to a valid row past the end)
         __builtin_amdgcn_sched_barrier(0);
-        if (tile < ntiles) {
+        if (MASKED ? !((skip >> jt) & 1u) : tile < ntiles) {
             const rac_f4 k0 = kb[jt & 1][0], k1 = kb[jt & 1][1];
             sasa_f4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0.x, qb4[0].x, acc, 0, 0, 0);
@@ -279,7 +326,10 @@ __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int kk = tile * 16 + 4 * lk + r;
-                if (kk < Q) {
+                bool allowed = kk < Q;
+                if constexpr (MASKED)   // (the field has the keys past Q set)
+                    allowed = !((mfield[jt >> 1] >> ((jt & 1) * 16 + 4 * lk + r)) & 1u);
+                if (allowed) {
                     const float dx = cqx - scen[2 * kk], dy = cqy - scen[2 * kk + 1];
                     const float v = acc[r] - sqrtf(dx * dx + dy * dy) * tau;
                     sc[jt][r] = v;
@@ -323,14 +373,15 @@ __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
         }
     };
     float vb[2][2][4];
-    load_v(0, vb[0]);
+    if (!MASKED || !(skip & 1u))
+        load_v(0, vb[0]);
 #pragma unroll
     for (int jt = 0; jt < SASA_NT; ++jt) {
         const int tile = wave + 4 * jt;
-        if (jt + 1 < SASA_NT)
+        if (jt + 1 < SASA_NT && (!MASKED || !((skip >> (jt + 1)) & 1u)))
             load_v(jt + 1, vb[(jt + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
-        if (tile < ntiles) {
+        if (MASKED ? !((skip >> jt) & 1u) : tile < ntiles) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 oacc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vb[jt & 1][0][i], sc[jt][i], oacc[0], 0, 0, 0);
@@ -366,32 +417,60 @@ __global__ __launch_bounds__(256) void sasa_mfma_kernel(const SasaArgs a)
     }
 }
 
-extern "C" int rac_sasa_fwd_ex(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
-                               float *out, float *lse, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim,
-                               const float *pc_range, void *stream)
+__global__ __launch_bounds__(256) void sasa_stream_mask_kernel(const SasaArgs a);   // (below, beside the backward whose helpers it shares)
+
+// the argument checks and the launch of rac_sasa_fwd_ex (masked = false) and rac_sasa_fwd_mask
+static int sasa_fwd_launch(const char *fn, bool masked, const float *qkv, const float *tau, const float *query_bbox,
+                           const float *box_table, float *out, float *lse, const uint32_t *mask_bits, int ld_mask, int ld_qkv,
+                           int ld_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream)
 {
-    RAC_CHECK_ARG(dim == SASA_D, "rac_sasa_fwd_ex: head dim %d (the kernel is built for %d)", dim, SASA_D);
-    RAC_CHECK_ARG(B >= 0 && Q >= 0 && heads >= 1 && ld_tau >= heads && ld_qkv >= 3 * heads * dim && ld_qkv % 4 == 0, "rac_sasa_fwd_ex: bad sizes B=%d Q=%d heads=%d", B, Q, heads);
-    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "rac_sasa_fwd_ex: Q=%d too large for the LDS centre table", Q);
+    RAC_CHECK_ARG(dim == SASA_D, "%s: head dim %d (the kernel is built for %d)", fn, dim, SASA_D);
+    RAC_CHECK_ARG(B >= 0 && Q >= 0 && heads >= 1 && ld_tau >= heads && ld_qkv >= 3 * heads * dim && ld_qkv % 4 == 0, "%s: bad sizes B=%d Q=%d heads=%d", fn, B, Q, heads);
+    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "%s: Q=%d too large for the LDS centre table", fn, Q);
+    RAC_CHECK_ARG(!masked || ld_mask >= (Q + 31) / 32, "%s: ld_mask=%d shorter than the %d words of a mask row (Q=%d)", fn, ld_mask, (Q + 31) / 32, Q);
     if (B == 0 || Q == 0)
         return 0;
-    RAC_CHECK_ARG(qkv && tau && query_bbox && out && pc_range, "rac_sasa_fwd_ex: null pointer");
+    RAC_CHECK_ARG(qkv && tau && query_bbox && out && pc_range, "%s: null pointer", fn);
+    RAC_CHECK_ARG(!masked || mask_bits, "%s: null pointer (mask_bits)", fn);
     SasaArgs a;
     a.qkv = qkv; a.tau = tau; a.qbox = query_bbox; a.box = box_table; a.out = out; a.lse = lse;
     for (int i = 0; i < 6; ++i)
         a.pc[i] = pc_range[i];
     a.B = B; a.Q = Q; a.H = heads; a.ld_tau = ld_tau; a.ld_qkv = ld_qkv;
     a.row_blocks = (Q + SASA_ROWS - 1) / SASA_ROWS;
+    a.mask = masked ? mask_bits : nullptr; a.ld_mask = masked ? ld_mask : 0;
     const int nb = B * heads * a.row_blocks;
     const size_t cen = (size_t)2 * ((Q + 1) & ~1);
-    if (Q <= 4 * SASA_NT * 16) {
-        const size_t lds = (cen + 2 * 4 * 16 + 4 * 32 * 16) * sizeof(float);
-        hipLaunchKernelGGL(sasa_mfma_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
+    const size_t lds_mfma = (cen + 2 * 4 * 16 + 4 * 32 * 16) * sizeof(float);
+    if (masked) {
+        // register-resident up to Q = 1024 (with an all-zero mask: rac_sasa_fwd_ex bit for bit), the streaming kernel above
+        if (Q <= 4 * SASA_NT * 16)
+            hipLaunchKernelGGL(sasa_mfma_kernel<true>, dim3(nb), dim3(256), lds_mfma, (hipStream_t)stream, a);
+        else
+            hipLaunchKernelGGL(sasa_stream_mask_kernel, dim3(nb), dim3(256), lds_mfma, (hipStream_t)stream, a);
+    } else if (Q <= 4 * SASA_NT * 16) {
+        hipLaunchKernelGGL(sasa_mfma_kernel<false>, dim3(nb), dim3(256), lds_mfma, (hipStream_t)stream, a);
     } else {
         const size_t lds = (cen + 2 * SASA_TILE * SASA_KS) * sizeof(float);
         hipLaunchKernelGGL(sasa_d32_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
     }
-    return rac_launch_status("rac_sasa_fwd_ex");
+    return rac_launch_status(fn);
+}
+
+extern "C" int rac_sasa_fwd_ex(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                               float *out, float *lse, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim,
+                               const float *pc_range, void *stream)
+{
+    return sasa_fwd_launch("rac_sasa_fwd_ex", false, qkv, tau, query_bbox, box_table, out, lse, nullptr, 0, ld_qkv, ld_tau, B, Q,
+                           heads, dim, pc_range, stream);
+}
+
+extern "C" int rac_sasa_fwd_mask(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                                 float *out, float *lse, int ld_qkv, int ld_tau, int B, int Q, int heads, int dim,
+                                 const float *pc_range, void *stream, const uint32_t *mask_bits, int ld_mask)
+{
+    return sasa_fwd_launch("rac_sasa_fwd_mask", true, qkv, tau, query_bbox, box_table, out, lse, mask_bits, ld_mask, ld_qkv,
+                           ld_tau, B, Q, heads, dim, pc_range, stream);
 }
 
 extern "C" int rac_sasa_fwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
@@ -422,6 +501,8 @@ struct SasaBwdArgs {
     float pc[6];
     int B, Q, H, ld_qkv, ld_tau, ld_gqkv, ld_gtau;
     int row_blocks;
+    const unsigned *mask;  // masked instantiation only, as in SasaArgs
+    int ld_mask;
 };
 
 #define SASA_MFMA8(acc, a4, b4)                                                       \
@@ -475,6 +556,131 @@ __device__ __forceinline__ float2 sasa_combine(float *so, const sasa_f4 (&acc)[2
     return make_float2(o0, o1);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Masked forward for Q > 1024 (rac_sasa_fwd_mask): the matrix-core forward as a stream over the key tiles, like the backward's
+// row role -- one tile in flight per wave, nothing kept per tile, so every Q the centre table admits runs here.  Online softmax:
+// a wave carries, per query column, the running max m and sum l of the tiles it has seen and the O^T accumulator scaled to m; a
+// tile whose max raises m rescales l and the accumulator (eight multiplies a lane: the accumulator's query is the lane's own
+// column li, so the factor needs no exchange).  The tile max goes over the four lk groups with two DPP steps.  One pass over K
+// and V and 16 MFMAs a tile; the two-pass alternative (statistics first, then P V against the final max) forms every S tile
+// twice -- 24 MFMAs and the K rows read twice -- to save the rescale, which is the cheaper of the two here.  The four waves'
+// states are merged through LDS in a fixed order (log-sum-exp of the four maxima).  A tile without an allowed pair is skipped by
+// the whole wave before any of its loads.  A query's result depends on its own allowed keys only: blocked pairs enter as exact zeros.
+__global__ __launch_bounds__(256) void sasa_stream_mask_kernel(const SasaArgs a)
+{
+    extern __shared__ float smem[];
+    float *scen = smem;                         // [Q][2] key centres (metres)
+    float *sred = smem + 2 * ((a.Q + 1) & ~1);  // [4 waves][16] max, then [4][16] sum
+    float *so = sred + 2 * 4 * 16;              // [4 waves][32 ch][16 queries]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    int bid = blockIdx.x;
+    const int rb = bid % a.row_blocks; bid /= a.row_blocks;
+    const int h = bid % a.H;
+    const int b = bid / a.H;
+    const int Q = a.Q, H = a.H;
+    const size_t tok = (size_t)b * Q;
+    const int ld = a.ld_qkv;
+    const float scale = 0.17677669529663687f;
+
+    sasa_centres(scen, a.box, a.qbox, a.pc, b, Q);
+    const int qi = rb * SASA_ROWS + li;
+    const int qc = qi < Q ? qi : Q - 1;
+    rac_f4 qs[2];
+    sasa_row8(qs, a.qkv + (tok + qc) * ld + h * SASA_D, lk, scale);
+    const float tau = a.tau[(tok + qc) * a.ld_tau + h];
+    __syncthreads();
+    const float cqx = scen[2 * qc], cqy = scen[2 * qc + 1];
+
+    const int ntiles = (Q + 15) >> 4;
+    float m = -INFINITY, l = 0.f;   // m: the same in the four lanes of a query column; l: this lane's share of the sum
+    sasa_f4 oacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    for (int tile = wave; tile < ntiles; tile += 4) {
+        const unsigned field = sasa_mask_field(a.mask, a.ld_mask, qc, tile, Q);
+        if (sasa_all_blocked(field))
+            continue;
+        const int k0 = tile * 16;
+        const int kr = k0 + li < Q ? k0 + li : Q - 1;
+        rac_f4 kA[2];
+        sasa_row8(kA, a.qkv + (tok + kr) * ld + (H + h) * SASA_D, lk, 1.f);
+        // V^T operand of O^T: V[key k0 + 4lk + i][channel li (+16)]
+        float vt[2][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int key = k0 + 4 * lk + i;
+            const float *vp = a.qkv + (tok + (key < Q ? key : Q - 1)) * ld + (2 * H + h) * SASA_D;
+            vt[0][i] = vp[li];
+            vt[1][i] = vp[16 + li];
+        }
+        sasa_f4 s = {0.f, 0.f, 0.f, 0.f};
+        SASA_MFMA8(s, kA, qs);     // s[r] = S^T[key k0 + 4lk + r][query li]
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int kk = k0 + 4 * lk + r;
+            const int kc = kk < Q ? kk : Q - 1;
+            const float dx = cqx - scen[2 * kc], dy = cqy - scen[2 * kc + 1];
+            const float v = s[r] - sqrtf(dx * dx + dy * dy) * tau;
+            s[r] = ((field >> (4 * lk + r)) & 1u) ? -INFINITY : v;
+            tmax = fmaxf(tmax, s[r]);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        const float mn = fmaxf(m, tmax);   // (-inf only while the column has met no allowed key: then m is -inf too)
+        const float corr = (m == -INFINITY) ? 0.f : expf(m - mn);
+        l *= corr;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                oacc[c][r] *= corr;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[r] = (s[r] == -INFINITY) ? 0.f : expf(s[r] - mn);
+            l += s[r];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            oacc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[0][i], s[i], oacc[0], 0, 0, 0);
+            oacc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[1][i], s[i], oacc[1], 0, 0, 0);
+        }
+        m = mn;
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (lk == 0) {
+        sred[wave * 16 + li] = m;
+        sred[64 + wave * 16 + li] = l;
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            so[(wave * 32 + 16 * c + 4 * lk + r) * 16 + li] = oacc[c][r];
+    __syncthreads();
+    {
+        const int qq = tid >> 4, cp = (tid & 15) * 2;   // query within the tile, channel pair
+        const int qrow = rb * SASA_ROWS + qq;
+        if (qrow < Q) {
+            const float mm = fmaxf(fmaxf(sred[qq], sred[16 + qq]), fmaxf(sred[32 + qq], sred[48 + qq]));
+            float lsum = 0.f, o0 = 0.f, o1 = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const float mw = sred[w * 16 + qq];
+                const float f = (mw == -INFINITY) ? 0.f : expf(mw - mm);
+                lsum += sred[64 + w * 16 + qq] * f;
+                o0 += so[(w * 32 + cp) * 16 + qq] * f;
+                o1 += so[(w * 32 + cp + 1) * 16 + qq] * f;
+            }
+            *reinterpret_cast<float2 *>(a.out + (tok + qrow) * (size_t)(H * SASA_D) + h * SASA_D + cp) =
+                make_float2(o0 / lsum, o1 / lsum);
+            if (a.lse && cp == 0)
+                a.lse[((size_t)b * H + h) * Q + qrow] = mm + logf(lsum);
+        }
+    }
+}
+
+template <bool MASKED>
 __global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
 {
     extern __shared__ float smem[];
@@ -515,6 +721,12 @@ __global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
         sasa_f4 dq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         float dtau = 0.f;
         for (int tile = wave; tile < ntiles; tile += 4) {
+            unsigned field = 0;   // masked: this query's blocked keys of the tile (the keys past Q included)
+            if constexpr (MASKED) {
+                field = sasa_mask_field(a.mask, a.ld_mask, oc, tile, Q);
+                if (sasa_all_blocked(field))
+                    continue;
+            }
             const int k0 = tile * 16;
             const int kr = k0 + li < Q ? k0 + li : Q - 1;
             rac_f4 kA[2], vA[2];
@@ -539,7 +751,10 @@ __global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
                 const int kc = key < Q ? key : Q - 1;
                 const float dx = cqx - scen[2 * kc], dy = cqy - scen[2 * kc + 1];
                 const float dist = sqrtf(dx * dx + dy * dy);
-                const float p = key < Q ? expf(s[r] - dist * tau - lse_i) : 0.f;
+                bool allowed = key < Q;
+                if constexpr (MASKED)
+                    allowed = !((field >> (4 * lk + r)) & 1u);
+                const float p = allowed ? expf(s[r] - dist * tau - lse_i) : 0.f;
                 ds[r] = p * (dp[r] - Di);
                 dtau -= ds[r] * dist;
             }
@@ -569,6 +784,18 @@ __global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
         sasa_f4 dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         for (int tile = wave; tile < ntiles; tile += 4) {
             const int q0 = tile * 16;
+            // masked: the fields of queries q0 + 4lk + i for the workgroup's key tile rb (bit li: this lane's key); a query
+            // past Q counts as blocked
+            unsigned fq[4] = {0, 0, 0, 0};
+            if constexpr (MASKED) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int qi = q0 + 4 * lk + i;
+                    fq[i] = qi < Q ? sasa_mask_field(a.mask, a.ld_mask, qi, rb, Q) : 0xffffu;
+                }
+                if (sasa_all_blocked(fq[0] & fq[1] & fq[2] & fq[3]))
+                    continue;
+            }
             const int qr = q0 + li < Q ? q0 + li : Q - 1;
             rac_f4 qA[2], gA[2], oA[2];
             sasa_row8(qA, a.qkv + (tok + qr) * ld + h * SASA_D, lk, scale);
@@ -601,7 +828,10 @@ __global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
                 const float D = __shfl(Dq, 4 * lk + r, 64);
                 const float dx = cx[r] - ckx, dy = cy[r] - cky;
                 const float dist = sqrtf(dx * dx + dy * dy);
-                p[r] = q0 + 4 * lk + r < Q ? expf(s[r] - dist * tq[r] - lq[r]) : 0.f;
+                bool allowed = q0 + 4 * lk + r < Q;
+                if constexpr (MASKED)
+                    allowed = !((fq[r] >> li) & 1u);
+                p[r] = allowed ? expf(s[r] - dist * tq[r] - lq[r]) : 0.f;
                 ds[r] = p[r] * (dp[r] - D);
             }
 #pragma unroll
@@ -624,32 +854,58 @@ __global__ __launch_bounds__(256) void sasa_bwd_kernel(const SasaBwdArgs a)
     }
 }
 
-extern "C" int rac_sasa_bwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
-                            const float *out, const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau,
-                            int ld_qkv, int ld_tau, int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim,
-                            const float *pc_range, void *stream)
+// the argument checks and the launch of rac_sasa_bwd (masked = false) and rac_sasa_bwd_mask
+static int sasa_bwd_launch(const char *fn, bool masked, const float *qkv, const float *tau, const float *query_bbox,
+                           const float *box_table, const float *out, const float *lse, const float *grad_out, float *grad_qkv,
+                           float *grad_tau, const uint32_t *mask_bits, int ld_mask, int ld_qkv, int ld_tau, int ld_grad_qkv,
+                           int ld_grad_tau, int B, int Q, int heads, int dim, const float *pc_range, void *stream)
 {
-    RAC_CHECK_ARG(dim == SASA_D, "rac_sasa_bwd: head dim %d (the kernel is built for %d)", dim, SASA_D);
+    RAC_CHECK_ARG(dim == SASA_D, "%s: head dim %d (the kernel is built for %d)", fn, dim, SASA_D);
     RAC_CHECK_ARG(B >= 0 && Q >= 0 && heads >= 1 && ld_tau >= heads && ld_qkv >= 3 * heads * dim && ld_qkv % 4 == 0 &&
                       ld_grad_qkv >= 3 * heads * dim && ld_grad_qkv % 2 == 0 && ld_grad_tau >= heads,
-                  "rac_sasa_bwd: bad sizes B=%d Q=%d heads=%d ld_qkv=%d ld_tau=%d ld_grad_qkv=%d ld_grad_tau=%d", B, Q, heads,
+                  "%s: bad sizes B=%d Q=%d heads=%d ld_qkv=%d ld_tau=%d ld_grad_qkv=%d ld_grad_tau=%d", fn, B, Q, heads,
                   ld_qkv, ld_tau, ld_grad_qkv, ld_grad_tau);
-    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "rac_sasa_bwd: Q=%d too large for the LDS centre table", Q);
+    RAC_CHECK_ARG((size_t)Q * 2 * sizeof(float) <= 48 * 1024, "%s: Q=%d too large for the LDS centre table", fn, Q);
+    RAC_CHECK_ARG(!masked || ld_mask >= (Q + 31) / 32, "%s: ld_mask=%d shorter than the %d words of a mask row (Q=%d)", fn, ld_mask, (Q + 31) / 32, Q);
     if (B == 0 || Q == 0)
         return 0;
     RAC_CHECK_ARG(qkv && tau && query_bbox && out && lse && grad_out && grad_qkv && grad_tau && pc_range,
-                  "rac_sasa_bwd: null pointer");
+                  "%s: null pointer", fn);
+    RAC_CHECK_ARG(!masked || mask_bits, "%s: null pointer (mask_bits)", fn);
     SasaBwdArgs a;
     a.qkv = qkv; a.tau = tau; a.qbox = query_bbox; a.out = out; a.lse = lse; a.gout = grad_out;
-    // the centres the forward used: its VALU kernel (Q > 1024) always decodes the boxes itself
-    a.box = Q <= 4 * SASA_NT * 16 ? box_table : nullptr;
+    // the centres the forward used: the unmasked VALU kernel (Q > 1024) always decodes the boxes itself; both masked forwards
+    // read the table when there is one
+    a.box = (masked || Q <= 4 * SASA_NT * 16) ? box_table : nullptr;
     a.gqkv = grad_qkv; a.gtau = grad_tau;
     for (int i = 0; i < 6; ++i)
         a.pc[i] = pc_range[i];
     a.B = B; a.Q = Q; a.H = heads; a.ld_qkv = ld_qkv; a.ld_tau = ld_tau; a.ld_gqkv = ld_grad_qkv; a.ld_gtau = ld_grad_tau;
     a.row_blocks = (Q + SASA_ROWS - 1) / SASA_ROWS;
+    a.mask = masked ? mask_bits : nullptr; a.ld_mask = masked ? ld_mask : 0;
     const int nb = 2 * B * heads * a.row_blocks;
     const size_t lds = ((size_t)2 * ((Q + 1) & ~1) + 4 * 16 + 4 * 32 * 16) * sizeof(float);
-    hipLaunchKernelGGL(sasa_bwd_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
-    return rac_launch_status("rac_sasa_bwd");
+    if (masked)
+        hipLaunchKernelGGL(sasa_bwd_kernel<true>, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(sasa_bwd_kernel<false>, dim3(nb), dim3(256), lds, (hipStream_t)stream, a);
+    return rac_launch_status(fn);
+}
+
+extern "C" int rac_sasa_bwd(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                            const float *out, const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau,
+                            int ld_qkv, int ld_tau, int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim,
+                            const float *pc_range, void *stream)
+{
+    return sasa_bwd_launch("rac_sasa_bwd", false, qkv, tau, query_bbox, box_table, out, lse, grad_out, grad_qkv, grad_tau, nullptr,
+                           0, ld_qkv, ld_tau, ld_grad_qkv, ld_grad_tau, B, Q, heads, dim, pc_range, stream);
+}
+
+extern "C" int rac_sasa_bwd_mask(const float *qkv, const float *tau, const float *query_bbox, const float *box_table,
+                                 const float *out, const float *lse, const float *grad_out, float *grad_qkv, float *grad_tau,
+                                 int ld_qkv, int ld_tau, int ld_grad_qkv, int ld_grad_tau, int B, int Q, int heads, int dim,
+                                 const float *pc_range, void *stream, const uint32_t *mask_bits, int ld_mask)
+{
+    return sasa_bwd_launch("rac_sasa_bwd_mask", true, qkv, tau, query_bbox, box_table, out, lse, grad_out, grad_qkv, grad_tau,
+                           mask_bits, ld_mask, ld_qkv, ld_tau, ld_grad_qkv, ld_grad_tau, B, Q, heads, dim, pc_range, stream);
 }

@@ -335,11 +335,48 @@ def bev_sampling_multi_fused(streams, hw, query_bbox, time_diff, num_frames, num
     return out
 
 
-def sasa_fused(qkv, tau, query_bbox, num_heads, pc_range, box_table=None, lse_out=None):
+class PackedAttnMask:
+    """A boolean [Q,Q] attention mask (True: query i does not attend to key j) in the two forms its users read: ``bits``, the
+    int32 view [Q, ceil(Q/32)] of the uint32 words rac_sasa_fwd_mask / rac_sasa_bwd_mask take (bit j & 31 of word [i][j >> 5]),
+    and ``dense``, the bool tensor itself (forward_unfused).  Built by pack_attn_mask."""
+
+    __slots__ = ("bits", "dense")
+
+    def __init__(self, bits, dense):
+        self.bits, self.dense = bits, dense
+
+
+def pack_attn_mask(mask_bool):
+    """bool [Q,Q] -> PackedAttnMask.  torch ops on the mask's device only: no host synchronisation."""
+    if isinstance(mask_bool, PackedAttnMask):
+        return mask_bool
+    if mask_bool.dim() != 2 or mask_bool.shape[0] != mask_bool.shape[1] or mask_bool.dtype != torch.bool:
+        raise RuntimeError(f"pack_attn_mask: expected a bool [Q,Q] mask, got {mask_bool.dtype} {list(mask_bool.shape)}")
+    Q = mask_bool.shape[0]
+    W = (Q + 31) // 32
+    m = torch.nn.functional.pad(mask_bool, (0, W * 32 - Q)).view(Q, W, 32).to(torch.int64)
+    words = (m << torch.arange(32, device=mask_bool.device, dtype=torch.int64)).sum(-1)      # 0 .. 2^32 - 1
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)             # the same 32 bits, as int32
+    return PackedAttnMask(words.contiguous(), mask_bool)
+
+
+def _mask_words(mask, Q, what):
+    """(pointer, ld_mask) of a PackedAttnMask's words for a [.,Q,.] problem"""
+    if not isinstance(mask, PackedAttnMask):
+        raise RuntimeError(f"{what}: mask must be a PackedAttnMask (pack_attn_mask)")
+    bits = mask.bits
+    _lib.require_gpu(bits, what=f"{what}(mask)")
+    if bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[0] != Q or bits.shape[1] < (Q + 31) // 32 or not bits.is_contiguous():
+        raise RuntimeError(f"{what}: mask words must be contiguous int32 [{Q}, >= {(Q + 31) // 32}], got {list(bits.shape)}")
+    return _lib.ptr(bits), bits.shape[1]
+
+
+def sasa_fused(qkv, tau, query_bbox, num_heads, pc_range, box_table=None, lse_out=None, mask=None):
     """qkv [B,Q,3*E] (q|k|v, each [heads, E/heads]; may be a column slice), tau [B,Q,heads] ->
     attention output [B,Q,E] before out_proj.
     ``lse_out``: optional contiguous f32 [B,heads,Q] that receives every query row's log-sum-exp (rac_sasa_fwd_ex, for
-    sasa_backward); the output is bit-identical either way."""
+    sasa_backward); the output is bit-identical either way.
+    ``mask``: optional PackedAttnMask shared by all batches and heads (rac_sasa_fwd_mask): blocked pairs get probability 0."""
     _lib.require_gpu(query_bbox, what="sasa_fused")
     B, Q, _ = query_bbox.shape
     E = qkv.shape[-1] // 3
@@ -355,7 +392,12 @@ def sasa_fused(qkv, tau, query_bbox, num_heads, pc_range, box_table=None, lse_ou
     if ev:
         ev[0].record()
     box = _lib.ptr(box_table) if box_table is not None else None
-    if lse_out is None:
+    if mask is not None:
+        p_mask, ld_mask = _mask_words(mask, Q, "sasa_fused")
+        rc = _lib.lib().rac_sasa_fwd_mask(p_qkv, p_tau, _lib.ptr(query_bbox), box, _lib.ptr(out),
+                                          _lib.ptr(lse_out) if lse_out is not None else None, ld_qkv, ld_tau, B, Q, num_heads,
+                                          E // num_heads, pc, _lib.stream_ptr(), p_mask, ld_mask)
+    elif lse_out is None:
         rc = _lib.lib().rac_sasa_fwd(p_qkv, p_tau, _lib.ptr(query_bbox), box, _lib.ptr(out), ld_qkv, ld_tau, B, Q, num_heads,
                                      E // num_heads, pc, _lib.stream_ptr())
     else:
@@ -363,12 +405,14 @@ def sasa_fused(qkv, tau, query_bbox, num_heads, pc_range, box_table=None, lse_ou
                                         ld_tau, B, Q, num_heads, E // num_heads, pc, _lib.stream_ptr())
     if ev:
         ev[1].record()
-    _lib.check(rc, "rac_sasa_fwd" if lse_out is None else "rac_sasa_fwd_ex")
+    _lib.check(rc, "rac_sasa_fwd_mask" if mask is not None else "rac_sasa_fwd" if lse_out is None else "rac_sasa_fwd_ex")
     return out
 
 
-def sasa_backward(qkv, tau, query_bbox, num_heads, pc_range, out, lse, grad_out, box_table=None, grad_qkv=None, grad_tau=None):
-    """Backward of sasa_fused (rac_sasa_bwd): qkv, tau, query_bbox, box_table as given to it, out and lse what it returned and
+def sasa_backward(qkv, tau, query_bbox, num_heads, pc_range, out, lse, grad_out, box_table=None, grad_qkv=None, grad_tau=None,
+                  mask=None):
+    """Backward of sasa_fused (rac_sasa_bwd; rac_sasa_bwd_mask with ``mask``): qkv, tau, query_bbox, box_table, mask as given to
+    it, out and lse what it returned and
     wrote, grad_out [B,Q,E] -> (grad_qkv [B,Q,3*E], grad_tau [B,Q,heads]).  ``grad_qkv`` / ``grad_tau``: destinations with
     unit inner stride and a row stride of their own (e.g. the two column slices of one [B,Q,3*E+heads] buffer); allocated as
     that one buffer when not given.  Every element of both is written."""
@@ -389,12 +433,16 @@ def sasa_backward(qkv, tau, query_bbox, num_heads, pc_range, out, lse, grad_out,
     ev = _lib.timer.record("sasa_bwd") if _lib.timer is not None else None
     if ev:
         ev[0].record()
-    rc = _lib.lib().rac_sasa_bwd(p_qkv, p_tau, _lib.ptr(query_bbox), _lib.ptr(box_table) if box_table is not None else None,
-                                 _lib.ptr(out), _lib.ptr(lse), _lib.ptr(grad_out), p_gqkv, p_gtau, ld_qkv, ld_tau, ld_gqkv,
-                                 ld_gtau, B, Q, num_heads, E // num_heads, pc, _lib.stream_ptr())
+    args = (p_qkv, p_tau, _lib.ptr(query_bbox), _lib.ptr(box_table) if box_table is not None else None,
+            _lib.ptr(out), _lib.ptr(lse), _lib.ptr(grad_out), p_gqkv, p_gtau, ld_qkv, ld_tau, ld_gqkv,
+            ld_gtau, B, Q, num_heads, E // num_heads, pc, _lib.stream_ptr())
+    if mask is not None:
+        rc = _lib.lib().rac_sasa_bwd_mask(*args, *_mask_words(mask, Q, "sasa_backward"))
+    else:
+        rc = _lib.lib().rac_sasa_bwd(*args)
     if ev:
         ev[1].record()
-    _lib.check(rc, "rac_sasa_bwd")
+    _lib.check(rc, "rac_sasa_bwd_mask" if mask is not None else "rac_sasa_bwd")
     return grad_qkv, grad_tau
 
 

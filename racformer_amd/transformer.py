@@ -34,7 +34,7 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, 
                     generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, outproj_fused,
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
-                    pe_head, refine_backward, refine_fused, regroup_backward, regroup_fused, row_gemm,
+                    PackedAttnMask, pack_attn_mask, pe_head, refine_backward, refine_fused, regroup_backward, regroup_fused, row_gemm,
                     row_seg, rowgemm_launch, sampling4d_backward, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
 from .msda import msda_backward, msda_forward
 from .msmv import msmv_backward, msmv_forward, msmv_v2_backward, msmv_v2_forward
@@ -137,10 +137,15 @@ class ScaleAdaptiveSelfAttention(nn.Module):
                 torch.cat([p.in_proj_bias, self.gen_tau.bias], dim=0))
 
     def forward(self, query_bbox, query_feat, pre_attn_mask=None, prepared_w=None):
-        if self.fused and pre_attn_mask is None and self.embed_dims // self.num_heads == 32:
+        """``pre_attn_mask``: None, a bool [Q,Q] tensor (True: blocked; packed on the spot) or a PackedAttnMask (the decoder packs
+        once for its six layers).  The fused path takes a mask under the same conditions as without one (rac_sasa_fwd_mask /
+        rac_sasa_bwd_mask); without a mask every call launches what it launched before."""
+        if self.fused and self.embed_dims // self.num_heads == 32:
             # one GEMM for in_proj + gen_tau, one HIP kernel for mask + QK^T + softmax + AV
             p = self.attention.attn
             E = self.embed_dims
+            # (the keyword is passed only when there is a mask: an unmasked call is the call it always was)
+            mkw = {} if pre_attn_mask is None else {"mask": pack_attn_mask(pre_attn_mask)}
             params = (p.in_proj_weight, p.in_proj_bias, self.gen_tau.weight, self.gen_tau.bias)
             if torch.is_grad_enabled() and (query_feat.requires_grad or any(t.requires_grad for t in params)):
                 # training: through _SASACore (rac_sasa_fwd_ex + rac_sasa_bwd).  A prepared operand without autograd history
@@ -149,12 +154,12 @@ class ScaleAdaptiveSelfAttention(nn.Module):
                 if prepared_w is None or not (prepared_w[0].requires_grad and prepared_w[1].requires_grad):
                     prepared_w = self.wide_in_proj()
                 lin = F.linear(query_feat, prepared_w[0], prepared_w[1])
-                o = _SASACore.apply(lin, query_bbox.detach().contiguous(), None, self.num_heads, self.pc_range)
+                o = _SASACore.apply(lin, query_bbox.detach().contiguous(), None, self.num_heads, self.pc_range, *mkw.values())
                 return query_feat + p.out_proj(o)
             if prepared_w is None:
                 prepared_w = self.wide_in_proj()
             lin = F.linear(query_feat, prepared_w[0], prepared_w[1])
-            o = sasa_fused(lin[..., :3 * E], lin[..., 3 * E:], query_bbox.contiguous(), self.num_heads, self.pc_range)
+            o = sasa_fused(lin[..., :3 * E], lin[..., 3 * E:], query_bbox.contiguous(), self.num_heads, self.pc_range, **mkw)
             return query_feat + p.out_proj(o)
         return self.forward_unfused(query_bbox, query_feat, pre_attn_mask)
 
@@ -166,7 +171,7 @@ class ScaleAdaptiveSelfAttention(nn.Module):
         tau = self.gen_tau(query_feat).permute(0, 2, 1)                                     # [B,H,Q]
         mask = dist[:, None] * tau[..., None]
         if pre_attn_mask is not None:
-            mask[:, :, pre_attn_mask] = float("-inf")
+            mask[:, :, pre_attn_mask.dense if isinstance(pre_attn_mask, PackedAttnMask) else pre_attn_mask] = float("-inf")
         p = self.attention.attn
         qkv = F.linear(query_feat, p.in_proj_weight, p.in_proj_bias).view(B, Q, 3, Hn, d)
         q = qkv[:, :, 0].permute(0, 2, 1, 3) * math.sqrt(1.0 / d)
@@ -340,18 +345,22 @@ class _BEVAttendGather(torch.autograd.Function):
 
 
 class _SASACore(torch.autograd.Function):
-    """The SASA core: apply(lin [B,Q,3E+heads] = q|k|v|tau, query_bbox [B,Q,10], box_table [B,Q,8] or None, heads, pc_range)
+    """The SASA core: apply(lin [B,Q,3E+heads] = q|k|v|tau, query_bbox [B,Q,10], box_table [B,Q,8] or None, heads, pc_range
+    [, mask: a PackedAttnMask, not differentiable, kept on ctx and handed to the backward as it came])
     -> O [B,Q,E] before out_proj.  The forward is rac_sasa_fwd_ex (the output of rac_sasa_fwd, plus each row's log-sum-exp);
     the backward rac_sasa_bwd, writing dq|dk|dv and dtau into one [B,Q,3E+heads] gradient of lin (no cat).  No gradient for
     the boxes: the reference forms the distances under no_grad (calc_bbox_dists).  The launchers are looked up as this
     module's globals at call time."""
 
     @staticmethod
-    def forward(ctx, lin, query_bbox, box_table, num_heads, pc_range):
+    def forward(ctx, lin, query_bbox, box_table, num_heads, pc_range, mask=None):
         B, Q, W = lin.shape
         E = (W - num_heads) // 3
         lse = torch.empty(B, num_heads, Q, device=lin.device, dtype=torch.float32)
-        o = sasa_fused(lin[..., :3 * E], lin[..., 3 * E:], query_bbox, num_heads, pc_range, box_table=box_table, lse_out=lse)
+        # (the keyword is passed only when there is a mask: an unmasked call is the call it always was)
+        ctx.mkw = {} if mask is None else {"mask": mask}
+        o = sasa_fused(lin[..., :3 * E], lin[..., 3 * E:], query_bbox, num_heads, pc_range, box_table=box_table, lse_out=lse,
+                       **ctx.mkw)
         ctx.num_heads, ctx.pc_range = num_heads, pc_range
         ctx.save_for_backward(lin, query_bbox, box_table, o, lse)
         return o
@@ -362,8 +371,8 @@ class _SASACore(torch.autograd.Function):
         E = (lin.shape[-1] - ctx.num_heads) // 3
         grad_lin = torch.empty(lin.shape, device=lin.device, dtype=lin.dtype)
         sasa_backward(lin[..., :3 * E], lin[..., 3 * E:], query_bbox, ctx.num_heads, ctx.pc_range, o, lse, grad_o.contiguous(),
-                      box_table=box_table, grad_qkv=grad_lin[..., :3 * E], grad_tau=grad_lin[..., 3 * E:])
-        return grad_lin, None, None, None, None
+                      box_table=box_table, grad_qkv=grad_lin[..., :3 * E], grad_tau=grad_lin[..., 3 * E:], **ctx.mkw)
+        return grad_lin, None, None, None, None, None
 
 
 class _BEVSamplingCore(torch.autograd.Function):
@@ -1760,6 +1769,8 @@ class RaCFormerTransformerDecoder(nn.Module):
             grouped = regroup_pyramid(mlvl_feats, self.num_cams, 4, self.feature_dtype)
             for lvl, g in enumerate(grouped):
                 mlvl_feats[lvl] = g  # the reference mutates the caller's list too (:124)
+        if attn_mask is not None:
+            attn_mask = pack_attn_mask(attn_mask)    # a bool [Q,Q] mask is packed once; the six layers share the words
         dl = self.decoder_layer
         # (the gate of the training route is judged over ALL inputs of the layer here; prepare() alone sees the BEV stacks only)
         train = dl.records_grad(query_feat, query_bbox, lss_bev_feats, radar_bev_feats, *mlvl_feats)

@@ -56,6 +56,11 @@
  *   rac_sampling4d_bwd <- autograd of RaCFormerSampling.inner_forward + sampling_4d + msmv op in one launch
  *   rac_regroup_bwd / rac_regroup_multi_bwd <- autograd of the regroup's permute().contiguous(), models/racformer_transformer.py:112-124
  *   rac_refine_bwd    <- autograd of refine_bbox + velocity scaling + theta_d2xy_coods (the ops rac_refine_fwd replaces)
+ *   rac_match_cost_fwd <- the cost matrix of PolarHungarianAssigner3D / HungarianAssigner3D.assign
+ *                        models/bbox/assigners/polar_hungarian_assigner_3d.py:56-78, models/bbox/match_costs/match_cost.py
+ *   rac_lsap_fwd / rac_lsap_host <- scipy.optimize.linear_sum_assignment as the assigners call it (:84)
+ *   rac_det_loss_fwd  <- the targets, FocalLoss and L1Loss of loss_single / dn_loss_single with their autograd backwards
+ *                        models/racformer_head.py:264-300, 326-427
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -66,7 +71,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 17
+#define RAC_ABI_VERSION 18
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -693,6 +698,53 @@ int rac_upsample2x_image_fwd(const float *src, void *img, int frames, int h, int
 int rac_conv3x3_temporal_fwd(const void *xs, const void *ws, const float *pixel_bias_live, const float *pixel_bias_dead,
                              const float *amax, float w_alpha, float *out, void *q, float *scale, int N, int H, int W, int Cin,
                              int Cin_dead, int frames_per_group, int live_per_group, void *stream);
+
+/* ---- the head loss: match costs, assignment, focal + L1 (batched over P = num_layers * batch problems) ----
+ * Ground truth: ONE concatenated table gt_boxes [sum G, 9] (x, y, z, w, l, h, yaw, vx, vy; gravity centre), gt_labels [sum G]
+ * and offsets [batch + 1] (offsets[0] = 0; sample b owns rows offsets[b] .. offsets[b+1]).  offsets is a HOST array, built
+ * from the lengths of the ground-truth lists; batch <= 64.
+ *
+ * rac_match_cost_fwd: cost [P, gmax, qpad] fp32, the query index fastest; entry (p = l * batch + b, g, q) for g < G_b, q < Q:
+ *   FocalLossCost(alpha 0.25, gamma 2, eps 1e-12) * cls_weight
+ *   + sum_k |pred_k cw_k - normalize_bbox(gt)_k cw_k| * reg_weight              (all 10 columns)
+ *   + (polar) |remainder(|theta(pred) - theta(gt)| + 0.5, 1) - 0.5| * theta_weight, theta from the code-weighted x, y through
+ *     ThetaL1Cost's own pc_range (-51.2 .. 51.2) and xy2theta_d_coods(norm=True)
+ *   then nan_to_num(nan = 100, posinf = 100, neginf = -100).  Entries with g >= G_b or q >= Q are left as they are.
+ *   cls_scores [L,B,Q,C], bbox_preds [L,B,Q,10], code_weights [10] (device) */
+int rac_match_cost_fwd(const float *cls_scores, const float *bbox_preds, const float *gt_boxes, const int32_t *gt_labels,
+                       const int32_t *offsets, const float *code_weights, float *cost, int num_layers, int batch, int num_query,
+                       int num_classes, int gmax, int qpad, float cls_weight, float reg_weight, float theta_weight, int polar,
+                       void *stream);
+
+/* rac_lsap_fwd: the P rectangular assignment problems of a cost tensor laid out as above, on the device: every ground-truth box
+ * gets one distinct query at minimum total cost (shortest augmenting paths, duals and path lengths in float64, the cost widened
+ * on read; one wave64 per problem; ties of a step's minimum go to the smaller query index).  Entries with g >= G_b or
+ * q >= num_query are never read.
+ *   matched_query [P, gmax]  the query of box g (-1 for g >= G_b)
+ *   assigned_gt   [P, Q]     offsets[b] + g for a matched query (an index into the concatenated table), -1 for background
+ *   u [P, gmax], v [P, Q]    float64 duals: u_g + v_q <= cost everywhere, equal on matched pairs, v <= 0, v = 0 when unmatched
+ *   steps [P] or NULL        Dijkstra steps taken (at most G (G + 1) / 2); negative if the problem was given up
+ * A problem whose costs leave no finite path (NaN, +inf) is given up: all background, duals 0.
+ * num_query <= 2048 and gmax <= num_query, else RAC_E_UNSUPPORTED (rac_lsap_host takes those). */
+int rac_lsap_fwd(const float *cost, const int32_t *offsets, int32_t *matched_query, int32_t *assigned_gt, double *u, double *v,
+                 int32_t *steps, int num_layers, int batch, int num_query, int gmax, int qpad, void *stream);
+
+/* rac_lsap_host: ONE problem on the host in plain C++, the same algorithm and arithmetic, any num_gt and num_query (it iterates
+ * over the smaller side).  cost(g, q) = cost[g * gt_stride + q * query_stride] (HOST memory).
+ *   matched_query [num_gt] (-1: unmatched, possible when num_gt > num_query), matched_gt [num_query] (-1: background)
+ *   u [num_gt], v [num_query] float64 duals; steps: one counter or NULL.  RAC_E_UNSUPPORTED if no finite assignment exists. */
+int rac_lsap_host(const float *cost, int64_t gt_stride, int64_t query_stride, int num_gt, int num_query, int32_t *matched_query,
+                  int32_t *matched_gt, double *u, double *v, int64_t *steps);
+
+/* rac_det_loss_fwd: sigmoid focal loss + code-weighted L1 of rows [num_layers, rows], forward sums and unit gradients in one pass.
+ *   target [L, rows]: index into the ground-truth table, -1 = background (label num_classes, no box term); NULL: row r takes
+ *   entry r mod num_gt (the denoising rows).  A positive row whose normalize_bbox(gt) has a non-finite entry has no box term.
+ *   sums [L, 2] = (sum of focal terms, sum of |pred - target| * code_weights) -- raw, not averaged
+ *   grad_logits [L, rows, C], grad_boxes [L, rows, 10]: d sums[l,0] / d logits, d sums[l,1] / d boxes
+ * Fixed-order reduction (no float atomics): bitwise reproducible. */
+int rac_det_loss_fwd(const float *logits, const float *boxes, const int32_t *target, const float *gt_boxes, const int32_t *gt_labels,
+                     const float *code_weights, float *sums, float *grad_logits, float *grad_boxes, int num_layers, int rows,
+                     int num_classes, int num_gt, float alpha, float gamma, void *stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,15 @@ def decode_bbox(bboxes, pc_range=None):
     return torch.cat(parts, dim=-1)
 
 
+def normalize_bbox(bboxes):
+    """bbox/utils.py:7-23: [x, y, z, w, l, h, yaw, (vx, vy)] -> [cx, cy, log w, log l, cz, log h, sin, cos, (vx, vy)]"""
+    rot = bboxes[..., 6:7]
+    parts = [bboxes[..., 0:2], bboxes[..., 3:5].log(), bboxes[..., 2:3], bboxes[..., 5:6].log(), rot.sin(), rot.cos()]
+    if bboxes.size(-1) > 7:
+        parts.append(bboxes[..., 7:9])
+    return torch.cat(parts, dim=-1)
+
+
 def denormalize_bbox(normalized_bboxes):
     """bbox/utils.py:26-46 (input order cx, cy, w, l, cz, h, sin, cos, vx, vy)"""
     nb = normalized_bboxes

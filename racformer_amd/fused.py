@@ -1196,3 +1196,110 @@ def decode_fused(cls_scores, bbox_preds, max_num, post_center_range, score_thres
     _lib.check(rc, "rac_decode_fwd")
     return out
 
+
+
+# ------------------------------------------------------------------------------------------- head loss
+def _gt_offsets(counts, what):
+    off = [0]
+    for n in counts:
+        off.append(off[-1] + int(n))
+    if len(counts) > 64:
+        raise RuntimeError(f"racformer_amd.{what}: at most 64 samples a call")
+    return off, (ctypes.c_int32 * len(off))(*off)
+
+
+def _f32_gpu(what, *tensors):
+    _lib.require_gpu(*tensors, what=what)
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"racformer_amd.{what}: float32 tensors only")
+
+
+def match_cost_fused(all_cls_scores, all_bbox_preds, gt_boxes, gt_labels, counts, code_weights, cls_weight, reg_weight,
+                     theta_weight=None, out=None):
+    """The assigners' cost matrices of every (layer, sample) in one launch (rac_match_cost_fwd).  all_cls_scores [L,B,Q,C],
+    all_bbox_preds [L,B,Q,10] (detached); gt_boxes [sum G, 9], gt_labels [sum G] int32: the samples' ground truth concatenated;
+    counts: the host list of boxes per sample; theta_weight None: no ThetaL1Cost (HungarianAssigner3D).
+    -> cost [L*B, Gmax, Qpad] (Qpad: Q rounded up to 64); entries beyond a sample's boxes or beyond Q are not written."""
+    _f32_gpu("match_cost_fused", all_cls_scores, all_bbox_preds, gt_boxes, code_weights)
+    _lib.require_gpu(gt_labels, what="match_cost_fused")
+    if gt_labels.dtype != torch.int32:
+        raise RuntimeError("racformer_amd.match_cost_fused: gt_labels must be int32")
+    L, B, Q, C = all_cls_scores.shape
+    off, c_off = _gt_offsets(counts, "match_cost_fused")
+    if len(counts) != B or off[-1] != gt_boxes.shape[0] or gt_labels.shape[0] != off[-1] or tuple(all_bbox_preds.shape) != (L, B, Q, 10) \
+            or gt_boxes.shape[-1] != 9 or code_weights.numel() != 10:
+        raise RuntimeError("racformer_amd.match_cost_fused: shapes do not fit (boxes [L,B,Q,10], ground truth [sum G,9], one count per sample)")
+    gmax, qpad = max(counts) if counts else 0, (Q + 63) // 64 * 64
+    if out is None:
+        out = torch.empty(L * B, gmax, qpad, device=all_cls_scores.device, dtype=torch.float32)
+    elif tuple(out.shape) != (L * B, gmax, qpad) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise RuntimeError("racformer_amd.match_cost_fused: out must be a contiguous float32 [L*B, Gmax, Qpad]")
+    rc = _lib.lib().rac_match_cost_fwd(_lib.ptr(all_cls_scores), _lib.ptr(all_bbox_preds), _lib.ptr(gt_boxes), _lib.ptr(gt_labels), c_off,
+                                       _lib.ptr(code_weights), _lib.ptr(out), L, B, Q, C, gmax, qpad, float(cls_weight), float(reg_weight),
+                                       float(theta_weight or 0.0), int(theta_weight is not None), _lib.stream_ptr())
+    _lib.check(rc, "rac_match_cost_fwd")
+    return out
+
+
+def lsap_fused(cost, counts, num_layers, num_query, with_steps=False):
+    """The L*B assignment problems of a match_cost_fused tensor on the device (rac_lsap_fwd): no host read-back.
+    -> matched_query [P,Gmax] int32, assigned_gt [P,Q] int32 (index into the concatenated ground truth, -1 background),
+    u [P,Gmax] and v [P,Q] float64 duals (, steps [P] int32)."""
+    _f32_gpu("lsap_fused", cost)
+    P, gmax, qpad = cost.shape
+    B = len(counts)
+    _, c_off = _gt_offsets(counts, "lsap_fused")
+    if P != num_layers * B or gmax != (max(counts) if counts else 0) or qpad < num_query:
+        raise RuntimeError("racformer_amd.lsap_fused: cost must be [num_layers * len(counts), max(counts), >= num_query]")
+    dev = cost.device
+    matched = torch.empty(P, gmax, device=dev, dtype=torch.int32)
+    assigned = torch.empty(P, num_query, device=dev, dtype=torch.int32)
+    u = torch.empty(P, gmax, device=dev, dtype=torch.float64)
+    v = torch.empty(P, num_query, device=dev, dtype=torch.float64)
+    steps = torch.empty(P, device=dev, dtype=torch.int32) if with_steps else None
+    rc = _lib.lib().rac_lsap_fwd(_lib.ptr(cost), c_off, _lib.ptr(matched), _lib.ptr(assigned), _lib.ptr(u), _lib.ptr(v),
+                                 _lib.ptr(steps) if with_steps else None, num_layers, B, num_query, gmax, qpad, _lib.stream_ptr())
+    _lib.check(rc, "rac_lsap_fwd")
+    return (matched, assigned, u, v, steps) if with_steps else (matched, assigned, u, v)
+
+
+def det_loss_fused(logits, boxes, target, gt_boxes, gt_labels, code_weights, alpha=0.25, gamma=2.0):
+    """Focal + L1 sums of rows [L,R] with their unit gradients in one launch (rac_det_loss_fwd).  logits [L,R,C], boxes [L,R,10];
+    target [L,R] int32 (index into gt_boxes / gt_labels, -1 background) or None (row r takes entry r mod len(gt_boxes)).
+    -> sums [L,2], grad_logits [L,R,C], grad_boxes [L,R,10]."""
+    _f32_gpu("det_loss_fused", logits, boxes, gt_boxes, code_weights)
+    L, R, C = logits.shape
+    if tuple(boxes.shape) != (L, R, 10) or gt_boxes.shape[-1] != 9 or gt_labels.shape[0] != gt_boxes.shape[0] or code_weights.numel() != 10:
+        raise RuntimeError("racformer_amd.det_loss_fused: shapes do not fit (boxes [L,R,10], ground truth [n,9] with n labels)")
+    for t in (gt_labels, target):
+        if t is not None:
+            _lib.require_gpu(t, what="det_loss_fused")
+            if t.dtype != torch.int32:
+                raise RuntimeError("racformer_amd.det_loss_fused: gt_labels and target must be int32")
+    if target is not None and tuple(target.shape) != (L, R):
+        raise RuntimeError("racformer_amd.det_loss_fused: target must be [L,R]")
+    sums = torch.empty(L, 2, device=logits.device, dtype=torch.float32)
+    g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
+    rc = _lib.lib().rac_det_loss_fwd(_lib.ptr(logits), _lib.ptr(boxes), _lib.ptr(target) if target is not None else None, _lib.ptr(gt_boxes),
+                                     _lib.ptr(gt_labels), _lib.ptr(code_weights), _lib.ptr(sums), _lib.ptr(g_logits), _lib.ptr(g_boxes),
+                                     L, R, C, gt_boxes.shape[0], float(alpha), float(gamma), _lib.stream_ptr())
+    _lib.check(rc, "rac_det_loss_fwd")
+    return sums, g_logits, g_boxes
+
+
+def lsap_host(cost_gq=None, cost_qg=None):
+    """One assignment problem on the host (rac_lsap_host, plain C++ in float64; no GPU, no scipy).  Give the float32 cost as
+    cost_gq [G,Q] or as cost_qg [Q,G] (the reference's layout), any strides, CPU memory.
+    -> matched_query [G] int32 (-1: unmatched), matched_gt [Q] int32 (-1: background), u [G], v [Q] float64, steps."""
+    c = cost_gq if cost_gq is not None else cost_qg
+    if c.is_cuda or c.dtype != torch.float32 or c.dim() != 2:
+        raise RuntimeError("racformer_amd.lsap_host: a float32 CPU matrix")
+    (G, Q), (gs, qs) = (c.shape, c.stride()) if cost_gq is not None else (c.shape[::-1], c.stride()[::-1])
+    mq, mg = torch.empty(G, dtype=torch.int32), torch.empty(Q, dtype=torch.int32)
+    u, v = torch.empty(G, dtype=torch.float64), torch.empty(Q, dtype=torch.float64)
+    steps = ctypes.c_int64(0)
+    rc = _lib.lib().rac_lsap_host(_lib.ptr(c), gs, qs, G, Q, _lib.ptr(mq), _lib.ptr(mg), _lib.ptr(u), _lib.ptr(v),
+                                  ctypes.cast(ctypes.pointer(steps), ctypes.c_void_p))
+    _lib.check(rc, "rac_lsap_host")
+    return mq, mg, u, v, steps.value

@@ -3,15 +3,41 @@ and ``NMSFreeCoder`` (models/bbox/coders/nms_free_coder.py:8-110): same names, c
 arguments, ``forward`` / ``get_bboxes`` / ``decode`` behaviour and ``state_dict`` keys
 (``init_query_bbox.weight``, ``label_enc.weight``, ``code_weights``, ``transformer.*``).
 Training mode builds the query-denoising inputs (``prepare_for_dn_input``), runs the decoder under their attention mask and
-returns the reference's dict with ``dn_mask_dict``; ``prepare_for_dn_loss`` is there for the losses.  The assigner and the losses
-themselves are not built: ``loss`` raises."""
+returns the reference's dict with ``dn_mask_dict``.  ``loss`` (racformer_head.py:264-485) is built when the constructor gets
+``loss_cls``, ``loss_bbox`` and ``train_cfg['assigner']``: on CUDA float32 outputs as three HIP launches for all layers and
+samples (match costs, assignment, focal + L1) plus one for the denoising rows, without a host read-back; ``loss_unfused`` is the
+reference's per-layer, per-sample route.  A head built without them raises from ``loss``."""
 import math
 
 import torch
 import torch.nn as nn
 
-from .bbox_utils import const_tensor, denormalize_bbox, encode_bbox, xy2theta_d_coods
+from .bbox_utils import const_tensor, denormalize_bbox, encode_bbox, normalize_bbox, xy2theta_d_coods
+from .losses import FocalLoss, L1Loss, build_assigner, build_loss, head_loss_sums
 from .transformer import RaCFormerTransformer
+
+_EPS32 = float(torch.finfo(torch.float32).eps)
+
+
+def multi_apply(func, *args):
+    """mmdet.core.multi_apply: map, then transpose the results"""
+    return tuple(map(list, zip(*map(func, *args))))
+
+
+def reduce_mean(tensor):
+    """mmdet.core.reduce_mean: the mean over the ranks (the tensor itself outside torch.distributed)"""
+    if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        return tensor
+    tensor = tensor.clone()
+    torch.distributed.all_reduce(tensor.div_(torch.distributed.get_world_size()), op=torch.distributed.ReduceOp.SUM)
+    return tensor
+
+
+def plain_gt_boxes(gt, device):
+    """[n,9] (gravity centre, w, l, h, yaw, vx, vy) from mmdet3d-style boxes (``.gravity_center``, ``.tensor``) or a plain tensor"""
+    if not isinstance(gt, torch.Tensor):
+        gt = torch.cat((gt.gravity_center, gt.tensor[:, 3:]), dim=1)
+    return gt.to(device)
 
 
 class NMSFreeCoder:
@@ -49,14 +75,23 @@ class NMSFreeCoder:
 
 
 class RaCFormer_head(nn.Module):
-    """models/racformer_head.py without the assigner and the losses.  ``transformer`` is a config dict
-    (``type='RaCFormerTransformer'``, as in configs/racformer_r50_nuimg_704x256_f8.py:152-166) or a
-    module; ``bbox_coder`` a config dict (``type='NMSFreeCoder'``) or an instance."""
+    """models/racformer_head.py.  ``transformer`` is a config dict (``type='RaCFormerTransformer'``, as in
+    configs/racformer_r50_nuimg_704x256_f8.py:152-166) or a module; ``bbox_coder`` a config dict (``type='NMSFreeCoder'``) or an
+    instance; ``loss_cls`` (FocalLoss, use_sigmoid=True), ``loss_bbox`` (L1Loss) and ``train_cfg['assigner']``
+    (PolarHungarianAssigner3D / HungarianAssigner3D) config dicts as in the same file (:180-199) or instances -- without them the
+    head is an inference head and ``loss`` raises."""
 
     def __init__(self, *args, num_classes, in_channels, num_query=900, num_clusters=5, transformer=None,
                  bbox_coder=None, code_size=10, code_weights=[1.0] * 10, query_denoising=True,
-                 query_denoising_groups=10, train_cfg=dict(), test_cfg=dict(max_per_img=100), **kwargs):
+                 query_denoising_groups=10, train_cfg=dict(), test_cfg=dict(max_per_img=100), loss_cls=None, loss_bbox=None,
+                 loss_iou=None, sync_cls_avg_factor=False, **kwargs):
         super().__init__()
+        # mmdet's DETRHead: the background weight of the classification term is 0 with FocalLoss (class_weight is not given)
+        self.bg_cls_weight, self.sync_cls_avg_factor, self.cls_out_channels = 0, sync_cls_avg_factor, num_classes
+        if isinstance(loss_iou, dict) and loss_iou.get("loss_weight", 1.0) != 0:
+            raise NotImplementedError("racformer_amd: an IoU loss is not built (the reference's configs weigh it 0)")
+        self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)
+        self.assigner = build_assigner(train_cfg["assigner"]) if train_cfg and "assigner" in train_cfg else None
         self.num_classes, self.in_channels, self.embed_dims = num_classes, in_channels, in_channels
         self.num_query, self.num_clusters, self.code_size = num_query, num_clusters, code_size
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
@@ -266,8 +301,169 @@ class RaCFormer_head(nn.Module):
             bbox_preds = bbox_preds.permute(1, 2, 0, 3)[(bid, map_known_indice)].permute(1, 0, 2)
         return known_labels, known_bboxs, cls_scores, bbox_preds, num_tgt
 
-    def loss(self, *args, **kwargs):
-        raise NotImplementedError("racformer_amd: assigner and losses are not built")
+    # ------------------------------------------------------------------------------------------------ losses
+    def _require_losses(self):
+        if self.assigner is None or self.loss_cls is None or self.loss_bbox is None:
+            raise NotImplementedError("racformer_amd: assigner and losses are not built")
+
+    def _avg_factors(self, num_total_pos, like):
+        """(cls_avg_factor, box avg factor) of loss_single (:396-409): host numbers outside torch.distributed, 0-dim device
+        tensors under it (the all_reduce stays on the stream)"""
+        cls_avg = num_total_pos * 1.0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            mean = reduce_mean(like.new_tensor([cls_avg]))[0]
+            return (mean.clamp(min=1) if self.sync_cls_avg_factor else max(cls_avg, 1)), mean.clamp(min=1)
+        return max(cls_avg, 1), max(cls_avg, 1.0)
+
+    def dn_loss_single(self, cls_scores, bbox_preds, known_bboxs, known_labels, num_total_pos=None):
+        """racformer_head.py:264-300"""
+        num_total_pos = self._avg_factors(num_total_pos, cls_scores)[1]
+        cls_scores = cls_scores.reshape(-1, self.cls_out_channels)
+        bbox_weights = torch.ones_like(bbox_preds)
+        label_weights = torch.ones_like(known_labels)
+        loss_cls = self.loss_cls(cls_scores, known_labels.long(), label_weights, avg_factor=num_total_pos)
+        bbox_preds = bbox_preds.reshape(-1, bbox_preds.size(-1))
+        normalized_bbox_targets = normalize_bbox(known_bboxs)
+        isnotnan = torch.isfinite(normalized_bbox_targets).all(dim=-1)
+        bbox_weights = bbox_weights * self.code_weights
+        loss_bbox = self.loss_bbox(bbox_preds[isnotnan, :10], normalized_bbox_targets[isnotnan, :10], bbox_weights[isnotnan, :10],
+                                   avg_factor=num_total_pos)
+        return self.dn_weight * torch.nan_to_num(loss_cls), self.dn_weight * torch.nan_to_num(loss_bbox)
+
+    def calc_dn_loss(self, loss_dict, preds_dicts, num_dec_layers):
+        """racformer_head.py:302-324"""
+        known_labels, known_bboxs, cls_scores, bbox_preds, num_tgt = self.prepare_for_dn_loss(preds_dicts["dn_mask_dict"])
+        dn_losses_cls, dn_losses_bbox = multi_apply(self.dn_loss_single, cls_scores, bbox_preds, [known_bboxs] * num_dec_layers,
+                                                    [known_labels] * num_dec_layers, [num_tgt] * num_dec_layers)
+        return self._fill_loss_dict(loss_dict, dn_losses_cls, dn_losses_bbox, "_dn")
+
+    @staticmethod
+    def _fill_loss_dict(loss_dict, losses_cls, losses_bbox, suffix=""):
+        """the last layer under the plain keys, layer i before it under 'd{i}.' (:315-322, :476-484)"""
+        loss_dict["loss_cls" + suffix], loss_dict["loss_bbox" + suffix] = losses_cls[-1], losses_bbox[-1]
+        for i, (c, b) in enumerate(zip(losses_cls[:-1], losses_bbox[:-1])):
+            loss_dict[f"d{i}.loss_cls" + suffix], loss_dict[f"d{i}.loss_bbox" + suffix] = c, b
+        return loss_dict
+
+    def _get_target_single(self, cls_score, bbox_pred, gt_labels, gt_bboxes, gt_bboxes_ignore=None):
+        """racformer_head.py:326-352 (the pseudo sampler: the positive rows are the assigned ones)"""
+        num_bboxes = bbox_pred.size(0)
+        assigned_gt_inds, _ = self.assigner.assign(bbox_pred, cls_score, gt_bboxes, gt_labels, gt_bboxes_ignore, self.code_weights, True)
+        pos_inds = torch.nonzero(assigned_gt_inds > 0, as_tuple=False).squeeze(-1).unique()
+        neg_inds = torch.nonzero(assigned_gt_inds == 0, as_tuple=False).squeeze(-1).unique()
+        pos_assigned_gt_inds = assigned_gt_inds[pos_inds] - 1
+        labels = gt_bboxes.new_full((num_bboxes,), self.num_classes, dtype=torch.long)
+        labels[pos_inds] = gt_labels.long()[pos_assigned_gt_inds]
+        label_weights = gt_bboxes.new_ones(num_bboxes)
+        bbox_targets = torch.zeros_like(bbox_pred)[..., :9]
+        bbox_weights = torch.zeros_like(bbox_pred)
+        bbox_weights[pos_inds] = 1.0
+        bbox_targets[pos_inds] = gt_bboxes[pos_assigned_gt_inds].to(bbox_targets.dtype)
+        return labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+
+    def get_targets(self, cls_scores_list, bbox_preds_list, gt_bboxes_list, gt_labels_list, gt_bboxes_ignore_list=None):
+        """racformer_head.py:354-372"""
+        assert gt_bboxes_ignore_list is None, "Only supports for gt_bboxes_ignore setting to None."
+        ignore = [None] * len(cls_scores_list)
+        labels, label_weights, bbox_targets, bbox_weights, pos, neg = multi_apply(
+            self._get_target_single, cls_scores_list, bbox_preds_list, gt_labels_list, gt_bboxes_list, ignore)
+        return labels, label_weights, bbox_targets, bbox_weights, sum(i.numel() for i in pos), sum(i.numel() for i in neg)
+
+    def loss_single(self, cls_scores, bbox_preds, gt_bboxes_list, gt_labels_list, gt_bboxes_ignore_list=None):
+        """racformer_head.py:374-427: one decoder layer, [B,Q,.] outputs"""
+        num_imgs = cls_scores.size(0)
+        labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = self.get_targets(
+            [cls_scores[i] for i in range(num_imgs)], [bbox_preds[i] for i in range(num_imgs)], gt_bboxes_list, gt_labels_list,
+            gt_bboxes_ignore_list)
+        labels, label_weights = torch.cat(labels_list, 0), torch.cat(label_weights_list, 0)
+        bbox_targets, bbox_weights = torch.cat(bbox_targets_list, 0), torch.cat(bbox_weights_list, 0)
+        cls_scores = cls_scores.reshape(-1, self.cls_out_channels)
+        cls_avg_factor, box_avg_factor = self._avg_factors(num_total_pos * 1.0 + num_total_neg * self.bg_cls_weight, cls_scores)
+        loss_cls = self.loss_cls(cls_scores, labels, label_weights, avg_factor=cls_avg_factor)
+        bbox_preds = bbox_preds.reshape(-1, bbox_preds.size(-1))
+        normalized_bbox_targets = normalize_bbox(bbox_targets)
+        isnotnan = torch.isfinite(normalized_bbox_targets).all(dim=-1)
+        bbox_weights = bbox_weights * self.code_weights
+        loss_bbox = self.loss_bbox(bbox_preds[isnotnan, :10], normalized_bbox_targets[isnotnan, :10], bbox_weights[isnotnan, :10],
+                                   avg_factor=box_avg_factor)
+        return torch.nan_to_num(loss_cls), torch.nan_to_num(loss_bbox)
+
+    def _loss_inputs(self, gt_bboxes_list, gt_labels_list, preds_dicts, gt_bboxes_ignore):
+        assert gt_bboxes_ignore is None, f"{self.__class__.__name__} only supports for gt_bboxes_ignore setting to None."
+        if preds_dicts.get("enc_cls_scores") is not None:
+            raise NotImplementedError("racformer_amd: encoder proposals (enc_cls_scores) have no loss here; the head never emits them")
+        all_cls_scores, all_bbox_preds = preds_dicts["all_cls_scores"], preds_dicts["all_bbox_preds"]
+        device = all_cls_scores.device
+        gt_bboxes_list = [plain_gt_boxes(gt, device) for gt in gt_bboxes_list]
+        gt_labels_list = [lab.to(device) for lab in gt_labels_list]
+        return all_cls_scores, all_bbox_preds, gt_bboxes_list, gt_labels_list
+
+    def loss_unfused(self, gt_bboxes_list, gt_labels_list, preds_dicts, gt_bboxes_ignore=None):
+        """racformer_head.py:429-485 as the reference runs it: per layer and per sample a torch cost matrix, a copy to the host,
+        the host solver, scattered targets, FocalLoss and L1Loss.  Any device and dtype; the comparison of the fused route."""
+        self._require_losses()
+        all_cls_scores, all_bbox_preds, gt_bboxes_list, gt_labels_list = self._loss_inputs(gt_bboxes_list, gt_labels_list, preds_dicts,
+                                                                                           gt_bboxes_ignore)
+        num_dec_layers = len(all_cls_scores)
+        losses_cls, losses_bbox = multi_apply(self.loss_single, all_cls_scores, all_bbox_preds, [gt_bboxes_list] * num_dec_layers,
+                                              [gt_labels_list] * num_dec_layers, [None] * num_dec_layers)
+        loss_dict = dict()
+        if preds_dicts.get("dn_mask_dict") is not None:
+            loss_dict = self.calc_dn_loss(loss_dict, preds_dicts, num_dec_layers)
+        return self._fill_loss_dict(loss_dict, losses_cls, losses_bbox)
+
+    def _fused_loss_applies(self, all_cls_scores, all_bbox_preds, counts):
+        Q = all_cls_scores.shape[2]
+        return all_cls_scores.is_cuda and all_cls_scores.dtype == torch.float32 and all_bbox_preds.dtype == torch.float32 \
+            and all_bbox_preds.shape[-1] == 10 and self.assigner.fusable() and type(self.loss_cls) is FocalLoss \
+            and type(self.loss_bbox) is L1Loss and Q <= 2048 and max(counts, default=0) <= Q and len(counts) <= 64
+
+    def loss(self, gt_bboxes_list, gt_labels_list, preds_dicts, gt_bboxes_ignore=None):
+        """racformer_head.py:429-485 -> {'loss_cls', 'loss_bbox', 'd{i}.loss_cls', 'd{i}.loss_bbox'} and, with denoising queries,
+        the same keys with '_dn'.  gt_bboxes_list: per sample an object with ``.gravity_center`` and ``.tensor`` or a plain [n,9]
+        tensor; gt_labels_list: integer tensors.
+
+        CUDA float32 outputs take the fused route: rac_match_cost_fwd, rac_lsap_fwd and rac_det_loss_fwd once for all layers and
+        samples, rac_det_loss_fwd once more for the denoising rows -- no read-back to the host (the counts of positives are the
+        lengths of the ground-truth lists).  Everything else (CPU, other dtypes, a sample with more boxes than queries, more than
+        2048 queries) takes loss_unfused."""
+        self._require_losses()
+        all_cls_scores, all_bbox_preds, gt_bboxes_list, gt_labels_list = self._loss_inputs(gt_bboxes_list, gt_labels_list, preds_dicts,
+                                                                                           gt_bboxes_ignore)
+        counts = [int(g.shape[0]) for g in gt_bboxes_list]
+        if not self._fused_loss_applies(all_cls_scores, all_bbox_preds, counts):
+            return self.loss_unfused(gt_bboxes_list, gt_labels_list, preds_dicts)
+        from .fused import lsap_fused, match_cost_fused
+        L, B, Q, C = all_cls_scores.shape
+        cls, box = all_cls_scores.contiguous(), all_bbox_preds.contiguous()
+        table = torch.cat(gt_bboxes_list).float().contiguous()
+        labels = torch.cat(gt_labels_list).to(torch.int32)
+        code_weights = self.code_weights.detach().float().contiguous()
+        a = self.assigner
+        if max(counts) > 0:
+            cost = match_cost_fused(cls.detach(), box.detach(), table, labels, counts, code_weights, a.cls_cost.weight, a.reg_cost.weight,
+                                    a.theta_cost.weight if a.polar else None)
+            assigned = lsap_fused(cost, counts, L, Q)[1]
+        else:
+            assigned = torch.full((L * B, Q), -1, device=cls.device, dtype=torch.int32)
+        alpha, gamma = self.loss_cls.alpha, self.loss_cls.gamma
+        sums = head_loss_sums(cls.view(L, B * Q, C), box.view(L, B * Q, 10), assigned.view(L, B * Q), table, labels, code_weights, alpha, gamma)
+        num_total_pos = sum(min(Q, n) for n in counts)
+        cls_avg, box_avg = self._avg_factors(num_total_pos * 1.0 + (B * Q - num_total_pos) * self.bg_cls_weight, cls)
+        losses_cls = torch.nan_to_num(self.loss_cls.loss_weight * (sums[:, 0] / (cls_avg + _EPS32)))
+        losses_bbox = torch.nan_to_num(self.loss_bbox.loss_weight * (sums[:, 1] / (box_avg + _EPS32)))
+        loss_dict = dict()
+        md = preds_dicts.get("dn_mask_dict")
+        if md is not None:
+            known_labels, known_bboxs, dn_cls, dn_box, num_tgt = self.prepare_for_dn_loss(md)
+            total = int(md["batch_idx"].numel())                # row r of a layer belongs to box r mod total (:180-183)
+            dn_sums = head_loss_sums(dn_cls, dn_box, None, known_bboxs[:total].float().contiguous(), known_labels[:total].to(torch.int32),
+                                     code_weights, alpha, gamma)
+            dn_avg = self._avg_factors(num_tgt, cls)[1]
+            dn_cls_l = self.dn_weight * torch.nan_to_num(self.loss_cls.loss_weight * (dn_sums[:, 0] / (dn_avg + _EPS32)))
+            dn_box_l = self.dn_weight * torch.nan_to_num(self.loss_bbox.loss_weight * (dn_sums[:, 1] / (dn_avg + _EPS32)))
+            self._fill_loss_dict(loss_dict, dn_cls_l.unbind(0), dn_box_l.unbind(0), "_dn")
+        return self._fill_loss_dict(loss_dict, losses_cls.unbind(0), losses_bbox.unbind(0))
 
     def get_bboxes(self, preds_dicts, img_metas, rescale=False):
         """racformer_head.py:488-507 (VERSION 'v1.0.0').  Boxes are returned as a plain [n,9] tensor

@@ -53,6 +53,7 @@
  *   rac_bev_sampling_fwd <- BEVSampling keypoints + BEVSelfAttention's MSDA + frame fusion, fused
  *                        models/racformer_transformer.py:490-529, models/bev_self_attention.py:176-213
  *   rac_bev_sampling_bwd <- autograd of the same chain (keypoints, MSDA, frame fusion) in one launch
+ *   rac_bev_sampling_bwd_batch <- the same for B >= 1, with the frame / batch pairing of models/bev_self_attention.py:162-218
  *   rac_sampling4d_bwd <- autograd of RaCFormerSampling.inner_forward + sampling_4d + msmv op in one launch
  *   rac_regroup_bwd / rac_regroup_multi_bwd <- autograd of the regroup's permute().contiguous(), models/racformer_transformer.py:112-124
  *   rac_refine_bwd    <- autograd of refine_bbox + velocity scaling + theta_d2xy_coods (the ops rac_refine_fwd replaces)
@@ -71,7 +72,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 18
+#define RAC_ABI_VERSION 19
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -257,6 +258,25 @@ int rac_bev_sampling_bwd(const void *value, const float *query_bbox, const float
                          int gld_ray, int gld_scale, int gld_queue, int B, int T, int Q, int heads, int NP, int D, int H,
                          int W, int dim, const float *pc_range, const float *depth_base, float d_region, int dtype,
                          void *stream);
+
+/* rac_bev_sampling_bwd for batches: the same arguments and outputs, any B >= 1 (B = 0 is refused), float32 values, dim == 64.
+ * For B > 1 the forward pairs row r = 0 .. B*T-1 of the value frames -- frame and output slot (b_o, t_o) = (r / T, r % T), whose
+ * frame weight and grad_out row it takes -- with the keypoints and point weights of (b_l, t_l) = (r % B, r / B)
+ * (models/bev_self_attention.py:162-218); the gradients of (b_l, q)'s offsets, ray and scale logits and box table collect terms
+ * from several output rows, and the softmax-over-T backward of (b_o, q) the rows of several b_l.  One workgroup takes query
+ * index q of all B samples, so every output except grad_value keeps one writer and a fixed summation order.  time_diff is
+ * [B,T]; the optional debug outputs are indexed by the output slot, as the forward's loc_out.  At B == 1 every output except
+ * grad_value equals rac_bev_sampling_bwd's bit for bit.  Refused before any launch: what rac_bev_sampling_bwd refuses except
+ * B > 1, and B * (heads*T*NP*D) keypoints per query index beyond the 160 KB LDS of a workgroup (about 19 KB per sample at
+ * heads 4, T 8, NP*D 20). */
+int rac_bev_sampling_bwd_batch(const void *value, const float *query_bbox, const float *box_table, const float *offsets,
+                               const float *ray_logits, const float *scale_logits, const float *queue_logits,
+                               const float *time_diff, const float *grad_out, float *grad_value, float *grad_offsets,
+                               float *grad_ray, float *grad_scale, float *grad_queue, float *grad_box, float *grad_loc_out,
+                               float *grad_attn_out, int ld_off, int ld_ray, int ld_scale, int ld_queue, int gld_off,
+                               int gld_ray, int gld_scale, int gld_queue, int B, int T, int Q, int heads, int NP, int D, int H,
+                               int W, int dim, const float *pc_range, const float *depth_base, float d_region, int dtype,
+                               void *stream);
 
 /* The same kernel for the BEV streams of one decoder layer (radar, LSS) in ONE launch: same queries, boxes and time_diff,
  * per stream its own value maps, Linear outputs (same row strides) and output.  HOST arrays of nstreams (1..2) device

@@ -70,6 +70,7 @@ SIGNATURES = {
     "rac_conv3x3s2_fwd": (_i, [_vp] * 4 + [_f, _vp] + [_i] * 7 + [_vp]),
     "rac_bev_sampling_fwd": (_i, [_vp] * 10 + [_i] * 4 + [_i] * 9 + [_vp, _vp, _f, _i, _vp]),
     "rac_bev_sampling_bwd": (_i, [_vp] * 17 + [_i] * 8 + [_i] * 9 + [_vp, _vp, _f, _i, _vp]),
+    "rac_bev_sampling_bwd_batch": (_i, [_vp] * 17 + [_i] * 8 + [_i] * 9 + [_vp, _vp, _f, _i, _vp]),
     "rac_bev_sampling_multi_fwd": (_i, [_i] + [_vp] * 9 + [_i] * 4 + [_i] * 9 + [_vp, _vp, _f, _i, _vp]),
     "rac_bev_sampling_multi_q16_fwd": (_i, [_i] + [_vp] * 10 + [_i] * 4 + [_i] * 9 + [_vp, _vp, _f, _vp]),
     "rac_quant_i16_fwd": (_i, [_vp, _vp, _vp, ctypes.c_int64, _vp]),

@@ -1,6 +1,6 @@
 // bev_device.h -- what the BEV sampling forward (bev_fused.hip) and its backward (bev_fused_bwd.hip) compute alike: the
-// T-invariant base point of a keypoint, the ray-depth offset, the two wave softmaxes and the per-frame warp with its polar
-// jitter.  The backward recomputes the keypoints with these functions instead of reading saved ones, so its locations and
+// T-invariant base point of a keypoint, the ray-depth offset, the two wave softmaxes, the per-frame warp with its polar
+// jitter, and the whole chain from the query box as it is formed for B > 1.  The backward recomputes the keypoints with these functions instead of reading saved ones, so its locations and
 // weights are the forward's own.
 #pragma once
 #include "rac_common.h"
@@ -53,6 +53,37 @@ __device__ __forceinline__ void bev_warp(const float *pc, float px, float py, fl
     const float nx = (px - pc[0]) / sx, ny = (py - pc[1]) / sy;
     const float ex = nx * 102.4f - 51.2f, ey = ny * 102.4f - 51.2f;
     bev_polar_jitter(ex, ey, doff, loc2);
+}
+
+// The whole keypoint chain of one (query, head, point, frame) from the query box itself, as the forward forms it for B > 1
+// (no box table, no T-invariant half: the frame / batch pairing reads another sample's query per frame).  qb: the query's
+// [10] row, o: the point's two offsets, td: the frame's time difference.  The rotation's two multiply-adds are written out with
+// contraction off, for the reason given at bev_base_point: this is the form the forward kernel was compiled to.
+__device__ __forceinline__ void bev_keypoint_from_query(const float *pc, const float *qb, const float *o, float ray_logit, float td,
+                                                        float depth_base, float d_region, int D, float *loc2)
+{
+    const float sx = pc[3] - pc[0], sy = pc[4] - pc[1];
+    const float ang0 = qb[0] * BEV_TWO_PI, rad0 = qb[1] * 65.0f;
+    const float xn0 = fminf(fmaxf((51.2f + rad0 * cosf(ang0)) / 102.4f, 0.f), 1.f);
+    const float yn0 = fminf(fmaxf((51.2f + rad0 * sinf(ang0)) / 102.4f, 0.f), 1.f);
+    const float cx = xn0 * sx + pc[0], cy = yn0 * sy + pc[1];
+    const float yaw = atan2f(qb[6], qb[7]);
+    const float cs = cosf(yaw), sn = sinf(yaw);
+    const float dx = expf(qb[3]) * o[0], dy = expf(qb[4]) * o[1];
+    float rx, ry;
+    {
+#pragma clang fp contract(off)
+        rx = __builtin_fmaf(dx, cs, -(dy * sn));
+        ry = __builtin_fmaf(dx, sn, dy * cs);
+    }
+    float px = cx + rx;
+    float py = cy + ry;
+    px -= qb[8] * td;
+    py -= qb[9] * td;
+    const float nx = (px - pc[0]) / sx, ny = (py - pc[1]) / sy;
+    const float ex = nx * 102.4f - 51.2f, ey = ny * 102.4f - 51.2f;
+    const float sg = 1.f / (1.f + expf(-ray_logit));
+    bev_polar_jitter(ex, ey, depth_base + (sg * 2.f - 1.f) * d_region / (float)D / 2.f, loc2);
 }
 
 __device__ __forceinline__ float bev_wave_max(float v)

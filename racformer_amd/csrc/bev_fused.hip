@@ -16,7 +16,8 @@
 // keypoints per item).  Phase C: per frame 20 points unrolled by 4 (16 taps in flight), scaled by
 // the frame weight.  Phase D: fixed-order LDS sum of the four point subsets (deterministic).
 // For B>1 the reference pairs value frame i=b*T+t with the locations of (t'=i/B, b'=i%B)
-// (bev_self_attention.py:185-188 vs :162,173, quirk Q2); reproduced as written.
+// (bev_self_attention.py:185-188 vs :162,173, quirk Q2); reproduced as written.  Its keypoints come from
+// bev_keypoint_from_query (bev_device.h), which rac_bev_sampling_bwd_batch recomputes them with.
 #include "bev_device.h"
 
 #define BEV_MAX_STREAMS 2
@@ -53,25 +54,10 @@ struct BevArgs {
 __device__ __forceinline__ void bev_keypoint(const BevArgs &a, const BevStream &s, int bq, int tq, int q, int h, int p, float *loc2)
 {
     const float *qb = a.qbox + ((size_t)bq * a.Q + q) * 10;
-    const float sx = a.pc[3] - a.pc[0], sy = a.pc[4] - a.pc[1];
-    const float ang0 = qb[0] * BEV_TWO_PI, rad0 = qb[1] * 65.0f;
-    const float xn0 = fminf(fmaxf((51.2f + rad0 * cosf(ang0)) / 102.4f, 0.f), 1.f);
-    const float yn0 = fminf(fmaxf((51.2f + rad0 * sinf(ang0)) / 102.4f, 0.f), 1.f);
-    const float cx = xn0 * sx + a.pc[0], cy = yn0 * sy + a.pc[1];
-    const float yaw = atan2f(qb[6], qb[7]);
-    const float cs = cosf(yaw), sn = sinf(yaw);
     const float *o = s.off + ((size_t)bq * a.Q + q) * a.ld_off + ((size_t)h * a.P + p) * 2;
-    const float dx = expf(qb[3]) * o[0], dy = expf(qb[4]) * o[1];
-    float px = cx + (dx * cs - dy * sn);
-    float py = cy + (dx * sn + dy * cs);
-    const float td = a.time_diff[bq * a.T + tq];
-    px -= qb[8] * td;
-    py -= qb[9] * td;
-    const float nx = (px - a.pc[0]) / sx, ny = (py - a.pc[1]) / sy;
-    const float ex = nx * 102.4f - 51.2f, ey = ny * 102.4f - 51.2f;
     const int dd = p % a.D;
-    const float sg = 1.f / (1.f + expf(-s.ray[((size_t)bq * a.Q + q) * a.ld_ray + dd]));
-    bev_polar_jitter(ex, ey, a.depth_base[dd] + (sg * 2.f - 1.f) * a.d_region / (float)a.D / 2.f, loc2);
+    bev_keypoint_from_query(a.pc, qb, o, s.ray[((size_t)bq * a.Q + q) * a.ld_ray + dd], a.time_diff[bq * a.T + tq], a.depth_base[dd],
+                            a.d_region, a.D, loc2);
 }
 
 #ifndef BEV_U

@@ -202,14 +202,27 @@ def bev_sampling_fused(value, hw, query_bbox, offsets, ray_logits, scale_logits,
     return (out, loc_out) if debug else out
 
 
+BEV_BWD_LDS_LIMIT = 160 * 1024
+
+
+def bev_backward_batch_fits(B, num_heads, num_frames, points):
+    """Whether rac_bev_sampling_bwd_batch accepts a batch of B: its workgroup stages a query index of all B samples in LDS
+    (bev_bwd_batch_lds_floats in bev_fused_bwd.hip; tests/test_bev_sampling_batch_grad_cpu.py holds the two together)."""
+    per_sample = num_heads * num_frames * points * 6 + num_heads * points * 8 + num_heads * 64 + num_frames * 3 + 16 * 2 + 16
+    return B >= 1 and num_frames <= 64 and points <= 64 and 4 * B * per_sample <= BEV_BWD_LDS_LIMIT
+
+
 def bev_sampling_backward(value, hw, query_bbox, offsets, ray_logits, scale_logits, queue_logits, time_diff, grad_out,
                           num_frames, num_heads, num_points, depth_num, pc_range, d_region, box_table=None, grad_offsets=None,
-                          grad_ray=None, grad_scale=None, grad_queue=None, debug=False):
-    """Backward of bev_sampling_fused (rac_bev_sampling_bwd): the forward's arguments and grad_out [B,Q,heads*64] ->
+                          grad_ray=None, grad_scale=None, grad_queue=None, debug=False, batch_symbol=None):
+    """Backward of bev_sampling_fused (rac_bev_sampling_bwd at B == 1, rac_bev_sampling_bwd_batch at B > 1, which reproduces the
+    forward's frame / batch pairing): the forward's arguments and grad_out [B,Q,heads*64] ->
     (grad_value [B*T,H*W,heads,64], grad_offsets, grad_ray, grad_scale, grad_queue, grad_box [B,Q,8]); with ``debug`` also
     the kernel's per-keypoint gradients (grad_loc [B,Q,heads,T,P,2], grad_attn [B,Q,heads,T,P]).  ``grad_offsets`` ..
     ``grad_queue``: destinations with unit inner stride and a row stride of their own (column slices of one gradient of a
-    fused Linear output); allocated when not given.  Every element of them is written.  float32 values and B == 1 only."""
+    fused Linear output); allocated when not given.  Every element of them is written.  float32 values only; a batch whose
+    keypoints exceed a workgroup's LDS is refused (RuntimeError).  ``batch_symbol``: True / False picks the entry point whatever
+    B is (the tests compare the two at B == 1)."""
     _lib.require_gpu(value, query_bbox, time_diff, grad_out, what="bev_sampling_backward")
     B, Q, _ = query_bbox.shape
     T, Hn, NP, D = num_frames, num_heads, num_points, depth_num
@@ -245,7 +258,8 @@ def bev_sampling_backward(value, hw, query_bbox, offsets, ray_logits, scale_logi
     ev = _lib.timer.record("bev_sampling_bwd") if _lib.timer is not None else None
     if ev:
         ev[0].record()
-    rc = _lib.lib().rac_bev_sampling_bwd(
+    symbol = "rac_bev_sampling_bwd_batch" if (B != 1 if batch_symbol is None else batch_symbol) else "rac_bev_sampling_bwd"
+    rc = getattr(_lib.lib(), symbol)(
         _lib.ptr(value), _lib.ptr(query_bbox), _lib.ptr(box_table), p_off, p_ray, p_sc, p_qu, _lib.ptr(time_diff),
         _lib.ptr(grad_out), _lib.ptr(grad_value), p_goff, p_gray, p_gsc, p_gqu, _lib.ptr(grad_box),
         _lib.ptr(grad_loc) if debug else None, _lib.ptr(grad_attn) if debug else None, ld_off, ld_ray, ld_sc, ld_qu,
@@ -253,7 +267,7 @@ def bev_sampling_backward(value, hw, query_bbox, offsets, ray_logits, scale_logi
         code, _lib.stream_ptr())
     if ev:
         ev[1].record()
-    _lib.check(rc, "rac_bev_sampling_bwd")
+    _lib.check(rc, symbol)
     res = (grad_value, grad_offsets, grad_ray, grad_scale, grad_queue, grad_box)
     return res + (grad_loc, grad_attn) if debug else res
 

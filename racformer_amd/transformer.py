@@ -28,8 +28,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .bbox_utils import decode_bbox, inverse_sigmoid, theta_d2xy_coods, xy2theta_d_coods
-from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_sampling_backward, bev_sampling_fused,
-                    bev_sampling_multi_fused,
+from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, bev_backward_batch_fits, bev_sampling_backward,
+                    bev_sampling_fused, bev_sampling_multi_fused,
                     box_prep, conv_direct, quantize_values_i16, upsample2x_image,
                     generator_fused, gru_gate_fused, layer_boundary_fused, mixing_backward, mixing_fused, outproj_fused,
                     pack_conv3x3_weight,
@@ -379,8 +379,9 @@ class _BEVSamplingCore(torch.autograd.Function):
     """The BEVSampling core: apply(value [B*T,H*W,heads,64], lin_off, lin_ray, lin_sc, lin_qu (the four Linear outputs),
     query_ray [B,Q,10], box_graph, box_table, time_diff, hw, T, heads, NP, D, pc_range, d_region) -> [B,Q,heads*64] before
     output_proj.  The forward is bev_sampling_fused exactly as BEVSampling.attend_prepared calls it under no_grad (same
-    kernels, same arguments: ``box_table`` is the caller's table or None); the backward rac_bev_sampling_bwd, which recomputes
-    the keypoints, so only the inputs are saved.  ``box_graph``: box_table_torch(query_ray) when the boxes need a gradient, else
+    kernels, same arguments: ``box_table`` is the caller's table or None); the backward rac_bev_sampling_bwd (B > 1:
+    rac_bev_sampling_bwd_batch, with the forward's frame / batch pairing), which recomputes the keypoints, so only the inputs
+    are saved.  ``box_graph``: box_table_torch(query_ray) when the boxes need a gradient, else
     None -- the kernels never read it; it receives grad_box, and plain autograd carries that on to query_ray (components 0, 1,
     3, 4, 6, 7, as in the reference; the velocity is detached there).  The launchers are looked up as this module's globals at
     call time."""
@@ -994,11 +995,14 @@ class BEVSampling(nn.Module):
         mods = [self.attention.value_proj, self.positional_encoding] + ([self.temporal_encoder] if self.temp_radar else [])
         return any(_records_grad(m, bev_feats) for m in mods)
 
-    def attend_prepared(self, query_ray, query_feat, value, hw, time_diff, d_region, linear_out=None, box_table=None):
+    def attend_prepared(self, query_ray, query_feat, value, hw, time_diff, d_region, linear_out=None, box_table=None,
+                        fused_batch=False):
         """One fused HIP kernel (rac_bev_sampling_fwd) + output_proj + identity.  When autograd is recording and the value
         stream, the queries, the boxes or a parameter requires grad: through _BEVSamplingCore (the same forward kernel, and
         rac_bev_sampling_bwd behind it) where the fused backward applies -- float32 values, B == 1 -- and through
-        forward_unfused otherwise (B > 1: the reference's frame / batch pairing; bf16 and int16 value streams)."""
+        forward_unfused otherwise (B > 1: the reference's frame / batch pairing; bf16 and int16 value streams).
+        ``fused_batch``: B > 1 takes _BEVSamplingCore too (rac_bev_sampling_bwd_batch, which reproduces the pairing), where its
+        workgroup's LDS holds the batch; the decoder layer's training route asks for it."""
         given = linear_out is not None
         if not given:
             linear_out = (self.sampling_offset(query_feat), self.ray_points_offset(query_feat),
@@ -1011,7 +1015,9 @@ class BEVSampling(nn.Module):
             if not plain:
                 raise RuntimeError("BEVSampling.attend_prepared: an int16 block-stored value stream has no gradient path; "
                                    "prepare the value stream in float32 under autograd")
-            if query_ray.shape[0] != 1 or value.dtype != torch.float32 or value.shape[-1] != 64:
+            B = query_ray.shape[0]
+            batch_ok = fused_batch and bev_backward_batch_fits(B, self.num_heads, self.num_frames, self.num_points * self.depth_num)
+            if not (B == 1 or batch_ok) or value.dtype != torch.float32 or value.shape[-1] != 64:
                 return self.forward_unfused(query_ray, query_feat, value, hw, time_diff, d_region, linear_out=linear_out if given else None)
             box_graph = box_table_torch(query_ray, self.pc_range) if query_ray.requires_grad else None
             fused = _BEVSamplingCore.apply(value, off, ray, sc, qu, query_ray.contiguous(), box_graph, box_table, time_diff, hw,
@@ -1629,7 +1635,7 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
     def forward_train(self, query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, layer, prepared, stages=None):
         """The layer as a composition of its modules with torch layers around them (racformer_transformer.py:239-279): the
         training route.  Every heavy module takes its own autograd Function where a gradient is wanted -- _SASACore,
-        _BEVSamplingCore (forward_unfused for B > 1), _Sampling4DCore, _MixingCore, _RefineCore, each a fused HIP forward with a
+        _BEVSamplingCore (at B > 1 too: fused_batch), _Sampling4DCore, _MixingCore, _RefineCore, each a fused HIP forward with a
         fused HIP backward --, the eleven 256 -> . Linears are ONE F.linear over the wide operand (concatenated from the live
         parameters by prepare_train, so each of the eleven weights and biases receives its gradient), the norms, fusion, FFN
         and the cls / reg branches are torch modules.  One rac_box_prep_fwd table serves the three sampling modules; where
@@ -1646,9 +1652,9 @@ class RaCFormerTransformerDecoderLayer(nn.Module):
         qb = query_bbox.contiguous()
         table = box_prep(qb, self.pc_range)       # decode_bbox(theta_d2xy(.)) once for the 3 sampling kernels
         radar_raw = self.sampling_radar_bev.attend_prepared(qb, query_feat, prepared["radar_value"],
-                                                            prepared["radar_hw"], time_diff, d_region, lin[3:7], table)
+                                                            prepared["radar_hw"], time_diff, d_region, lin[3:7], table, fused_batch=True)
         lss_raw = self.sampling_lss_bev.attend_prepared(qb, query_feat, prepared["lss_value"],
-                                                        prepared["lss_hw"], time_diff, d_region, lin[7:11], table)
+                                                        prepared["lss_hw"], time_diff, d_region, lin[7:11], table, fused_batch=True)
         sampled_feat = self._sample(qb, query_feat, mlvl_feats, img_metas, d_region, lin[0:3], table)
         query_radar_feat = self.norm_radar_bev(radar_raw)
         query_lss_feat = self.norm_lss_bev(lss_raw)

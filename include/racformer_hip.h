@@ -72,7 +72,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 19
+#define RAC_ABI_VERSION 20
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -441,6 +441,14 @@ enum {
 int rac_mixing_fwd(const float *x, const float *params, float param_scale, float *out, void *out_split,
                    float split_scale, int ld_params, int num_query, int groups, int in_points, int channels, int out_points,
                    float eps, int mfma_mode, void *stream);
+
+/* rac_mixing_fwd with a parameter row period: item row q reads the parameter row at params + (q % period)*ld_params.  For
+ * item rows whose parameters repeat -- B batch elements generated from the same queries -- the parameter block is held
+ * once ([period] rows) instead of B times.  period divides num_query; period == num_query is rac_mixing_fwd, address for
+ * address.  Every other argument as for rac_mixing_fwd. */
+int rac_mixing_period_fwd(const float *x, const float *params, float param_scale, float *out, void *out_split,
+                          float split_scale, int ld_params, int period, int num_query, int groups, int in_points, int channels,
+                          int out_points, float eps, int mfma_mode, void *stream);
 
 /* Backward of rac_mixing_fwd in RAC_MIX_F32 mode with param_scale 1 (the training forward): given dZ, the gradients in x and
  * in the generated parameters.  x, params, ld_params, num_query, groups, in_points, channels, out_points, eps: as given to

@@ -46,6 +46,7 @@ SIGNATURES = {
     "rac_refine_bwd": (_i, [_vp] * 7 + [_i] * 3 + [_f, _vp]),
     "rac_head_finish_fwd": (_i, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _i, _vp, _vp]),
     "rac_mixing_fwd": (_i, [_vp, _vp, _f, _vp, _vp, _f] + [_i] * 6 + [_f, _i, _vp]),
+    "rac_mixing_period_fwd": (_i, [_vp, _vp, _f, _vp, _vp, _f] + [_i] * 7 + [_f, _i, _vp]),
     "rac_mixing_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp] + [_i] * 5 + [_f, _vp]),
     "rac_sasa_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp, _vp]),
     "rac_sasa_fwd_ex": (_i, [_vp] * 6 + [_i] * 6 + [_vp, _vp]),

@@ -31,10 +31,11 @@ typedef float mix_f4 __attribute__((ext_vector_type(4)));
 
 struct MixArgs {
     const float *x;       // [items_q, G, P, 64]
-    const float *params;  // row q at params + q*ld_params: per group [64*64 | 128*P]
+    const float *params;  // row q at params + (q % period)*ld_params: per group [64*64 | 128*P]
     float *out;           // [items_q, G, 128, 64] (may be null when out_split is given)
     _Float16 *out_split;  // optional: f16 [items_q, G*256, hi 32 | lo 32] = the line image of out * split_scale (rac_outproj_fwd's A operand)
     int nq, G, P, ld_params;
+    int period;           // parameter row period: nq (one row per item row), or a divisor of it (rows shared by batch elements)
     float eps, split_scale;
     float param_scale;    // every generated parameter is multiplied by this on load (the split GEMM's power-of-two alpha)
 };
@@ -114,7 +115,7 @@ __device__ __forceinline__ void mix_f32_core(const MixArgs &a, float *smem, int 
     const int PP = MIX_PMAX;        // rows / K are always padded to 96 with zeros: branch-free MFMA loops
     (void)MT;
     const float *gx = a.x + ((size_t)q * a.G + g) * P * MIX_C;
-    const float *gM = a.params + (size_t)q * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
+    const float *gM = a.params + (size_t)(q % a.period) * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
     const float *gS = gM + MIX_C * MIX_C;
 
     // ---- stage x (zero rows up to PP), M and S half 0 -------------------------------------------
@@ -339,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
     float *sS = smem + MIX_REGION_A;                    // [64][100]
     float *red = sS + 64 * MIX_SS;
     const size_t item_off = (size_t)q * a.G + g;
-    const float *gM = a.params + (size_t)q * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
+    const float *gM = a.params + (size_t)(q % a.period) * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
     const float *gS = gM + MIX_C * MIX_C;
     const float *gdz = b.grad_out + item_off * MIX_OUT * MIX_C;
     float *gdM = b.grad_params + (size_t)q * b.ld_grad_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
@@ -618,7 +619,7 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     const int item = RAC_MIX_REVERSE ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
     const int q = item / a.G, g = item % a.G;
     const float *gx = a.x + ((size_t)q * a.G + g) * P * MIX_C;
-    const float *gM = a.params + (size_t)q * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
+    const float *gM = a.params + (size_t)(q % a.period) * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
     const float *gS = gM + MIX_C * MIX_C;
     const float ps = a.param_scale;
 
@@ -802,9 +803,10 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     mix_write_out(a, sO, q, g, tid);
 }
 
-extern "C" int rac_mixing_fwd(const float *x, const float *params, float param_scale, float *out, void *out_split,
-                              float split_scale, int ld_params, int num_query, int groups, int in_points, int channels, int out_points,
-                              float eps, int mfma_mode, void *stream)
+// rac_mixing_fwd with a parameter row period: item row q reads parameter row q % period (period == num_query: one row each).
+extern "C" int rac_mixing_period_fwd(const float *x, const float *params, float param_scale, float *out, void *out_split,
+                                     float split_scale, int ld_params, int period, int num_query, int groups, int in_points,
+                                     int channels, int out_points, float eps, int mfma_mode, void *stream)
 {
     RAC_CHECK_ARG(mfma_mode == RAC_MIX_F32 || mfma_mode == RAC_MIX_F16X3, "rac_mixing_fwd: mfma_mode=%d", mfma_mode);
     RAC_CHECK_ARG(channels == MIX_C && out_points == MIX_OUT,
@@ -814,6 +816,8 @@ extern "C" int rac_mixing_fwd(const float *x, const float *params, float param_s
     RAC_CHECK_ARG(ld_params >= groups * (MIX_C * MIX_C + MIX_OUT * in_points) && ld_params % 4 == 0 &&
                       (MIX_C * MIX_C + MIX_OUT * in_points) % 4 == 0,
                   "rac_mixing_fwd: parameter row stride %d", ld_params);
+    RAC_CHECK_ARG(num_query == 0 || (period >= 1 && period <= num_query && num_query % period == 0),
+                  "rac_mixing_period_fwd: parameter row period %d does not divide %d rows", period, num_query);
     static_assert(MIX_REGION_A >= MIX_OUT * MIX_C, "output tile must fit region A");
     static_assert(MIX_REGION_A >= MIX_PMAX * MIX_MS, "Y must fit region A");
     if (num_query == 0)
@@ -823,6 +827,7 @@ extern "C" int rac_mixing_fwd(const float *x, const float *params, float param_s
     a.x = x; a.params = params; a.out = out;
     a.out_split = reinterpret_cast<_Float16 *>(out_split); a.split_scale = split_scale; a.param_scale = param_scale;
     a.nq = num_query; a.G = groups; a.P = in_points; a.ld_params = ld_params; a.eps = eps;
+    a.period = period;
     const size_t lds = (size_t)MIX_LDS_FLOATS * sizeof(float);
     if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_MIXING_F32, reinterpret_cast<const void *>(mixing_c64_kernel), (int)((int)lds)))
         return rc_attr;
@@ -837,6 +842,15 @@ extern "C" int rac_mixing_fwd(const float *x, const float *params, float param_s
     }
     hipLaunchKernelGGL(mixing_c64_kernel, dim3(num_query * groups), dim3(256), lds, (hipStream_t)stream, a);
     return rac_launch_status("rac_mixing_fwd");
+}
+
+extern "C" int rac_mixing_fwd(const float *x, const float *params, float param_scale, float *out, void *out_split,
+                              float split_scale, int ld_params, int num_query, int groups, int in_points, int channels, int out_points,
+                              float eps, int mfma_mode, void *stream)
+{
+    // (period = max(num_query, 1): one parameter row per item row, and the size checks keep their own messages)
+    return rac_mixing_period_fwd(x, params, param_scale, out, out_split, split_scale, ld_params, num_query > 0 ? num_query : 1,
+                                 num_query, groups, in_points, channels, out_points, eps, mfma_mode, stream);
 }
 
 extern "C" int rac_mixing_bwd(const float *x, const float *params, int ld_params, const float *grad_out, float *grad_x,
@@ -861,6 +875,7 @@ extern "C" int rac_mixing_bwd(const float *x, const float *params, int ld_params
     memset(&b, 0, sizeof(b));
     b.f.x = x; b.f.params = params; b.f.param_scale = 1.f;
     b.f.nq = num_query; b.f.G = groups; b.f.P = in_points; b.f.ld_params = ld_params; b.f.eps = eps;
+    b.f.period = num_query;
     b.grad_out = grad_out; b.grad_x = grad_x; b.grad_params = grad_params; b.z_out = z_out; b.ld_grad_params = ld_grad_params;
     const size_t lds = (size_t)MIX_LDS_FLOATS * sizeof(float);
     if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_MIXING_BWD, reinterpret_cast<const void *>(mixing_c64_bwd_kernel), (int)lds))

@@ -460,20 +460,28 @@ def sasa_backward(qkv, tau, query_bbox, num_heads, pc_range, out, lse, grad_out,
     return grad_qkv, grad_tau
 
 
-def mixing_fused(x, params, in_points, n_groups, out_points=128, eps=1e-5, split=False, param_scale=1.0, f16x3=False, out=None):
+def mixing_fused(x, params, in_points, n_groups, out_points=128, eps=1e-5, split=False, param_scale=1.0, f16x3=False, out=None,
+                 period=None):
     """x [B,Q,G,P,64] (contiguous), params [B,Q,G*(64*64+128*P)] (unit inner stride) ->
     relu(LN(S @ relu(LN(x @ M)))) as [B,Q,G*128*64], ready for out_proj.
     ``split=True``: instead returns the f16 line image [B*Q, G*256, hi 32 | lo 32] of the same values * SPLIT_ACT_SCALE
     (A operand of rac_outproj_fwd: every value stored once as hi + lo).
     ``param_scale``: factor applied to every parameter on load (the power-of-two alpha of a split generator GEMM).
     ``f16x3``: run the two products as 3-product split-precision f16 MFMAs (RAC_MIX_F16X3) instead of f32-input MFMAs.
-    ``out``: write into this tensor (a row range of a larger image) instead of allocating."""
+    ``out``: write into this tensor (a row range of a larger image) instead of allocating.
+    ``period``: params holds ``period`` rows (a divisor of B*Q) and item row r reads row r % period (rac_mixing_period_fwd):
+    the parameters of batch elements generated from the same queries, held once."""
     _lib.require_gpu(x, what="mixing_fused")
     B, Q, G, P, C = x.shape
     if G != n_groups or P != in_points or x.dtype != torch.float32:
         raise RuntimeError("mixing_fused: x must be float32 [B,Q,G,P,64]")
     width = G * (C * C + out_points * P)
     p_par, ld_par = _rows(params, width, "mixing_fused(params)")
+    rows = params.numel() // params.shape[-1]
+    if period is None:
+        period = B * Q
+    if period < 1 or (B * Q) % period != 0 or rows != period or params.dtype != torch.float32:
+        raise RuntimeError(f"mixing_fused: params must be float32 with {period} rows (a divisor of {B * Q}), got {rows}")
     if out is not None:
         want = ((B * Q, G * out_points * C // 32, 64), torch.float16) if split else ((B, Q, G * out_points * C), torch.float32)
         if tuple(out.shape) != want[0] or out.dtype != want[1] or not out.is_contiguous() or not out.is_cuda:
@@ -485,10 +493,13 @@ def mixing_fused(x, params, in_points, n_groups, out_points=128, eps=1e-5, split
     ev = _lib.timer.record("mixing_fwd") if _lib.timer is not None else None
     if ev:
         ev[0].record()
-    rc = _lib.lib().rac_mixing_fwd(_lib.ptr(x), p_par, float(param_scale), None if split else _lib.ptr(out),
-                                   _lib.ptr(out) if split else None,
-                                   SPLIT_ACT_SCALE, ld_par, B * Q, G, P, C, out_points, float(eps),
-                                   _lib.MIX_F16X3 if f16x3 else _lib.MIX_F32, _lib.stream_ptr())
+    head = (_lib.ptr(x), p_par, float(param_scale), None if split else _lib.ptr(out), _lib.ptr(out) if split else None,
+            SPLIT_ACT_SCALE, ld_par)
+    tail = (B * Q, G, P, C, out_points, float(eps), _lib.MIX_F16X3 if f16x3 else _lib.MIX_F32, _lib.stream_ptr())
+    if period != B * Q:
+        rc = _lib.lib().rac_mixing_period_fwd(*head, int(period), *tail)
+    else:
+        rc = _lib.lib().rac_mixing_fwd(*head, *tail)
     if ev:
         ev[1].record()
     _lib.check(rc, "rac_mixing_fwd")

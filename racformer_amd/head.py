@@ -137,15 +137,13 @@ class RaCFormer_head(nn.Module):
         grid = torch.stack(torch.meshgrid(theta, rng, indexing="ij"), dim=-1)       # [rays, clusters, 2]
         return grid.reshape(-1, 2)
 
-    def forward(self, mlvl_feats, lss_bev_feats, radar_bev_feats, img_metas):
-        """racformer_head.py:82-134.  Eval mode: the eval branch of prepare_for_dn_input (:142-145, :241-245) with cached initial
-        queries and the fused output tail.  Training mode: forward_training."""
-        if self.training:
-            return self.forward_training(mlvl_feats, lss_bev_feats, radar_bev_feats, img_metas)
-        B = lss_bev_feats.shape[0]
+    def eval_queries(self, B):
+        """The eval branch of prepare_for_dn_input (:142-145, :241-245) -> (query_bbox [B,Q,10], query_feat [B,Q,E], query_key).
+        The initial queries depend on the embeddings only: built once per (weights, batch size) in eval, not per forward (four
+        small launches per step otherwise); the decoder never writes into its inputs.  ``query_key`` names exactly these cached
+        tensors -- the key under which the decoder's layer 0 keeps what it computes from them alone
+        (RaCFormerTransformerDecoderLayer.layer0_block); None while autograd is recording (fresh tensors, nothing is cached)."""
         Q = self.num_query
-        # the initial queries depend on the embeddings only: built once per (weights, batch size) in eval, not per forward
-        # (four small launches per step otherwise); the decoder never writes into its inputs
         wq, wl = self.init_query_bbox.weight, self.label_enc.weight
         sig = (wq.data_ptr(), wq._version, wl.data_ptr(), wl._version, str(wq.device), B)
         hit = getattr(self, "_init_queries", None)
@@ -157,19 +155,27 @@ class RaCFormer_head(nn.Module):
                 self._init_queries = (sig, query_bbox, query_feat)
         else:
             _, query_bbox, query_feat = hit
+        return query_bbox, query_feat, (("init_queries",) + sig if not torch.is_grad_enabled() else None)
+
+    def forward(self, mlvl_feats, lss_bev_feats, radar_bev_feats, img_metas):
+        """racformer_head.py:82-134.  Eval mode: the eval branch of prepare_for_dn_input (:142-145, :241-245) with cached initial
+        queries and the fused output tail.  Training mode: forward_training."""
+        if self.training:
+            return self.forward_training(mlvl_feats, lss_bev_feats, radar_bev_feats, img_metas)
+        query_bbox, query_feat, query_key = self.eval_queries(lss_bev_feats.shape[0])
         pc = self.pc_range
         if lss_bev_feats.is_cuda and self.code_size == 10 and not torch.is_grad_enabled():
             # nan_to_num of both outputs, the centre's scaling to metres and the column reorder: one HIP launch instead of five
             from .fused import head_finish_fused
             cls_scores, bbox_xy = self.transformer(query_bbox, query_feat, mlvl_feats, lss_bev_feats, radar_bev_feats,
-                                                   attn_mask=None, img_metas=img_metas, raw=True)
+                                                   attn_mask=None, img_metas=img_metas, raw=True, query_key=query_key)
             if cls_scores.dtype == torch.float32 and bbox_xy.dtype == torch.float32:
                 cls_scores, bbox_preds = head_finish_fused(cls_scores.contiguous(), bbox_xy.contiguous(), pc)
                 return {"all_cls_scores": cls_scores, "all_bbox_preds": bbox_preds, "enc_cls_scores": None, "enc_bbox_preds": None}
             cls_scores, bbox_preds = torch.nan_to_num(cls_scores), torch.nan_to_num(bbox_xy)
         else:
             cls_scores, bbox_preds = self.transformer(query_bbox, query_feat, mlvl_feats, lss_bev_feats,
-                                                      radar_bev_feats, attn_mask=None, img_metas=img_metas)
+                                                      radar_bev_feats, attn_mask=None, img_metas=img_metas, query_key=query_key)
         lo = const_tensor(bbox_preds, pc[0:3])
         span = const_tensor(bbox_preds, [pc[3] - pc[0], pc[4] - pc[1], pc[5] - pc[2]])
         xyz = bbox_preds[..., 0:3] * span + lo

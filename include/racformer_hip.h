@@ -50,6 +50,8 @@
  *                        models/racformer_transformer.py:705-720, :633-636
  *   rac_absmax_fwd / rac_conv_pack_fwd / rac_conv3x3_fwd <- RadarBEVTemporalEncoder.temporal_fusion (nn.Conv2d 3x3)
  *                        models/racformer_transformer.py:631,655
+ *   rac_conv_pack_cl_fwd / rac_conv3x3_wgrad <- autograd of the same convolution: the data gradient is rac_conv3x3_fwd on an
+ *                        image of the output gradient with transposed, flipped weights; the weight gradient is a kernel of its own
  *   rac_bev_sampling_fwd <- BEVSampling keypoints + BEVSelfAttention's MSDA + frame fusion, fused
  *                        models/racformer_transformer.py:490-529, models/bev_self_attention.py:176-213
  *   rac_bev_sampling_bwd <- autograd of the same chain (keypoints, MSDA, frame fusion) in one launch
@@ -72,7 +74,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 20
+#define RAC_ABI_VERSION 21
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -726,6 +728,26 @@ int rac_upsample2x_image_fwd(const float *src, void *img, int frames, int h, int
 int rac_conv3x3_temporal_fwd(const void *xs, const void *ws, const float *pixel_bias_live, const float *pixel_bias_dead,
                              const float *amax, float w_alpha, float *out, void *q, float *scale, int N, int H, int W, int Cin,
                              int Cin_dead, int frames_per_group, int live_per_group, void *stream);
+
+/* ---- backward of the 3x3 / stride 1 / pad 1 convolution of rac_conv3x3_fwd (the temporal-fusion convolution under autograd) ----
+ * Same arithmetic as the forward: hi / lo split operands, three f16 MFMA products, fp32 accumulate.
+ *
+ * Data gradient: dX = conv3x3(dY, W') with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx] is rac_conv3x3_fwd itself (bias NULL) on
+ * an activation image of dY (256 channels, its scale from rac_absmax_fwd) and a weight image packed from W'
+ * (racformer_amd.fused.pack_conv3x3_dgrad_weight: 256 input channels of W at a time, zero output columns where fewer remain).
+ *
+ *   rac_conv_pack_cl_fwd  rac_conv_pack_fwd for a channel-LAST source: src [N,H,W,C] f32 (contiguous, 16-byte aligned) -> channel
+ *                         range [c_offset, c_offset+C) of the image xs f16 [N][H+2][W+2][c_total/32][hi 32 | lo 32] (interior
+ *                         pixels; the border must be zero).  C, c_total, c_offset multiples of 32.
+ *   rac_conv3x3_wgrad     dw [256][Cin][3][3] f32 = sum_{n,h,w} dY[n,co,h,w] X[n,ci,h+ky-1,w+kx-1] from the two images
+ *                         xs (X: Cin channels, scale amax_x) and gs (dY: 256 channels, scale amax_g).  The N*H image rows are
+ *                         split into k_splits contiguous ranges (1 <= k_splits <= N*H) whose partial sums go to
+ *                         workspace [k_splits][9][256][Cin] f32 and are added in ascending order by a second launch: no float
+ *                         atomics, bitwise reproducible for equal k_splits.  Cin a multiple of 32, Cout == 256, any H, W. */
+int rac_conv_pack_cl_fwd(const float *src, const float *amax, void *xs, int N, int C, int H, int W, int c_total, int c_offset,
+                         void *stream);
+int rac_conv3x3_wgrad(const void *xs, const void *gs, const float *amax_x, const float *amax_g, float *workspace, float *dw, int N,
+                      int H, int W, int Cin, int Cout, int k_splits, void *stream);
 
 /* ---- the head loss: match costs, assignment, focal + L1 (batched over P = num_layers * batch problems) ----
  * Ground truth: ONE concatenated table gt_boxes [sum G, 9] (x, y, z, w, l, h, yaw, vx, vy; gravity centre), gt_labels [sum G]

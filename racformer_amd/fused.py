@@ -778,6 +778,44 @@ def pack_conv3x3_weight(weight, cout=256):
     return torch.stack([hi, lo], dim=3).contiguous(), 2.0 ** (-s)
 
 
+def conv3x3_dgrad_weight(weight):
+    """The weights of the data gradient of a 3x3 / stride 1 / pad 1 convolution, itself such a convolution of the output gradient:
+    W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx].  weight [Cout, Cin, 3, 3] -> [Cin, Cout, 3, 3]."""
+    return weight.detach().flip(2, 3).transpose(0, 1).contiguous()
+
+
+def pack_conv3x3_dgrad_weight(weight, c0=0, cout=256):
+    """pack_conv3x3_weight of the rows [c0, c0 + cout) of conv3x3_dgrad_weight(weight) -- the gradient of ``cout`` input channels
+    per launch of rac_conv3x3_fwd on an image of the output gradient.  Where fewer than ``cout`` input channels remain the
+    image gets zero output columns: -> (ws, w_alpha, rows) with ``rows`` the number of real ones ((None, None, 0) if the weights
+    cannot be held, an all-zero slice included).
+    Accuracy of the image, as of pack_conv3x3_weight's: hi + lo = w' * 2^s to 2^-22 relative per element (two 11-bit halves),
+    plus at most 2^-25 of the scaled unit where lo falls below f16's subnormal step 2^-24 -- with the largest |w'| * 2^s in
+    [2^13, 2^14) that absolute term is below 2^-38 of the largest weight."""
+    wt = conv3x3_dgrad_weight(weight)[c0:c0 + cout].float()
+    rows = int(wt.shape[0])
+    if 0 < rows < cout:
+        wt = torch.cat([wt, wt.new_zeros((cout - rows,) + tuple(wt.shape[1:]))], dim=0)
+    ws, alpha = pack_conv3x3_weight(wt, cout=cout) if rows > 0 else (None, None)
+    return (ws, alpha, rows) if ws is not None else (None, None, 0)
+
+
+def unpack_conv3x3_weight(ws, w_alpha):
+    """Inverse of pack_conv3x3_weight up to the split's rounding: (ws [9, Cin/32, cout, 2, 32] f16, w_alpha) -> [cout, Cin, 3, 3] float64."""
+    v = (ws[:, :, :, 0].double() + ws[:, :, :, 1].double()) * float(w_alpha)          # [tap, chunk, co, 32]
+    taps, chunks, co, _ = v.shape
+    return v.permute(2, 1, 3, 0).reshape(co, chunks * 32, 3, 3)
+
+
+def wgrad_k_splits(N, H, W, cin):
+    """Number of K ranges of rac_conv3x3_wgrad for a shape: about 512 workgroups (two per CU) over the 2 * cin / 32 output tiles,
+    at most one range per image row, none empty.  A function of the shape alone, so a shape always sums in the same order."""
+    rows = N * H
+    want = max(1, min(rows, 512 // max(1, 2 * (cin // 32))))
+    per = -(-rows // want)
+    return -(-rows // per)
+
+
 _conv_images = {}
 _scratch_ns = [None]
 
@@ -836,6 +874,15 @@ class ConvImage:
             raise RuntimeError("ConvImage.pack: sources must be float32 [N,C,H,W] matching the image")
         _lib.check(_lib.lib().rac_conv_pack_fwd(_lib.ptr(src), _lib.ptr(self.amax), _lib.ptr(self.xs), self.N, int(src.shape[1]),
                                                 self.H, self.W, self.cin, int(c_offset), _lib.stream_ptr()), "rac_conv_pack_fwd")
+        return self
+
+    def pack_cl(self, src, c_offset):
+        """``pack`` for a channel-last source [N,H,W,C] (rac_conv_pack_cl_fwd)."""
+        _lib.require_gpu(src, what="ConvImage.pack_cl")
+        if tuple(src.shape[:3]) != (self.N, self.H, self.W) or src.dtype != torch.float32 or not src.is_contiguous():
+            raise RuntimeError("ConvImage.pack_cl: sources must be contiguous float32 [N,H,W,C] matching the image")
+        _lib.check(_lib.lib().rac_conv_pack_cl_fwd(_lib.ptr(src), _lib.ptr(self.amax), _lib.ptr(self.xs), self.N, int(src.shape[3]),
+                                                   self.H, self.W, self.cin, int(c_offset), _lib.stream_ptr()), "rac_conv_pack_cl_fwd")
         return self
 
     def pack_live(self, src, bias, c_offset, frames_per_group):
@@ -917,6 +964,67 @@ class ConvImage:
                                                 _lib.ptr(self.amax), float(w_alpha), _lib.ptr(out), int(out.shape[1]), N, H, W,
                                                 int(cin), self.cin, 64, _lib.stream_ptr()), "rac_conv3x3s2_fwd")
         return out
+
+
+def conv3x3_wgrad(x_img, g_img, k_splits=None):
+    """Weight gradient [256, Cin, 3, 3] fp32 of the 3x3 / stride 1 / pad 1 convolution from the packed images of its input
+    (``x_img``, Cin channels) and of its output gradient (``g_img``, 256 channels): rac_conv3x3_wgrad, partial sums per range of
+    image rows added in a fixed order."""
+    N, H, W = x_img.N, x_img.H, x_img.W
+    if (g_img.N, g_img.H, g_img.W, g_img.cin) != (N, H, W, 256):
+        raise RuntimeError("conv3x3_wgrad: the gradient image must be [N,H,W] of 256 channels like the input image")
+    k = wgrad_k_splits(N, H, W, x_img.cin) if k_splits is None else int(k_splits)
+    work = torch.empty(k, 9, 256, x_img.cin, device=x_img.dev, dtype=torch.float32)
+    dw = torch.empty(256, x_img.cin, 3, 3, device=x_img.dev, dtype=torch.float32)
+    _lib.check(_lib.lib().rac_conv3x3_wgrad(_lib.ptr(x_img.xs), _lib.ptr(g_img.xs), _lib.ptr(x_img.amax), _lib.ptr(g_img.amax),
+                                            _lib.ptr(work), _lib.ptr(dw), N, H, W, x_img.cin, 256, k, _lib.stream_ptr()),
+               "rac_conv3x3_wgrad")
+    return dw
+
+
+def temporal_fusion_forward(x, hid, ws, w_alpha, bias):
+    """conv3x3(cat[x, hid]) + bias -> [N,H,W,256] fp32 channel-last: both halves packed into one image, no concatenation."""
+    N, cx, H, W = x.shape
+    img = ConvImage(N, H, W, cx + int(hid.shape[1]), x.device)
+    img.begin([x, hid]).pack(x, 0).pack(hid, cx)
+    return img.conv(ws, w_alpha, bias)
+
+
+def _zero_dgrad(w_slice, like):
+    """The data gradient through a weight slice pack_conv3x3_weight could not hold: zeros where the slice is all zero (e.g. a
+    zero-initialised hidden half); anything else (inf, NaN) is an error, not something to paper over."""
+    if bool((w_slice.detach() != 0).any()):
+        raise RuntimeError("temporal_fusion_backward: the transposed weights cannot be packed (non-finite values)")
+    return torch.zeros_like(like)
+
+
+def temporal_fusion_backward(x, hid, weight, grad_out, need_x, need_hid, need_w, packs):
+    """Gradients of temporal_fusion_forward: grad_out [N,H,W,256] channel-last -> (grad_x [N,256,H,W], grad_hid [N,hidden,H,W],
+    grad_w [256,Cin,3,3]; None where not asked for).  ``packs``: a dict that keeps the packed transposed weights ("dx", "dh")
+    for the weights' lifetime.  The image of grad_out gets its scale from its own maximum; the data gradients are
+    rac_conv3x3_fwd launches on it (views of channel-last results), the weight gradient rac_conv3x3_wgrad on it and the re-packed
+    image of the input."""
+    N, cx, H, W = x.shape
+    hd = int(hid.shape[1])
+    g_img = ConvImage(N, H, W, 256, x.device)
+    g_img.begin([grad_out]).pack_cl(grad_out, 0)
+    gx = gh = gw = None
+    if need_x:
+        if "dx" not in packs:
+            packs["dx"] = pack_conv3x3_dgrad_weight(weight, 0)
+        ws, alpha, _ = packs["dx"]
+        # (an all-zero slice of the weights has no power-of-two scale to pack with: its data gradient is exactly zero)
+        gx = g_img.conv(ws, alpha).permute(0, 3, 1, 2) if ws is not None else _zero_dgrad(weight[:, :cx], x)
+    if need_hid:
+        if "dh" not in packs:
+            packs["dh"] = pack_conv3x3_dgrad_weight(weight, cx)
+        ws, alpha, _ = packs["dh"]
+        gh = g_img.conv(ws, alpha)[..., :hd].permute(0, 3, 1, 2) if ws is not None else _zero_dgrad(weight[:, cx:], hid)
+    if need_w:
+        x_img = ConvImage(N, H, W, cx + hd, x.device)
+        x_img.begin([x, hid]).pack(x, 0).pack(hid, cx)
+        gw = conv3x3_wgrad(x_img, g_img)
+    return gx, gh, gw
 
 
 def conv3x3_fused(sources, ws, w_alpha, bias, bounds=None, pixel_bias=None):

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .bbox_utils import decode_bbox, inverse_sigmoid, theta_d2xy_coods, xy2theta_d_coods
@@ -35,7 +36,8 @@ from .fused import (SPLIT_ACT_SCALE, SPLIT_SLICE, ConvImage, act_image, add_ln, 
                     pack_conv3x3_weight,
                     pack_gemm_split_weight,
                     PackedAttnMask, pack_attn_mask, pe_head, refine_backward, refine_fused, regroup_backward, regroup_fused, row_gemm,
-                    row_seg, rowgemm_launch, sampling4d_backward, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16, upsample2x_fused, value_proj_fused)
+                    row_seg, rowgemm_launch, sampling4d_backward, sampling4d_fused, sasa_backward, sasa_fused, split_weight_f16,
+                    temporal_fusion_backward, temporal_fusion_forward, upsample2x_fused, value_proj_fused)
 from .msda import msda_backward, msda_forward
 from .msmv import msmv_backward, msmv_forward, msmv_v2_backward, msmv_v2_forward
 
@@ -562,6 +564,33 @@ def sampling_4d(sample_points, mlvl_feats, scale_weights, lidar2img, image_h, im
     return final
 
 
+class _TemporalFusionCore(torch.autograd.Function):
+    """The temporal-fusion convolution: apply(x [N,256,H,W], hid [N,hidden,H,W], weight [256,256+hidden,3,3], bias [256] or None,
+    packs) -> conv3x3(cat[x, hid]) + bias as [N,H,W,256] channel-last fp32.  ``packs``: dict(ws, alpha = pack_conv3x3_weight(weight)),
+    which the backward extends by the packed transposed weights.  The forward is rac_conv3x3_fwd on one image of both halves;
+    the backward rac_conv3x3_fwd on an image of the output gradient with transposed, flipped weights (one launch for x, one
+    for hid), rac_conv3x3_wgrad and a sum for the bias -- each only where ctx.needs_input_grad asks.  The fp32 inputs are saved,
+    not the image: images are scratch shared per shape.  The launchers are looked up as this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, x, hid, weight, bias, packs):
+        ctx.packs = packs
+        ctx.save_for_backward(x, hid, weight)
+        return temporal_fusion_forward(x, hid, packs["ws"], packs["alpha"], bias)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, hid, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grad_out = grad_out.contiguous()
+        gx = gh = gw = None
+        if need[0] or need[1] or need[2]:
+            gx, gh, gw = temporal_fusion_backward(x, hid, weight, grad_out, need[0], need[1], need[2], ctx.packs)
+        gb = grad_out.sum(dim=(0, 1, 2)) if need[3] else None       # (torch's reduction: a fixed tree, no atomics)
+        return gx, gh, gw, gb, None
+
+
 # ------------------------------------------------------------------------------- BEV branch
 def _records_grad(module, x):
     """autograd is recording and ``x`` or a parameter of ``module`` requires grad"""
@@ -692,8 +721,43 @@ class RadarBEVTemporalEncoder(nn.Module):
     def forward(self, bev_feats):
         B, T, C, H, W = bev_feats.shape
         x, hid = self.hidden_stream(bev_feats)
+        if self.fused_conv_grad and _records_grad(self, bev_feats) and self.fused_conv_grad_supported(bev_feats):
+            packs = self._fusion_packs()
+            if packs is not None:
+                tf = self.temporal_fusion
+                out = _TemporalFusionCore.apply(x.contiguous(), hid.contiguous(), tf.weight, tf.bias, packs)
+                return out.permute(0, 3, 1, 2).reshape(B, T, C, H, W)      # (a view: project_value transposes it back for free)
         cat = torch.cat([x, hid], dim=1)
         return self.temporal_fusion(cat).reshape(B, T, C, H, W)
+
+    # Under autograd temporal_fusion runs on the same kernel with a backward of its own (_TemporalFusionCore: the data gradients
+    # on rac_conv3x3_fwd, the weight gradient on rac_conv3x3_wgrad, fixed summation order) instead of the library's nn.Conv2d.
+    # False: the library route (the comparison of tools/temporal_fusion_bwd_timing.py).
+    fused_conv_grad = True
+
+    def fused_conv_grad_supported(self, bev_feats):
+        """Shapes the autograd route's kernels are built for: 256 map channels, 256 output channels, a hidden half of 32 .. 256
+        channels in multiples of 32, 3x3 / stride 1 / pad 1, rows that are whole float4s and at most 128 wide (the pack kernels
+        and rac_conv3x3_wgrad's row segments handle wider rows, but nothing wider is tested); any H and N -- unlike
+        fused_conv_supported, H * W need not be a multiple of 256: without a per-pixel map the forward kernel's ragged last
+        tile is handled, as are the weight gradient's ragged row segments."""
+        B, T, C, H, W = bev_feats.shape
+        tf = self.temporal_fusion
+        return (bev_feats.is_cuda and bev_feats.dtype == torch.float32 and self.embed_dims == 256 and C == 256
+                and self.hidden_dims % 32 == 0 and 32 <= self.hidden_dims <= 256 and W % 4 == 0 and W <= 128 and B * T >= 1
+                and B * T * (H + 2) * (W + 2) < 2 ** 31
+                and tf.kernel_size == (3, 3) and tf.padding == (1, 1) and tf.stride == (1, 1) and tf.dilation == (1, 1)
+                and tf.groups == 1 and tuple(tf.weight.shape[:2]) == (256, 256 + self.hidden_dims) and tf.weight.dtype == torch.float32)
+
+    def _fusion_packs(self):
+        """The packed temporal_fusion weights of the autograd route, re-packed when the weights change (None: cannot be held)."""
+        w = self.temporal_fusion.weight
+        key = (w.data_ptr(), w._version, str(w.device))
+        hit = getattr(self, "_fusion_pack_cache", None)
+        if hit is None or hit[0] != key:
+            ws, alpha = pack_conv3x3_weight(w)
+            hit = self._fusion_pack_cache = (key, dict(ws=ws, alpha=alpha) if ws is not None else None)
+        return hit[1]
 
     # temporal_fusion (193 of the encoder's 220 GFLOP) on the hand-written implicit-GEMM kernel (rac_conv3x3_fwd:
     # f16 matrix cores, hi/lo-split operands, fp32-convolution accuracy); no concatenation, no layout transposes,
@@ -950,7 +1014,8 @@ class BEVSampling(nn.Module):
         ``conv_pack["pixel_bias"]`` the pack holds value_proj o temporal_fusion (composed_value_pack) and the
         convolution's output IS the value stream."""
         H, W = bev_feats.shape[-2:]
-        # a packed convolution has no autograd history: a value stream that must carry a gradient takes the torch branch
+        # a packed convolution has no autograd history: a value stream that must carry a gradient takes the torch branch (whose
+        # temporal encoder then runs its fusion convolution through _TemporalFusionCore where fused_conv_grad_supported holds)
         if self.temp_radar and conv_pack is not None and conv_pack.get("ws") is not None and \
                 self.temporal_encoder.fused_conv_supported(bev_feats) and not self._value_needs_grad(bev_feats):
             B, T = bev_feats.shape[:2]

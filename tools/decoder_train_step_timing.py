@@ -36,7 +36,11 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decoder_train_step_f8.json"))
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--batch", type=int, default=3)
+    ap.add_argument("--library-conv-grad", action="store_true",
+                    help="the temporal-fusion convolution on the library's nn.Conv2d under autograd (RadarBEVTemporalEncoder.fused_conv_grad = False)")
     a = ap.parse_args()
+    if a.library_conv_grad:
+        T.RadarBEVTemporalEncoder.fused_conv_grad = False
     assert torch.cuda.is_available(), "needs the MI355X: a CPU run cannot give a time"
     dev = "cuda:0"
     cfg = syn.F8
@@ -105,6 +109,7 @@ def main():
                us={k: stat(v) for k, v in times.items()},
                regroup_bwd_per_level_us={k: dict(kernel_one_level_launch=stat(v["kernel"]), torch_permute_contiguous=stat(v["torch"]))
                                          for k, v in per_level.items()},
+               fused_conv_grad=bool(T.RadarBEVTemporalEncoder.fused_conv_grad),
                device=torch.cuda.get_device_name(0))
     k_us = rec["us"]["regroup_multi_bwd_all_levels"]["median"]
     rec["regroup_multi_bwd_TBps"] = 2 * nbytes / (k_us * 1e-6) / 1e12

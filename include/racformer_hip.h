@@ -50,6 +50,9 @@
  *                        models/racformer_transformer.py:705-720, :633-636
  *   rac_absmax_fwd / rac_conv_pack_fwd / rac_conv3x3_fwd <- RadarBEVTemporalEncoder.temporal_fusion (nn.Conv2d 3x3)
  *                        models/racformer_transformer.py:631,655
+ *   rac_linear_pack_act / rac_linear_pack_wt / rac_generator_ds_fwd / rac_linear_reduce / rac_linear_wgrad <- autograd of
+ *     AdaptiveMixing.parameter_generator and out_proj (models/racformer_transformer.py:565-566): forward and data gradients on
+ *     rac_generator_fwd's and rac_outproj_fwd's kernels, the weight gradients on a kernel of their own
  *   rac_conv_pack_cl_fwd / rac_conv3x3_wgrad <- autograd of the same convolution: the data gradient is rac_conv3x3_fwd on an
  *                        image of the output gradient with transposed, flipped weights; the weight gradient is a kernel of its own
  *   rac_bev_sampling_fwd <- BEVSampling keypoints + BEVSelfAttention's MSDA + frame fusion, fused
@@ -74,7 +77,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 21
+#define RAC_ABI_VERSION 22
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -748,6 +751,42 @@ int rac_conv_pack_cl_fwd(const float *src, const float *amax, void *xs, int N, i
                          void *stream);
 int rac_conv3x3_wgrad(const void *xs, const void *gs, const float *amax_x, const float *amax_g, float *workspace, float *dw, int N,
                       int H, int W, int Cin, int Cout, int k_splits, void *stream);
+
+/* ---- the two big Linears of AdaptiveMixing under autograd (y = x W^T + b: x [M][K], W [N][K], g = dy [M][N]) ----
+ * Same arithmetic as the forward kernels: hi / lo split operands, three f16 MFMA products, fp32 accumulate; no float atomics,
+ * fixed summation orders (bitwise reproducible); no host synchronisation and no allocation in any of them.
+ * Activations and gradients carry a DEVICE-side scale: amax (device f32[1], from rac_absmax_fwd) is read by the kernels, the
+ * image holds v * rac_act_scale(amax) with the scale a power of two that brings amax into [2^13, 2^14) (1 for amax == 0).
+ *
+ *   rac_linear_pack_act   src f32 rows [M][K], row m at src + m*ld_src -> image f16 [M][K/32][hi 32 | lo 32] (the X / Z image of
+ *                         rac_generator_fwd / rac_outproj_fwd).  K % 32 == 0, ld_src % 4 == 0, 16-byte aligned.  Rows past M
+ *                         are never read; amax == 0 gives an all-zero image.
+ *   rac_linear_pack_wt    weight f32 [N][K] (contiguous) -> the line image of its TRANSPOSE, f16 [K][N/32][hi 32 | lo 32] of
+ *                         weight * scale (host float): the W operand of a data gradient dX = g W.  N, K multiples of 32.
+ *   rac_generator_ds_fwd  rac_generator_fwd's K == 256 weights-stationary kernel for an X image with a device-side scale:
+ *                         out[m][n] = alpha / rac_act_scale(*amax) * sum_k X[m][k] W[n][k] + bias[n]  (bias NULL: none).
+ *                         The generator forward (X: pack of the query) and out_proj's data gradient dZ (X: pack of g, W: the
+ *                         transposed image of W_out).  A second instantiation: rac_generator_fwd's own code is unchanged.
+ *   rac_linear_reduce     out[m][n] = bias[n] + alpha / rac_act_scale(*amax) * sum_s partials[s][m][n], s ASCENDING: the slices
+ *                         of rac_outproj_fwd in true units -- the out_proj forward (Z image: pack of Z) and the generator's data
+ *                         gradient dquery (Z image: pack of dP, W image: the transposed image of W_gen).  N, ld_out % 4 == 0.
+ *   rac_linear_wgrad      C[a][b] = sum_m A[m][a] * Bm[m][b] over all M rows in ascending order, one workgroup per 128 columns b,
+ *                         every output element written once.  A, the narrow operand (`narrow` == 256 columns), comes as its
+ *                         line image [M][8][hi 32 | lo 32] packed with amax_narrow; Bm, the wide one (`wide_cols` a multiple of
+ *                         128), as fp32 rows (row m at wide + m*ld_wide, ld_wide % 4 == 0), split in the kernel with amax_wide
+ *                         (which must bound it: rac_absmax_fwd over the same tensor).
+ *                         wide_major == 0: out f32 [256][wide_cols]   (dW_out: narrow = g, wide = Z)
+ *                         wide_major != 0: out f32 [wide_cols][256]   (dW_gen: narrow = query, wide = dP)
+ *                         colsum (f32 [wide_cols] or NULL) receives sum_m Bm[m][b] in fp32, rows added in a fixed order (the
+ *                         generator's bias gradient).  Other shapes are refused (RAC_E_ARG). */
+int rac_linear_pack_act(const float *src, int64_t ld_src, const float *amax, void *image, int M, int K, void *stream);
+int rac_linear_pack_wt(const float *weight, void *image, int N, int K, float scale, void *stream);
+int rac_generator_ds_fwd(const void *x_image, const void *w_image, const float *bias, float alpha, const float *amax, float *out,
+                         int64_t ld_out, int M, int N, int K, void *stream);
+int rac_linear_reduce(const float *partials, const float *bias, const float *amax, float alpha, float *out, int64_t ld_out, int slices,
+                      int M, int N, void *stream);
+int rac_linear_wgrad(const void *narrow_image, const float *amax_narrow, const float *wide, int64_t ld_wide, const float *amax_wide,
+                     float *out, float *colsum, int M, int narrow, int wide_cols, int wide_major, void *stream);
 
 /* ---- the head loss: match costs, assignment, focal + L1 (batched over P = num_layers * batch problems) ----
  * Ground truth: ONE concatenated table gt_boxes [sum G, 9] (x, y, z, w, l, h, yaw, vx, vy; gravity centre), gt_labels [sum G]

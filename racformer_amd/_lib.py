@@ -79,6 +79,11 @@ SIGNATURES = {
     "rac_upsample2x_image_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "rac_conv_pack_cl_fwd": (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "rac_conv3x3_wgrad": (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    "rac_linear_pack_act": (_i, [_vp, ctypes.c_int64, _vp, _vp, _i, _i, _vp]),
+    "rac_linear_pack_wt": (_i, [_vp, _vp, _i, _i, _f, _vp]),
+    "rac_generator_ds_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, ctypes.c_int64, _i, _i, _i, _vp]),
+    "rac_linear_reduce": (_i, [_vp, _vp, _vp, _f, _vp, ctypes.c_int64, _i, _i, _i, _vp]),
+    "rac_linear_wgrad": (_i, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rac_conv3x3_temporal_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp] + [_i] * 7 + [_vp]),
     "rac_match_cost_fwd": (_i, [_vp] * 7 + [_i] * 6 + [_f] * 3 + [_i, _vp]),
     "rac_lsap_fwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),

@@ -265,6 +265,7 @@ struct GenArgs {
     long ld_out;
     int rows_per_wg;   // rows a workgroup walks (blockIdx.y selects the chunk): M for the wide generator, a multiple of
                        // the stage height for narrow outputs, where the feature blocks alone would leave most CUs idle
+    const float *amax;  // DEVSCALE instantiations only: device max |value| of the X image's source; the epilogue divides by rac_act_scale(*amax)
 };
 
 // Two shapes of the same kernel:
@@ -295,7 +296,10 @@ extern "C" int rac_dbg_gw_stamps(unsigned long long *host_out)
 #define GW_STAMP(i)
 #endif
 
-template <int WAVES, int ROWS>
+// DEVSCALE (rac_generator_ds_fwd, the training route): the X image was packed with the device-side scale rac_act_scale(*g.amax)
+// (rac_linear_pack_act); the epilogue reads the amax itself and multiplies by the scale's reciprocal after alpha.  The <.., false>
+// instantiations are the inference kernels, instruction for instruction what they were before the flag existed.
+template <int WAVES, int ROWS, bool DEVSCALE = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_kernel(const GenArgs g)
 {
     constexpr int STAGE = ROWS * 1024;          // bytes: K = 256 -> 8 lines = 1 KB per row
@@ -350,6 +354,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_k
         const int n = n0 + 16 * t + 4 * lk;
         bias4[t] = (g.bias && n + 3 < g.N) ? *reinterpret_cast<const gs_f4 *>(g.bias + n) : (gs_f4){0.f, 0.f, 0.f, 0.f};
     }
+    float inv_scale = 1.f;      // (two exact power-of-two factors one after the other: their product could leave the float range)
+    if constexpr (DEVSCALE)
+        inv_scale = 1.f / rac_act_scale(*g.amax);
     // (the waits below are spelled out: everything issued so far -- 12 pieces and 32 weight loads -- has to be complete)
     // (as a builtin, so that hipcc's own wait-count bookkeeping knows the weight registers have landed: behind an inline-asm wait it
     //  still placed a vmcnt(0) in front of their first use inside the stage loop -- once per trip, draining the stores of the stage before)
@@ -432,14 +439,19 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_k
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int n = n0 + 16 * t + 4 * lk;
-                const gs_f4 v = acc[t][j] * g.alpha + bias4[t];
+                gs_f4 v;
+                if constexpr (DEVSCALE)
+                    v = acc[t][j] * g.alpha * inv_scale + bias4[t];
+                else
+                    v = acc[t][j] * g.alpha + bias4[t];
                 if (row < m0 + mrows) {
                     if (n + 3 < g.N) {
                         *reinterpret_cast<gs_f4 *>(g.out + (size_t)row * g.ld_out + n) = v;
                     } else {
                         for (int r = 0; r < 4; ++r)
                             if (n + r < g.N)
-                                g.out[(size_t)row * g.ld_out + n + r] = acc[t][j][r] * g.alpha + (g.bias ? g.bias[n + r] : 0.f);
+                                g.out[(size_t)row * g.ld_out + n + r] = (DEVSCALE ? acc[t][j][r] * g.alpha * inv_scale : acc[t][j][r] * g.alpha)
+                                                                        + (g.bias ? g.bias[n + r] : 0.f);
                     }
                 }
             }
@@ -543,6 +555,57 @@ extern "C" int rac_outproj_fwd(const void *z_image, const void *w_image, float *
     return gs_launch(g, 1, (hipStream_t)stream, "rac_outproj_fwd");
 }
 
+// the K == 256 weights-stationary launches of rac_generator_fwd (DS = false) and rac_generator_ds_fwd (DS = true)
+template <bool DS>
+static int gen_ws_launch(GenArgs &a, hipStream_t st, const char *what)
+{
+    const int M = a.M, N = a.N;
+    if (GW_WIDE_WAVES == 4 && N >= 128 * 128) {
+        // the wide generator (65536 features): 512 workgroups of four waves, two per CU, every one walks all rows
+        a.rows_per_wg = (M + 15) / 16 * 16;
+        if (const int rc_attr = rac_set_dynamic_lds_once(DS ? RAC_ATTR_GENERATOR4_DS : RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16, DS>), GW_STAGES * 16 * 1024 + GW4_LDS_PAD))
+            return rc_attr;
+        hipLaunchKernelGGL((generator_ws_kernel<4, 16, DS>), dim3((N + 127) / 128, 1), dim3(256), GW_STAGES * 16 * 1024 + GW4_LDS_PAD, st, a);
+        return rac_launch_status(what);
+    }
+    // narrow outputs (the 2189 features of the sampling Linears, not the generator's 65536): the rows are cut into chunks so that
+    // feature blocks x chunks covers the CUs; every chunk re-reads its weight rows (L2) for a few row stages of work, so the
+    // weight prologue is most of a workgroup's life.  Round 5: the FOUR-wave shape here (128 features = 128 KB of weights per
+    // workgroup instead of 256 KB, 16-row stages; about 256 workgroups): 15.6 -> 12.3 us at N = 2189, M = 900
+    // (the same shape LOSES on the wide generator, 104-106 us against 88-90: there the stage loop is everything).
+#if !defined(GW_NARROW_WAVES) || GW_NARROW_WAVES == 4
+    if (N < 128 * 128) {
+        const int fb = (N + 127) / 128;
+        int ch = fb >= 256 ? 1 : 256 / fb;      // about one workgroup per CU (rows per workgroup 32 / 48 / 64 / 80 / 112: 15.7 / 13.9 / 12.9 / 12.3 / 12.7 us)
+        const int maxc = (M + 15) / 16;
+        ch = ch > maxc ? maxc : ch;
+        a.rows_per_wg = ((M + ch - 1) / ch + 15) / 16 * 16;
+#ifdef GW_NARROW_ROWS
+        a.rows_per_wg = GW_NARROW_ROWS;      /* A/B builds */
+#endif
+        ch = (M + a.rows_per_wg - 1) / a.rows_per_wg;
+        if (const int rc_attr = rac_set_dynamic_lds_once(DS ? RAC_ATTR_GENERATOR4_DS : RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16, DS>), GW_STAGES * 16 * 1024 + GW4_LDS_PAD))
+            return rc_attr;
+        hipLaunchKernelGGL((generator_ws_kernel<4, 16, DS>), dim3(fb, ch), dim3(256), GW_STAGES * 16 * 1024 + GW4_LDS_PAD, st, a);
+        return rac_launch_status(what);
+    }
+#endif
+    // the eight-wave shape for narrow outputs (rounds 2-4; A/B builds with -DGW_NARROW_WAVES=8): one workgroup per CU (128 KB of
+    // LDS), so at most 256 workgroups: a 257th would wait for a whole round.  (Measured at N = 2189, M = 900: 135 workgroups
+    // 14.8 us, 261 workgroups 20.5 us; an XCD-major item order that keeps a feature block's chunks on one L2 changed nothing.)
+    constexpr int ROWS = 32;
+    const int fblocks = (N + 255) / 256;
+    int chunks = fblocks >= 128 ? 1 : 256 / fblocks;
+    const int max_chunks = (M + ROWS - 1) / ROWS;
+    chunks = chunks > max_chunks ? max_chunks : chunks;
+    a.rows_per_wg = ((M + chunks - 1) / chunks + ROWS - 1) / ROWS * ROWS;
+    chunks = (M + a.rows_per_wg - 1) / a.rows_per_wg;
+    if (const int rc_attr = rac_set_dynamic_lds_once(DS ? RAC_ATTR_GENERATOR_DS : RAC_ATTR_GENERATOR, reinterpret_cast<const void *>(generator_ws_kernel<8, 32, DS>), GW_STAGES * ROWS * 1024))
+        return rc_attr;
+    hipLaunchKernelGGL((generator_ws_kernel<8, 32, DS>), dim3(fblocks, chunks), dim3(512), GW_STAGES * ROWS * 1024, st, a);
+    return rac_launch_status(what);
+}
+
 extern "C" int rac_generator_fwd(const void *x_image, const void *w_image, const float *bias, float alpha, float *out, int64_t ld_out,
                                  int M, int N, int K, void *stream)
 {
@@ -554,51 +617,8 @@ extern "C" int rac_generator_fwd(const void *x_image, const void *w_image, const
         GenArgs a;
         a.x = reinterpret_cast<const char *>(x_image);
         a.w = reinterpret_cast<const char *>(w_image);
-        a.bias = bias; a.out = out; a.alpha = alpha; a.M = M; a.N = N; a.ld_out = ld_out;
-        if (GW_WIDE_WAVES == 4 && N >= 128 * 128) {
-            // the wide generator (65536 features): 512 workgroups of four waves, two per CU, every one walks all rows
-            a.rows_per_wg = (M + 15) / 16 * 16;
-            if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16>), GW_STAGES * 16 * 1024 + GW4_LDS_PAD))
-                return rc_attr;
-            hipLaunchKernelGGL((generator_ws_kernel<4, 16>), dim3((N + 127) / 128, 1), dim3(256), GW_STAGES * 16 * 1024 + GW4_LDS_PAD, (hipStream_t)stream, a);
-            return rac_launch_status("rac_generator_fwd");
-        }
-        // narrow outputs (the 2189 features of the sampling Linears, not the generator's 65536): the rows are cut into chunks so that
-        // feature blocks x chunks covers the CUs; every chunk re-reads its weight rows (L2) for a few row stages of work, so the
-        // weight prologue is most of a workgroup's life.  Round 5: the FOUR-wave shape here (128 features = 128 KB of weights per
-        // workgroup instead of 256 KB, 16-row stages; about 256 workgroups): 15.6 -> 12.3 us at N = 2189, M = 900
-        // (the same shape LOSES on the wide generator, 104-106 us against 88-90: there the stage loop is everything).
-#if !defined(GW_NARROW_WAVES) || GW_NARROW_WAVES == 4
-        if (N < 128 * 128) {
-            const int fb = (N + 127) / 128;
-            int ch = fb >= 256 ? 1 : 256 / fb;      // about one workgroup per CU (rows per workgroup 32 / 48 / 64 / 80 / 112: 15.7 / 13.9 / 12.9 / 12.3 / 12.7 us)
-            const int maxc = (M + 15) / 16;
-            ch = ch > maxc ? maxc : ch;
-            a.rows_per_wg = ((M + ch - 1) / ch + 15) / 16 * 16;
-#ifdef GW_NARROW_ROWS
-            a.rows_per_wg = GW_NARROW_ROWS;      /* A/B builds */
-#endif
-            ch = (M + a.rows_per_wg - 1) / a.rows_per_wg;
-            if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16>), GW_STAGES * 16 * 1024 + GW4_LDS_PAD))
-                return rc_attr;
-            hipLaunchKernelGGL((generator_ws_kernel<4, 16>), dim3(fb, ch), dim3(256), GW_STAGES * 16 * 1024 + GW4_LDS_PAD, (hipStream_t)stream, a);
-            return rac_launch_status("rac_generator_fwd");
-        }
-#endif
-        // the eight-wave shape for narrow outputs (rounds 2-4; A/B builds with -DGW_NARROW_WAVES=8): one workgroup per CU (128 KB of
-        // LDS), so at most 256 workgroups: a 257th would wait for a whole round.  (Measured at N = 2189, M = 900: 135 workgroups
-        // 14.8 us, 261 workgroups 20.5 us; an XCD-major item order that keeps a feature block's chunks on one L2 changed nothing.)
-        constexpr int ROWS = 32;
-        const int fblocks = (N + 255) / 256;
-        int chunks = fblocks >= 128 ? 1 : 256 / fblocks;
-        const int max_chunks = (M + ROWS - 1) / ROWS;
-        chunks = chunks > max_chunks ? max_chunks : chunks;
-        a.rows_per_wg = ((M + chunks - 1) / chunks + ROWS - 1) / ROWS * ROWS;
-        chunks = (M + a.rows_per_wg - 1) / a.rows_per_wg;
-        if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_GENERATOR, reinterpret_cast<const void *>(generator_ws_kernel<8, 32>), GW_STAGES * ROWS * 1024))
-            return rc_attr;
-        hipLaunchKernelGGL((generator_ws_kernel<8, 32>), dim3(fblocks, chunks), dim3(512), GW_STAGES * ROWS * 1024, (hipStream_t)stream, a);
-        return rac_launch_status("rac_generator_fwd");
+        a.bias = bias; a.out = out; a.alpha = alpha; a.M = M; a.N = N; a.ld_out = ld_out; a.amax = nullptr;
+        return gen_ws_launch<false>(a, (hipStream_t)stream, "rac_generator_fwd");
     }
     GemmSplitArgs g;
     g.x = reinterpret_cast<const char *>(x_image);
@@ -607,4 +627,21 @@ extern "C" int rac_generator_fwd(const void *x_image, const void *w_image, const
     g.M = M; g.N = N; g.K = K; g.slices = 1;
     // other K: the tiled kernel; one workgroup per W tile walks all row tiles (its W rows stay in its XCD's L2)
     return gs_launch(g, (M + GS_TX - 1) / GS_TX, (hipStream_t)stream, "rac_generator_fwd");
+}
+
+// rac_generator_fwd's K == 256 kernel on an X image that carries a device-side scale (rac_linear_pack_act):
+// out = alpha * X W^T / rac_act_scale(*amax) + bias, the amax read in the kernel -- no host read-back.
+extern "C" int rac_generator_ds_fwd(const void *x_image, const void *w_image, const float *bias, float alpha, const float *amax, float *out,
+                                    int64_t ld_out, int M, int N, int K, void *stream)
+{
+    RAC_CHECK_ARG(x_image && w_image && out && amax, "rac_generator_ds_fwd: null pointer");
+    RAC_CHECK_ARG(K == 256, "rac_generator_ds_fwd: built for K = 256 (got %d)", K);
+    RAC_CHECK_ARG(M >= 1 && N >= 1 && ld_out >= N && ld_out % 4 == 0, "rac_generator_ds_fwd: M=%d N=%d ld_out=%lld (ld_out %% 4 must be 0)", M, N,
+                  (long long)ld_out);
+    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "rac_generator_ds_fwd: out must be 16-byte aligned");
+    GenArgs a;
+    a.x = reinterpret_cast<const char *>(x_image);
+    a.w = reinterpret_cast<const char *>(w_image);
+    a.bias = bias; a.out = out; a.alpha = alpha; a.M = M; a.N = N; a.ld_out = ld_out; a.amax = amax;
+    return gen_ws_launch<true>(a, (hipStream_t)stream, "rac_generator_ds_fwd");
 }

@@ -1313,6 +1313,256 @@ def outproj_fused(z_image, w_image, slices):
     return out
 
 
+# ------------------------------------------------------------------------------------------- the mixing Linears under autograd
+def _f32_rows(t, what, width=None):
+    """2-D float32 CUDA rows with unit inner stride, a row stride that is a multiple of 4 and a 16-byte aligned start ->
+    (pointer, M, width, row stride).  There is no CPU fallback."""
+    if not t.is_cuda:
+        raise RuntimeError(f"racformer_amd.{what}: tensor must be a CUDA tensor (HIP device); the hot path has no CPU fallback")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or (width is not None and t.shape[1] != width):
+        raise RuntimeError(f"racformer_amd.{what}: expected float32 rows [M, {width if width is not None else 'K'}], M >= 1")
+    ld = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+    if t.stride(1) != 1 or ld < t.shape[1] or ld % 4 != 0 or t.data_ptr() % 16 != 0:
+        raise RuntimeError(f"racformer_amd.{what}: rows need unit inner stride, a row stride >= the width that is a multiple of 4 "
+                           "and a 16-byte aligned start")
+    return _lib.ptr(t), int(t.shape[0]), int(t.shape[1]), ld
+
+
+def _amax1(amax, what):
+    if not amax.is_cuda:
+        raise RuntimeError(f"racformer_amd.{what}: amax must be a CUDA tensor (HIP device); the hot path has no CPU fallback")
+    if amax.dtype != torch.float32 or amax.numel() != 1:
+        raise RuntimeError(f"racformer_amd.{what}: amax must be one float32 (absmax_device)")
+    return _lib.ptr(amax)
+
+
+def absmax_device(*tensors, floor=0.0):
+    """max(floor, max |v|) over contiguous float32 CUDA tensors -> float32 [1] ON THE DEVICE (rac_absmax_fwd): the scale source of
+    linear_pack_act and linear_wgrad, never read by the host."""
+    _lib.require_gpu(*tensors, what="absmax_device")
+    if not tensors or any(t.dtype != torch.float32 for t in tensors):
+        raise RuntimeError("absmax_device: float32 tensors expected")
+    n = len(tensors)
+    amax = torch.empty(1, device=tensors[0].device, dtype=torch.float32)
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    counts = (ctypes.c_int64 * n)(*[t.numel() for t in tensors])
+    _lib.check(_lib.lib().rac_absmax_fwd(ptrs, counts, n, float(floor), _lib.ptr(amax), _lib.stream_ptr()), "rac_absmax_fwd")
+    return amax
+
+
+def linear_pack_act(src, amax, out=None):
+    """src float32 rows [M, K] (K % 32 == 0; a row stride of its own is allowed), amax float32 [1] on the device (absmax_device over
+    the same values) -> f16 line image [M, K/32, 64] = [hi 32 | lo 32] of src * rac_act_scale(amax) (rac_linear_pack_act): the X / Z
+    operand of generator_ds / outproj_fused and the narrow operand of linear_wgrad."""
+    p_src, M, K, ld = _f32_rows(src, "linear_pack_act")
+    p_amax = _amax1(amax, "linear_pack_act")
+    if K % 32 != 0:
+        raise RuntimeError(f"linear_pack_act: K = {K} must be a multiple of 32")
+    if out is None:
+        out = torch.empty(M, K // 32, 64, device=src.device, dtype=torch.float16)
+    elif tuple(out.shape) != (M, K // 32, 64) or out.dtype != torch.float16 or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError(f"linear_pack_act: out must be a contiguous CUDA float16 tensor of shape {(M, K // 32, 64)}")
+    ev = _lib.timer.record("linear_pack_act") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_linear_pack_act(p_src, ld, p_amax, _lib.ptr(out), M, K, _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_linear_pack_act")
+    return out
+
+
+def pack_linear_weight_t(weight):
+    """nn.Linear weight [N, K] fp32 (device, N and K multiples of 32) -> (f16 line image [K, N/32, 64] of weight^T * 2^s, 2^-s)
+    (rac_linear_pack_wt), the scale as pack_gemm_split_weight computes it (one host read: pack once per weight version).
+    (None, None) if f16 cannot hold the weights (all zero, non-finite) or a side is not a multiple of 32."""
+    import math
+    if not weight.is_cuda:
+        raise RuntimeError("racformer_amd.pack_linear_weight_t: tensor must be a CUDA tensor (HIP device); the hot path has no CPU fallback")
+    w = weight.detach().float().contiguous()
+    if w.dim() != 2:
+        raise RuntimeError("pack_linear_weight_t: a 2-D weight expected")
+    N, K = w.shape
+    amax = float(w.abs().max())
+    if K % 32 != 0 or N % 32 != 0 or not (amax > 0.0) or amax != amax or amax == float("inf"):
+        return None, None
+    s = 13 - math.frexp(amax)[1] + 1          # amax * 2^s in [2^13, 2^14)
+    img = torch.empty(K, N // 32, 64, device=w.device, dtype=torch.float16)
+    _lib.check(_lib.lib().rac_linear_pack_wt(_lib.ptr(w), _lib.ptr(img), N, K, float(2.0 ** s), _lib.stream_ptr()), "rac_linear_pack_wt")
+    return img, 2.0 ** (-s)
+
+
+def generator_ds(x_image, w_image, bias, alpha, amax, out=None):
+    """x_image f16 [M, 8, 64] (linear_pack_act with ``amax``), w_image f16 [N, 8, 64] -> fp32 [M, N] =
+    alpha / rac_act_scale(amax) * X @ W^T + bias (rac_generator_ds_fwd: rac_generator_fwd's K == 256 kernel reading the activation
+    scale on the device).  ``out``: destination rows [M, N] (a row stride of its own is allowed)."""
+    _lib.require_gpu(x_image, w_image, what="generator_ds")
+    p_amax = _amax1(amax, "generator_ds")
+    M, N = x_image.shape[0], w_image.shape[0]
+    if x_image.dtype != torch.float16 or w_image.dtype != torch.float16 or tuple(x_image.shape[1:]) != (8, 64) \
+            or tuple(w_image.shape[1:]) != (8, 64) or M < 1:
+        raise RuntimeError("generator_ds: operand images must be float16 [M, 8, 64] and [N, 8, 64] (K = 256)")
+    if bias is not None and (not bias.is_cuda or bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+        raise RuntimeError(f"generator_ds: bias must be a contiguous float32 CUDA [{N}] tensor")
+    if out is None:
+        out = torch.empty(M, (N + 3) // 4 * 4, device=x_image.device, dtype=torch.float32)[:, :N]
+    p_out, Mo, _, ld = _f32_rows(out, "generator_ds(out)", N)
+    if Mo != M:
+        raise RuntimeError(f"generator_ds: out must have {M} rows")
+    ev = _lib.timer.record("generator_ds") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_generator_ds_fwd(_lib.ptr(x_image), _lib.ptr(w_image), _lib.ptr(bias) if bias is not None else None, float(alpha),
+                                         p_amax, p_out, ld, M, N, 256, _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_generator_ds_fwd")
+    return out
+
+
+def linear_reduce(partials, bias, amax, alpha, out=None):
+    """partials f32 [slices, M, N] (outproj_fused) -> f32 [M, N] = bias + alpha / rac_act_scale(amax) * (the slices added in
+    ascending order) (rac_linear_reduce).  ``out``: destination rows [M, N] (a row stride of its own is allowed)."""
+    _lib.require_gpu(partials, what="linear_reduce")
+    p_amax = _amax1(amax, "linear_reduce")
+    if partials.dtype != torch.float32 or partials.dim() != 3 or partials.shape[2] % 4 != 0 or partials.shape[1] < 1:
+        raise RuntimeError("linear_reduce: partials must be float32 [slices, M, N] with N a multiple of 4")
+    S, M, N = partials.shape
+    if bias is not None and (not bias.is_cuda or bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+        raise RuntimeError(f"linear_reduce: bias must be a contiguous float32 CUDA [{N}] tensor")
+    if out is None:
+        out = torch.empty(M, N, device=partials.device, dtype=torch.float32)
+    p_out, Mo, _, ld = _f32_rows(out, "linear_reduce(out)", N)
+    if Mo != M:
+        raise RuntimeError(f"linear_reduce: out must have {M} rows")
+    _lib.check(_lib.lib().rac_linear_reduce(_lib.ptr(partials), _lib.ptr(bias) if bias is not None else None, p_amax, float(alpha),
+                                            p_out, ld, S, M, N, _lib.stream_ptr()), "rac_linear_reduce")
+    return out
+
+
+def outproj_slices(K):
+    """Split-K factor of rac_outproj_fwd for a reduction of length K: about 1024 per slice, a divisor of K / 32."""
+    lines = K // 32
+    s = max(1, lines // 32)
+    while lines % s != 0:
+        s -= 1
+    return s
+
+
+def linear_wgrad(narrow_image, amax_narrow, wide, amax_wide, wide_major, colsum=False, out=None):
+    """C[a][b] = sum_m A[m][a] * Bm[m][b] (rac_linear_wgrad): ``narrow_image`` f16 [M, 8, 64] = linear_pack_act(A [M, 256],
+    amax_narrow); ``wide`` float32 rows [M, Wd] (Wd a multiple of 128; a row stride of its own is allowed) with ``amax_wide`` =
+    absmax_device over it.  -> f32 [256, Wd], or with ``wide_major`` [Wd, 256]; with ``colsum`` also f32 [Wd] = sum_m Bm[m][b]
+    (returned as a pair).  All rows are walked in ascending order by one workgroup per 128 columns: bitwise reproducible.
+    ``out``: a contiguous destination of the result's shape."""
+    _lib.require_gpu(narrow_image, what="linear_wgrad")
+    p_wide, M, Wd, ld = _f32_rows(wide, "linear_wgrad(wide)")
+    p_an, p_aw = _amax1(amax_narrow, "linear_wgrad"), _amax1(amax_wide, "linear_wgrad")
+    if narrow_image.dtype != torch.float16 or tuple(narrow_image.shape) != (M, 8, 64):
+        raise RuntimeError(f"linear_wgrad: narrow_image must be float16 [{M}, 8, 64] (the narrow side is 256)")
+    if Wd % 128 != 0:
+        raise RuntimeError(f"linear_wgrad: the wide side {Wd} must be a multiple of 128")
+    shape = (Wd, 256) if wide_major else (256, Wd)
+    if out is None:
+        out = torch.empty(shape, device=wide.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError(f"linear_wgrad: out must be a contiguous CUDA float32 tensor of shape {shape}")
+    cs = torch.empty(Wd, device=wide.device, dtype=torch.float32) if colsum else None
+    ev = _lib.timer.record("linear_wgrad") if _lib.timer is not None else None
+    if ev:
+        ev[0].record()
+    rc = _lib.lib().rac_linear_wgrad(_lib.ptr(narrow_image), p_an, p_wide, ld, p_aw, _lib.ptr(out), _lib.ptr(cs) if colsum else None,
+                                     M, 256, Wd, 1 if wide_major else 0, _lib.stream_ptr())
+    if ev:
+        ev[1].record()
+    _lib.check(rc, "rac_linear_wgrad")
+    return (out, cs) if colsum else out
+
+
+def split_generator_forward(query, packs, bias):
+    """parameter_generator on the training route: query f32 [M, 256] -> (params f32 [M, N], amax of the query on the device)."""
+    amax = absmax_device(query)
+    img = linear_pack_act(query, amax)
+    return generator_ds(img, packs["gen_img"], bias, packs["gen_alpha"], amax), amax
+
+
+def split_generator_backward(query, amax_q, grad_params, packs, need_query, need_w, need_b):
+    """Gradients of split_generator_forward: grad_params f32 [M, N] contiguous -> (grad_query [M, 256], grad_weight [N, 256],
+    grad_bias [N]; None where not asked for).  The data gradient is rac_outproj_fwd's split-K kernel on the image of grad_params
+    and the transposed weight image (slices added in ascending order by rac_linear_reduce); the weight gradient rac_linear_wgrad
+    reading grad_params as fp32, with the bias gradient from the same pass."""
+    gq = gw = gb = None
+    if not (need_query or need_w or need_b):
+        return gq, gw, gb
+    M, N = grad_params.shape
+    amax_g = absmax_device(grad_params) if need_query or need_w else None
+    if need_query:
+        wt = packs.transposed("gen")
+        if wt[0] is None:       # (an all-zero weight has no power-of-two scale to pack with: its data gradient is exactly zero)
+            gq = torch.zeros_like(query)
+        else:
+            g_img = linear_pack_act(grad_params, amax_g)
+            gq = linear_reduce(outproj_fused(g_img, wt[0], outproj_slices(N)), None, amax_g, wt[1])
+            del g_img
+    if need_w:
+        q_img = linear_pack_act(query, amax_q)
+        res = linear_wgrad(q_img, amax_q, grad_params, amax_g, True, colsum=need_b)
+        gw, gb = res if need_b else (res, None)
+    elif need_b:
+        gb = grad_params.sum(0)
+    return gq, gw, gb
+
+
+def split_outproj_forward(z, packs, bias):
+    """out_proj on the training route: z f32 [M, K] -> (f32 [M, 256] = z W^T + bias, amax of z on the device)."""
+    amax = absmax_device(z)
+    img = linear_pack_act(z, amax)
+    K = z.shape[1]
+    return linear_reduce(outproj_fused(img, packs["out_img"], outproj_slices(K)), bias, amax, packs["out_alpha"]), amax
+
+
+def split_outproj_backward(z, amax_z, grad_out, packs, need_z, need_w, need_b):
+    """Gradients of split_outproj_forward: grad_out f32 [M, 256] contiguous -> (grad_z [M, K], grad_weight [256, K], grad_bias
+    [256]; None where not asked for).  The data gradient is rac_generator_fwd's K == 256 kernel on the image of grad_out and the
+    transposed weight image; the weight gradient rac_linear_wgrad reading z as fp32; the bias gradient a torch sum."""
+    gz = gw = None
+    gb = grad_out.sum(0) if need_b else None       # (torch's reduction: a fixed tree, no atomics)
+    if need_z or need_w:
+        amax_g = absmax_device(grad_out)
+        g_img = linear_pack_act(grad_out, amax_g)
+        if need_z:
+            wt = packs.transposed("out")
+            gz = generator_ds(g_img, wt[0], None, wt[1], amax_g) if wt[0] is not None else torch.zeros_like(z)
+        if need_w:
+            gw = linear_wgrad(g_img, amax_g, z, amax_z, False)
+    return gz, gw, gb
+
+
+class LinearGradPacks(dict):
+    """The weight images of the training route's two Linears for ONE version of the weights: "gen_img" / "gen_alpha" and
+    "out_img" / "out_alpha" (pack_gemm_split_weight; alpha = 2^-s, without an activation factor: the activations' scale lives on
+    the device), and -- packed on first use by a backward -- the transposed images ``transposed("gen" | "out")``."""
+
+    def __init__(self, gen_weight, out_weight):
+        super().__init__()
+        self._w = dict(gen=gen_weight, out=out_weight)
+        self._t = {}
+        for name, w in self._w.items():
+            img, alpha = pack_gemm_split_weight(w)
+            if img is None:
+                return
+            self[name + "_img"], self[name + "_alpha"] = img, alpha * SPLIT_ACT_SCALE
+
+    def complete(self):
+        return "gen_img" in self and "out_img" in self
+
+    def transposed(self, name):
+        hit = self._t.get(name)
+        if hit is None:
+            hit = self._t[name] = pack_linear_weight_t(self._w[name])
+        return hit
+
+
 # ------------------------------------------------------------------------------------------- decode
 def decode_fused(cls_scores, bbox_preds, max_num, post_center_range, score_threshold=None, out=None):
     """NMSFreeCoder.decode_single + get_bboxes' reshuffle for one sample in one launch (rac_decode_fwd):

@@ -6,7 +6,8 @@
     level, and the per-level share of the kernel measured as a one-level launch.
 Host-synchronised HIP events; batches alternate between the candidates so that clock and neighbours drift
 alike for all.  Writes one JSON record (default profiles/decoder_train_step_f8.json).  No time is asserted anywhere.
-    python tools/decoder_train_step_timing.py [--out PATH] [--rounds 4] [--batch 3]"""
+    python tools/decoder_train_step_timing.py [--out PATH] [--rounds 4] [--batch 3] [--library-conv-grad]
+                                              [--library-mixing-linears | --fused-mixing-linears]"""
 import argparse
 import json
 import os
@@ -38,9 +39,19 @@ def main():
     ap.add_argument("--batch", type=int, default=3)
     ap.add_argument("--library-conv-grad", action="store_true",
                     help="the temporal-fusion convolution on the library's nn.Conv2d under autograd (RadarBEVTemporalEncoder.fused_conv_grad = False)")
+    ap.add_argument("--library-mixing-linears", action="store_true",
+                    help="the mixing's parameter_generator and out_proj on the library's GEMMs under autograd (AdaptiveMixing.fused_linear_grad = False)")
+    ap.add_argument("--fused-mixing-linears", action="store_true",
+                    help="the same two Linears through _SplitLinearCore (AdaptiveMixing.fused_linear_grad = True), whatever the class default")
+    ap.add_argument("--alternate-mixing-linears", metavar="PATH", default="",
+                    help="also time the OTHER setting of AdaptiveMixing.fused_linear_grad, step by step in alternation with the chosen one in this "
+                         "process (clock, neighbours and host load drift alike for both), and write its record to PATH")
     a = ap.parse_args()
     if a.library_conv_grad:
         T.RadarBEVTemporalEncoder.fused_conv_grad = False
+    if a.library_mixing_linears or a.fused_mixing_linears:
+        assert not (a.library_mixing_linears and a.fused_mixing_linears)
+        T.AdaptiveMixing.fused_linear_grad = bool(a.fused_mixing_linears)
     assert torch.cuda.is_available(), "needs the MI355X: a CPU run cannot give a time"
     dev = "cuda:0"
     cfg = syn.F8
@@ -71,16 +82,36 @@ def main():
             return tr(qb.detach(), qf.detach(), [f.detach() for f in pyramid], lss.detach(), radar.detach(), None, metas)
 
     g1 = g2 = None
+    chosen = bool(T.AdaptiveMixing.fused_linear_grad)
+    other_times, other_peak = dict(train_forward=[], train_backward=[]), 0
     times = {k: [] for k in ("train_forward", "train_backward", "nograd_forward", "regroup_multi_bwd_all_levels", "torch_permute_contiguous_all_levels")}
     per_level = {f"level{l}": dict(kernel=[], torch=[]) for l in range(len(pyramid))}
     for r in range(a.rounds + 1):                     # round 0 warms every shape up and is dropped
         fw, bw, nf, rk, rt = [], [], [], [], []
+        ofw, obw = [], []
         lv = {k: dict(kernel=[], torch=[]) for k in per_level}
         for _ in range(a.batch):
+            if a.alternate_mixing_linears:          # the other route first, then the chosen one: one pair per step
+                T.AdaptiveMixing.fused_linear_grad = not chosen
+                torch.cuda.reset_peak_memory_stats()
+                t_f, (cls, box) = timed(step)
+                if g1 is None:
+                    g1, g2 = torch.randn_like(cls), torch.randn_like(box)
+                t_b, _ = timed(lambda: ((cls * g1).sum() + (box * g2).sum()).backward())
+                other_peak = torch.cuda.max_memory_allocated()
+                for x in leaves:
+                    x.grad = None
+                tr.zero_grad(set_to_none=True)
+                del cls, box
+                ofw.append(t_f)
+                obw.append(t_b)
+                T.AdaptiveMixing.fused_linear_grad = chosen
+            torch.cuda.reset_peak_memory_stats()
             t_f, (cls, box) = timed(step)
             if g1 is None:
                 g1, g2 = torch.randn_like(cls), torch.randn_like(box)
             t_b, _ = timed(lambda: ((cls * g1).sum() + (box * g2).sum()).backward())
+            peak = torch.cuda.max_memory_allocated()
             for x in leaves:
                 x.grad = None
             tr.zero_grad(set_to_none=True)
@@ -93,6 +124,9 @@ def main():
             for l, g in enumerate(gouts):
                 lv[f"level{l}"]["kernel"].append(timed(lambda: regroup_backward([g], dims, G))[0])
                 lv[f"level{l}"]["torch"].append(timed(lambda: torch_regroup_bwd(g))[0])
+        if r and a.alternate_mixing_linears:
+            other_times["train_forward"].append(float(np.median(ofw)))
+            other_times["train_backward"].append(float(np.median(obw)))
         if r:
             for k, v in (("train_forward", fw), ("train_backward", bw), ("nograd_forward", nf), ("regroup_multi_bwd_all_levels", rk),
                          ("torch_permute_contiguous_all_levels", rt)):
@@ -110,11 +144,23 @@ def main():
                regroup_bwd_per_level_us={k: dict(kernel_one_level_launch=stat(v["kernel"]), torch_permute_contiguous=stat(v["torch"]))
                                          for k, v in per_level.items()},
                fused_conv_grad=bool(T.RadarBEVTemporalEncoder.fused_conv_grad),
+               fused_linear_grad=bool(T.AdaptiveMixing.fused_linear_grad),
+               train_step_us_per_round=[f + b for f, b in zip(times["train_forward"], times["train_backward"])],
+               train_step_peak_memory_MB=round(peak / 1e6, 1),
                device=torch.cuda.get_device_name(0))
     k_us = rec["us"]["regroup_multi_bwd_all_levels"]["median"]
     rec["regroup_multi_bwd_TBps"] = 2 * nbytes / (k_us * 1e-6) / 1e12
     rec["regroup_speedup_over_torch"] = rec["us"]["torch_permute_contiguous_all_levels"]["median"] / k_us
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.alternate_mixing_linears:
+        note = ("train_forward / train_backward of fused_linear_grad = %s and = %s were timed step by step in alternation in one process; "
+                "the other figures belong to the process as a whole" % (chosen, not chosen))
+        rec["alternated_with"] = note
+        other = dict(rec, fused_linear_grad=not chosen, train_step_peak_memory_MB=round(other_peak / 1e6, 1),
+                     train_step_us_per_round=[f + b for f, b in zip(other_times["train_forward"], other_times["train_backward"])],
+                     us=dict(rec["us"], **{k: stat(v) for k, v in other_times.items()}))
+        with open(a.alternate_mixing_linears, "w") as f:
+            json.dump(other, f, indent=1)
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
     print(json.dumps(dict(us=rec["us"], regroup_multi_bwd_TBps=rec["regroup_multi_bwd_TBps"],

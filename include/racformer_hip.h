@@ -77,7 +77,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 22
+#define RAC_ABI_VERSION 23
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -834,6 +834,58 @@ int rac_lsap_host(const float *cost, int64_t gt_stride, int64_t query_stride, in
 int rac_det_loss_fwd(const float *logits, const float *boxes, const int32_t *target, const float *gt_boxes, const int32_t *gt_labels,
                      const float *code_weights, float *sums, float *grad_logits, float *grad_boxes, int num_layers, int rows,
                      int num_classes, int num_gt, float alpha, float gamma, void *stream);
+
+/* ---- Lift-Splat view transform around the splat (models/necks/view_transformer_racformer.py:112-295), forward and backward -------
+ * Frustum point p = ((bn * D + d) * H + h) * W + w of camera bn = b * N + n (the flat index in [B,N,D,H,W] = ranks_depth);
+ * pixel = bn * H * W + h * W + w (= ranks_feat); cell = ((b * Z + z) * Y + y) * X + x (= ranks_bev).  All pointers are device
+ * pointers, all tables int32.  No launch is sized by a count read back and nothing floating-point is accumulated atomically:
+ * the operator can be captured into a graph and is bitwise reproducible.
+ *
+ * rac_lss_cells_fwd: cells [B*N*D*H*W] = the point's cell, or -1 if dropped.
+ *   img2lidar [B*N,4,4] row-major f32 (the host's inverse of lidar2img, cast to f32); depth_tab [D], v_tab [H], u_tab [W]: the
+ *   frustum's three axes as the module's constructor built them.  point = M . (u * max(d, 1e-5), v * max(d, 1e-5), d, 1);
+ *   scaled = (point - lower) / interval in true f32 division; cell index = trunc toward zero per axis; kept when
+ *   0 <= index < size on all three axes -- so a scaled coordinate in (-1, 0) lands in cell 0 and IS kept (the reference's .long()).
+ *
+ * rac_lss_tables_fwd: cells -> ranks_bev / ranks_depth / ranks_feat [n_points], interval_starts / interval_lengths
+ *   [min(n_cells, n_points)], counts [2] = (kept points, occupied cells).  Points sorted by cell, ascending ranks_depth inside a
+ *   cell (histogram, one-workgroup scan, unordered fill, then each point placed by the number of smaller indices in its cell).
+ *   Padding past the counts: -1 in the three rank tables, start 0 / length 0 in the interval tables (trim to the counts before
+ *   handing the tables to rac_bev_pool_v2_fwd).  workspace: 3 * n_cells + n_points int32.
+ *
+ * rac_lss_softmax_stats_fwd: stats [B*N*H*W, 2] = (max, 1 / sum exp(x - max)) of each pixel's D logits; logits [B*N, D, H*W]
+ *   (channel-first, stride H*W).  The probabilities themselves are never written.
+ *
+ * rac_lss_transpose_fwd: dst [batch, cols, rows] from src [batch, rows, cols]: the layout pass between channel-first tensors and
+ *   channel-last rows (features [B*N, C, H*W] -> [B*N*H*W, C]; the incoming gradient [B*Z, C, Y*X] -> cell-major
+ *   [B*Z*Y*X, C]; grad_feat back to channel-first).
+ *
+ * rac_lss_splat_fwd: out [B, Z*C, Y, X] (channel-first, channel index z * C + c -- the order of voxel_pooling_v2's
+ *   torch.cat(bev_feat.unbind(dim=2), 1); fully written, empty cells zero)
+ *   = sum over a cell's points of softmax_D(logits)[ranks_depth] * feat[ranks_feat, :]; feat is CHANNEL-LAST [B*N*H*W, C].
+ *   The sorted points are cut into chunks of 64; one wave sums a chunk and writes one partial row per (chunk, cell) segment,
+ *   row index chunk + interval index; a second kernel adds each cell's rows in chunk order and writes runs of 16 x cells through
+ *   LDS.  cell_interval: B*Z*Y*X int32 scratch; partial: (ceil(n_points / 64) + min(n_cells, n_points)) * C f32 scratch.
+ *   C: multiples of 4 up to 320, anything else is RAC_E_ARG and nothing is launched.
+ *
+ * rac_lss_view_bwd: grad_cell [B*Z*Y*X, C] (the incoming gradient, cell-major), feat channel-last ->
+ *   grad_feat [B*N*H*W, C] (channel-last) = sum_d p_d * g[cell(d)] over the pixel's kept bins, and
+ *   grad_logits [B*N, D, H*W] = p_d * (s_d - sum_d' p_d' s_d') with s_d = <g[cell(d)], feat[pixel]> for kept bins and 0 for
+ *   dropped ones (which therefore still get a gradient).  One wave per pixel, gather only, one writer per element; D <= 256. */
+int rac_lss_cells_fwd(const float *img2lidar, const float *depth_tab, const float *v_tab, const float *u_tab, int32_t *cells,
+                      int BN, int N, int D, int H, int W, float lower_x, float lower_y, float lower_z, float interval_x,
+                      float interval_y, float interval_z, int X, int Y, int Z, void *stream);
+int rac_lss_tables_fwd(const int32_t *cells, int32_t *ranks_bev, int32_t *ranks_depth, int32_t *ranks_feat,
+                       int32_t *interval_starts, int32_t *interval_lengths, int32_t *counts, int32_t *workspace,
+                       int n_points, int n_cells, int D, int HW, void *stream);
+int rac_lss_softmax_stats_fwd(const float *logits, float *stats, int BN, int D, int HW, void *stream);
+int rac_lss_transpose_fwd(const float *src, float *dst, int batch, int rows, int cols, void *stream);
+int rac_lss_splat_fwd(const float *logits, const float *stats, const float *feat, const int32_t *ranks_depth,
+                      const int32_t *ranks_feat, const int32_t *ranks_bev, const int32_t *interval_starts,
+                      const int32_t *interval_lengths, const int32_t *counts, int32_t *cell_interval, float *partial,
+                      float *out, int n_points, int B, int C, int X, int Y, int Z, void *stream);
+int rac_lss_view_bwd(const float *grad_cell, const float *logits, const float *stats, const float *feat,
+                     const int32_t *cells, float *grad_feat, float *grad_logits, int BN, int C, int D, int HW, void *stream);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,12 @@ SIGNATURES = {
     "rac_lsap_fwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
     "rac_lsap_host": (_i, [_vp, ctypes.c_int64, ctypes.c_int64, _i, _i] + [_vp] * 5),
     "rac_det_loss_fwd": (_i, [_vp] * 9 + [_i] * 4 + [_f, _f, _vp]),
+    "rac_lss_cells_fwd": (_i, [_vp] * 5 + [_i] * 5 + [_f] * 6 + [_i] * 3 + [_vp]),
+    "rac_lss_tables_fwd": (_i, [_vp] * 8 + [_i] * 4 + [_vp]),
+    "rac_lss_softmax_stats_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "rac_lss_transpose_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "rac_lss_splat_fwd": (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
+    "rac_lss_view_bwd": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
 }
 
 

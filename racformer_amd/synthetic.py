@@ -193,6 +193,34 @@ def make_lss_ranks(n_cams=6, D=96, H=16, W=44, grid=128, cell=0.8, depth=(1.0, 6
     return tuple(torch.from_numpy(a[order].astype(np.int32)) for a in (rd, rf, rb))
 
 
+# ------------------------------------------------------------------ Lift-Splat view transform (racformer_amd.lss_view)
+LSS_GRID_F8 = dict(x=[-51.2, 51.2, 0.8], y=[-51.2, 51.2, 0.8], z=[-5.0, 3.0, 8.0], depth=[1.0, 65.0, 96.0])
+
+
+def make_lss_view_inputs(n_cams=6, batch=1, input_hw=(256, 704), downsample=16, channels=64, grid_config=None,
+                         yaws=(0.07,), seed=0, three_cam_front=False):
+    """Inputs of the Lift-Splat view transform on the ring rig WITH THE REFERENCE'S FRUSTUM (quadratic depth bins and the
+    linspace(0, size-1, n) pixel grid are the module's own, built from ``grid_config`` / ``input_hw`` / ``downsample``;
+    make_lss_ranks above keeps its uniform bins because bench.py times it).  Sample b's ego frame is yawed by ``yaws[b % len]``
+    (lidar2img right-multiplied by the rotation, as make_img_metas does).  Returns a dict: ``grid_config``, ``input_size``,
+    ``downsample``, ``img_metas`` (one {'lidar2img': [N float64 4x4]} per sample), ``depth_digit`` [B*N, D, H, W] and
+    ``tran_feat`` [B*N, C, H, W] float32 (seeded N(0,1))."""
+    grid_config = dict(grid_config or LSS_GRID_F8)
+    D = int(grid_config["depth"][2])
+    H, W = input_hw[0] // downsample, input_hw[1] // downsample
+    base = ring_lidar2img(1, n_cams, input_hw, three_cam_front)
+    metas = []
+    for b in range(batch):
+        yaw = yaws[b % len(yaws)]
+        c, s = np.cos(yaw), np.sin(yaw)
+        ego = np.array([[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float64)
+        metas.append(dict(lidar2img=[m @ ego for m in base]))
+    logits = rng_normal(seed * 1000 + 71, (batch * n_cams, D, H, W))
+    feat = rng_normal(seed * 1000 + 72, (batch * n_cams, channels, H, W))
+    return dict(grid_config=grid_config, input_size=tuple(input_hw), downsample=downsample, img_metas=metas,
+                depth_digit=torch.from_numpy(logits), tran_feat=torch.from_numpy(feat))
+
+
 # ------------------------------------------------------------------ queries
 def head_query_grid(cfg: RigConfig):
     """Polar query grid of RaCFormer_head._init_layers / generate_points

@@ -265,6 +265,7 @@ int rac_bev_sampling_bwd(const void *value, const float *query_bbox, const float
                          void *stream);
 
 /* rac_bev_sampling_bwd for batches: the same arguments and outputs, any B >= 1 (B = 0 is refused), float32 values, dim == 64.
+ * (One kernel source serves both: here B is read at run time, rac_bev_sampling_bwd's instantiation fixes it at 1.)
  * For B > 1 the forward pairs row r = 0 .. B*T-1 of the value frames -- frame and output slot (b_o, t_o) = (r / T, r % T), whose
  * frame weight and grad_out row it takes -- with the keypoints and point weights of (b_l, t_l) = (r % B, r / B)
  * (models/bev_self_attention.py:162-218); the gradients of (b_l, q)'s offsets, ray and scale logits and box table collect terms

@@ -26,6 +26,19 @@ def _rows(t, width, what):
     return _lib.ptr(t), int(t.stride(-2))
 
 
+def _bev_rows(who, tensors, Hn, P, D, T, names=("offsets", "ray_logits", "scale_logits", "queue_logits")):
+    """The four Linear outputs of a BEV stream (offsets, ray, scale, queue), or their gradients -> (pointers, row strides)."""
+    rows = [_rows(t, width, f"{who}({name})") for t, width, name in zip(tensors, (Hn * P * 2, D, Hn * P, T), names)]
+    return tuple(r[0] for r in rows), tuple(r[1] for r in rows)
+
+
+def _dest(t, query_bbox, width):
+    """A gradient destination [B,Q,width]: the caller's, or a new one."""
+    if t is not None:
+        return t
+    return torch.empty(query_bbox.shape[:2] + (width,), device=query_bbox.device, dtype=torch.float32)
+
+
 def box_prep(query_bbox, pc_range):
     """[B,Q,10] polar boxes -> [B,Q,8] (cx,cy,cz,w,l,h,cos yaw,sin yaw), once per decoder layer."""
     _lib.require_gpu(query_bbox, what="box_prep")
@@ -130,11 +143,8 @@ def sampling4d_backward(mlvl_feats, query_bbox, offsets, ray_logits, scale_logit
                                 or not view_in.is_contiguous()):
         raise RuntimeError(f"sampling4d_backward: view_in must be a contiguous CUDA uint8 [{S},{Q},{P}] tensor")
     dev = query_bbox.device
-
-    def dest(t_, width):
-        return torch.empty(B, Q, width, device=dev, dtype=torch.float32) if t_ is None else t_
-
-    grad_offsets, grad_ray, grad_scale = dest(grad_offsets, G * P * 3), dest(grad_ray, D), dest(grad_scale, G * T * P * L)
+    grad_offsets, grad_ray = _dest(grad_offsets, query_bbox, G * P * 3), _dest(grad_ray, query_bbox, D)
+    grad_scale = _dest(grad_scale, query_bbox, G * T * P * L)
     p_goff, gld_off = _rows(grad_offsets, G * P * 3, "sampling4d_backward(grad_offsets)")
     p_gray, gld_ray = _rows(grad_ray, D, "sampling4d_backward(grad_ray)")
     p_gsc, gld_sc = _rows(grad_scale, G * T * P * L, "sampling4d_backward(grad_scale)")
@@ -177,10 +187,7 @@ def bev_sampling_fused(value, hw, query_bbox, offsets, ray_logits, scale_logits,
     H, W = hw
     if tuple(value.shape) != (B * T, H * W, Hn, 64):
         raise RuntimeError(f"bev_sampling_fused: value must be [{B * T},{H * W},{Hn},64], got {tuple(value.shape)}")
-    p_off, ld_off = _rows(offsets, Hn * P * 2, "bev_sampling_fused(offsets)")
-    p_ray, ld_ray = _rows(ray_logits, D, "bev_sampling_fused(ray_logits)")
-    p_sc, ld_sc = _rows(scale_logits, Hn * P, "bev_sampling_fused(scale_logits)")
-    p_qu, ld_qu = _rows(queue_logits, T, "bev_sampling_fused(queue_logits)")
+    ptrs, lds = _bev_rows("bev_sampling_fused", (offsets, ray_logits, scale_logits, queue_logits), Hn, P, D, T)
     if box_table is None:
         box_table = box_prep(query_bbox, pc_range)
     if out is None:
@@ -193,8 +200,8 @@ def bev_sampling_fused(value, hw, query_bbox, offsets, ray_logits, scale_logits,
     if ev:
         ev[0].record()
     rc = _lib.lib().rac_bev_sampling_fwd(
-        _lib.ptr(value), _lib.ptr(query_bbox), _lib.ptr(box_table), p_off, p_ray, p_sc, p_qu, _lib.ptr(time_diff), _lib.ptr(out),
-        _lib.ptr(loc_out) if debug else None, ld_off, ld_ray, ld_sc, ld_qu, B, T, Q, Hn, NP, D, H, W, 64, pc,
+        _lib.ptr(value), _lib.ptr(query_bbox), _lib.ptr(box_table), *ptrs, _lib.ptr(time_diff), _lib.ptr(out),
+        _lib.ptr(loc_out) if debug else None, *lds, B, T, Q, Hn, NP, D, H, W, 64, pc,
         _depth_base(float(d_region), D), float(d_region), _lib.dtype_code(value), _lib.stream_ptr())
     if ev:
         ev[1].record()
@@ -207,7 +214,7 @@ BEV_BWD_LDS_LIMIT = 160 * 1024
 
 def bev_backward_batch_fits(B, num_heads, num_frames, points):
     """Whether rac_bev_sampling_bwd_batch accepts a batch of B: its workgroup stages a query index of all B samples in LDS
-    (bev_bwd_batch_lds_floats in bev_fused_bwd.hip; tests/test_bev_sampling_batch_grad_cpu.py holds the two together)."""
+    (bev_bwd_lds_floats in bev_fused_bwd.hip; tests/test_bev_sampling_batch_grad_cpu.py holds the two together)."""
     per_sample = num_heads * num_frames * points * 6 + num_heads * points * 8 + num_heads * 64 + num_frames * 3 + 16 * 2 + 16
     return B >= 1 and num_frames <= 64 and points <= 64 and 4 * B * per_sample <= BEV_BWD_LDS_LIMIT
 
@@ -232,23 +239,14 @@ def bev_sampling_backward(value, hw, query_bbox, offsets, ray_logits, scale_logi
         raise RuntimeError(f"bev_sampling_backward: value must be [{B * T},{H * W},{Hn},64], got {tuple(value.shape)}")
     if tuple(grad_out.shape) != (B, Q, Hn * 64) or grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
         raise RuntimeError(f"bev_sampling_backward: grad_out must be a contiguous float32 [{B},{Q},{Hn * 64}]")
-    p_off, ld_off = _rows(offsets, Hn * P * 2, "bev_sampling_backward(offsets)")
-    p_ray, ld_ray = _rows(ray_logits, D, "bev_sampling_backward(ray_logits)")
-    p_sc, ld_sc = _rows(scale_logits, Hn * P, "bev_sampling_backward(scale_logits)")
-    p_qu, ld_qu = _rows(queue_logits, T, "bev_sampling_backward(queue_logits)")
+    ptrs, lds = _bev_rows("bev_sampling_backward", (offsets, ray_logits, scale_logits, queue_logits), Hn, P, D, T)
     if box_table is None:
         box_table = box_prep(query_bbox, pc_range)
     dev = query_bbox.device
-
-    def dest(t_, width):
-        return torch.empty(B, Q, width, device=dev, dtype=torch.float32) if t_ is None else t_
-
-    grad_offsets, grad_ray = dest(grad_offsets, Hn * P * 2), dest(grad_ray, D)
-    grad_scale, grad_queue = dest(grad_scale, Hn * P), dest(grad_queue, T)
-    p_goff, gld_off = _rows(grad_offsets, Hn * P * 2, "bev_sampling_backward(grad_offsets)")
-    p_gray, gld_ray = _rows(grad_ray, D, "bev_sampling_backward(grad_ray)")
-    p_gsc, gld_sc = _rows(grad_scale, Hn * P, "bev_sampling_backward(grad_scale)")
-    p_gqu, gld_qu = _rows(grad_queue, T, "bev_sampling_backward(grad_queue)")
+    grad_offsets, grad_ray = _dest(grad_offsets, query_bbox, Hn * P * 2), _dest(grad_ray, query_bbox, D)
+    grad_scale, grad_queue = _dest(grad_scale, query_bbox, Hn * P), _dest(grad_queue, query_bbox, T)
+    gptrs, glds = _bev_rows("bev_sampling_backward", (grad_offsets, grad_ray, grad_scale, grad_queue), Hn, P, D, T,
+                            names=("grad_offsets", "grad_ray", "grad_scale", "grad_queue"))
     grad_value = torch.zeros(value.shape, device=dev, dtype=torch.float32)
     grad_box = torch.empty(B, Q, 8, device=dev, dtype=torch.float32)
     grad_loc = torch.empty(B, Q, Hn, T, P, 2, device=dev, dtype=torch.float32) if debug else None
@@ -260,11 +258,10 @@ def bev_sampling_backward(value, hw, query_bbox, offsets, ray_logits, scale_logi
         ev[0].record()
     symbol = "rac_bev_sampling_bwd_batch" if (B != 1 if batch_symbol is None else batch_symbol) else "rac_bev_sampling_bwd"
     rc = getattr(_lib.lib(), symbol)(
-        _lib.ptr(value), _lib.ptr(query_bbox), _lib.ptr(box_table), p_off, p_ray, p_sc, p_qu, _lib.ptr(time_diff),
-        _lib.ptr(grad_out), _lib.ptr(grad_value), p_goff, p_gray, p_gsc, p_gqu, _lib.ptr(grad_box),
-        _lib.ptr(grad_loc) if debug else None, _lib.ptr(grad_attn) if debug else None, ld_off, ld_ray, ld_sc, ld_qu,
-        gld_off, gld_ray, gld_sc, gld_qu, B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region),
-        code, _lib.stream_ptr())
+        _lib.ptr(value), _lib.ptr(query_bbox), _lib.ptr(box_table), *ptrs, _lib.ptr(time_diff),
+        _lib.ptr(grad_out), _lib.ptr(grad_value), *gptrs, _lib.ptr(grad_box),
+        _lib.ptr(grad_loc) if debug else None, _lib.ptr(grad_attn) if debug else None, *lds, *glds,
+        B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region), code, _lib.stream_ptr())
     if ev:
         ev[1].record()
     _lib.check(rc, symbol)
@@ -310,15 +307,12 @@ def bev_sampling_multi_fused(streams, hw, query_bbox, time_diff, num_frames, num
         _lib.require_gpu(value, what="bev_sampling_multi_fused")
         if tuple(value.shape) != (B * T, H * W, Hn, 64):
             raise RuntimeError(f"bev_sampling_multi_fused: value must be [{B * T},{H * W},{Hn},64], got {tuple(value.shape)}")
-        p_off, ld_off = _rows(off, Hn * P * 2, "bev_sampling_multi_fused(offsets)")
-        p_ray, ld_ray = _rows(ray, D, "bev_sampling_multi_fused(ray_logits)")
-        p_sc, ld_sc = _rows(sc, Hn * P, "bev_sampling_multi_fused(scale_logits)")
-        p_qu, ld_qu = _rows(qu, T, "bev_sampling_multi_fused(queue_logits)")
+        ptrs, ld = _bev_rows("bev_sampling_multi_fused", (off, ray, sc, qu), Hn, P, D, T)
         if lds is None:
-            lds = (ld_off, ld_ray, ld_sc, ld_qu)
-        elif lds != (ld_off, ld_ray, ld_sc, ld_qu) or value.dtype != streams[0][0].dtype:
+            lds = ld
+        elif lds != ld or value.dtype != streams[0][0].dtype:
             raise RuntimeError("bev_sampling_multi_fused: the streams must share row strides and dtype")
-        for c, v in zip(cols, (value.data_ptr(), p_off.value, p_ray.value, p_sc.value, p_qu.value)):
+        for c, v in zip(cols, (value.data_ptr(),) + tuple(x.value for x in ptrs)):
             c.append(v)
     arr = [(ctypes.c_void_p * n)(*c) for c in cols]
     outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
@@ -336,12 +330,12 @@ def bev_sampling_multi_fused(streams, hw, query_bbox, time_diff, num_frames, num
         vsc = (ctypes.c_void_p * n)(*[sc_.data_ptr() for sc_ in value_scales])
         rc = _lib.lib().rac_bev_sampling_multi_q16_fwd(
             n, arr[0], vsc, arr[1], arr[2], arr[3], arr[4], outs, _lib.ptr(query_bbox), _lib.ptr(box_table), _lib.ptr(time_diff),
-            lds[0], lds[1], lds[2], lds[3], B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region),
+            *lds, B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region),
             _lib.stream_ptr())
     else:
         rc = _lib.lib().rac_bev_sampling_multi_fwd(
             n, arr[0], arr[1], arr[2], arr[3], arr[4], outs, _lib.ptr(query_bbox), _lib.ptr(box_table), _lib.ptr(time_diff),
-            lds[0], lds[1], lds[2], lds[3], B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region),
+            *lds, B, T, Q, Hn, NP, D, H, W, 64, pc, _depth_base(float(d_region), D), float(d_region),
             _lib.dtype_code(streams[0][0]), _lib.stream_ptr())
     if ev:
         ev[1].record()

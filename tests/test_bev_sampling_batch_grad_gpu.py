@@ -11,7 +11,8 @@
    weights of (b_o, t_o) for row r) must fail every gradient kind at (B, T) = (2, 3) -- after checking on the CPU that the two
    pairings differ by far more than the bound on that input.
 3. B = 1 through the new symbol against rac_bev_sampling_bwd: every output but grad_value bit-identical, grad_value within 1e-5 of
-   its largest element.
+   its largest element.  Both symbols against a pin of the build before the two kernels became two instantiations of one source
+   (tests/golden/bev_bwd_pin.npz): every output but grad_value bit for bit, on the smallest cases that enter every loop's second trip.
 4. Two runs at B = 2, f8 shape (Q = 900, T = 8, heads 4, P = 20, 128 x 128): the same criterion.
 5. Module level: the ``b2:`` golden of the reference through attend_prepared(..., fused_batch=True): one forward and one backward
    launch of the fused kernels; the grad-mode output is the no_grad output bit for bit.
@@ -36,6 +37,7 @@ import test_bev_sampling_grad_gpu as G
 from racformer_amd import _lib
 from racformer_amd import synthetic as syn
 from racformer_amd import transformer as T
+from golden import gen_bev_bwd_pin as pin
 from racformer_amd.fused import bev_sampling_backward, bev_sampling_fused, box_prep
 from test_bev_sampling_batch_grad_cpu import case
 from test_bev_sampling_grad_cpu import check_against_golden, inputs_from, load_golden, module_from
@@ -179,6 +181,24 @@ def test_two_runs_are_reproducible_b2_f8():
     b, _, _ = run_kernel(c, gout)
     _same_but_value(a, b)
     assert float(a["offsets"].abs().max()) > 0 and bool(torch.isfinite(a["value"]).all())
+
+
+@pytest.mark.parametrize("name,batch_symbol", [(n, b) for n in pin.CASES for b in pin.symbols(n)])
+def test_single_writer_outputs_are_the_pinned_ones(golden_dir, name, batch_symbol):
+    """every output but grad_value, bit for bit as the build of the commit before the two kernels became one source returned it on the
+    MI355X (tests/golden/gen_bev_bwd_pin.py, bev_bwd_pin.npz), through both symbols at B = 1"""
+    with np.load(os.path.join(golden_dir, "bev_bwd_pin.npz")) as z:
+        d = {k[len(name) + 1:]: z[k] for k in z.files if k.startswith(name + "|")}
+    assert tuple(d["case"]) == tuple(float(x) for x in pin.CASES[name])
+    c, gout = pin.draw(name)
+    # (float64 sums of up to 3e7 float32 values: their order, so their last bits, is the library's; another draw is off by O(1))
+    assert np.allclose(pin.checksums(c, gout), d["checksums"], rtol=0, atol=1e-6), "the drawn inputs are not the pinned run's"
+    got, loc, _ = run_kernel(c, gout, batch_symbol=batch_symbol)
+    if pin.CASES[name][9]:
+        assert bool(((loc == 0) | (loc == 1)).any())
+    for kind in pin.OUTPUTS:
+        want = torch.from_numpy(d["grad_" + kind])
+        assert torch.equal(got[kind].reshape(want.shape), want), (name, batch_symbol, kind)
 
 
 # ------------------------------------------------------------------------------------------------------------ module level

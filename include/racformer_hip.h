@@ -77,7 +77,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 23
+#define RAC_ABI_VERSION 24
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -528,6 +528,12 @@ int rac_value_proj_q16_fwd(const float *x, const void *w_image, float w_alpha, c
  *                     ws = f16 [9 taps (ky*3+kx)][Cin/32][256][2][32] holding hi / lo of weight[co][ci][ky][kx] / w_alpha
  *                     (w_alpha a power of two chosen by the packer).  Any H*W (tiles of 256 pixels, the last one of an image
  *                     ragged); a pixel_bias map needs H*W to be a multiple of 256. */
+/* rac_conv3x3_relu_cf_fwd: the same kernel with another epilogue: out [N][256][H*W] f32 CHANNEL-FIRST = relu(conv3x3(xs) + bias[c])
+ * -- Conv2d(3x3, pad 1, bias=False) + BatchNorm2d (folded into ws and bias by the host) + ReLU, the last ConvModule of radar_bev_conv
+ * (models/racformer.py:81-99).  The image's scale is act_scale(scale_mul * (*amax) + scale_add) as in rac_cd_scale (amax: device
+ * word or NULL), so an image written by rac_conv_direct_fwd can be read as it is.  Cout = 256, Cin a multiple of 32, any H*W. */
+int rac_conv3x3_relu_cf_fwd(const void *xs, const void *ws, const float *bias, const float *amax, float scale_mul, float scale_add,
+                            float w_alpha, float *out, int N, int H, int W, int Cin, int Cout, void *stream);
 int rac_absmax_fwd(const float *const *srcs, const int64_t *counts, int num, float floor_value, float *amax_out,
                    void *stream);
 int rac_conv_pack_fwd(const float *src, const float *amax, void *xs, int N, int C, int H, int W, int c_total,
@@ -684,8 +690,12 @@ int rac_bev_pool_v2_bwd(const float *out_grad, float *depth_grad, float *feat_gr
  * mode RAC_CD_GRU   : Cout = 3 * 64 gate channels (z | r | candidate); pre = conv(h_prev image) + xpart[frame][pixel][192];
  *                     z = sigmoid, r = sigmoid, cand = tanh(pre_c + r * h_prev), h = (1 - z) h_prev + z cand  (:714-720);
  *                     h -> h_out f32 [frames][OH*OW][64] AND out_img (the next step's convolution input); h_prev NULL = zeros
+ * mode RAC_CD_IMAGE_RELU   : RAC_CD_IMAGE with out_img <- relu(conv + bias); stride 1, chunks = 2 (64 input channels)
+ * mode RAC_CD_F32_CF_RELU  : out_f32 [N][Cout][OH*OW] CHANNEL-FIRST <- relu(conv + bias); stride 1, chunks = 2, no pixel_map.
+ *                     These two are Conv2d(3x3, pad 1, bias=False) + BatchNorm2d (folded into weights and bias by the host) + ReLU
+ *                     of radar_bev_conv (models/racformer.py:81-99); the modes 0..2 are unchanged by them, bit for bit.
  */
-enum { RAC_CD_IMAGE = 0, RAC_CD_F32 = 1, RAC_CD_GRU = 2 };
+enum { RAC_CD_IMAGE = 0, RAC_CD_F32 = 1, RAC_CD_GRU = 2, RAC_CD_IMAGE_RELU = 3, RAC_CD_F32_CF_RELU = 4 };
 typedef struct {
     const float *amax;     /* device word or NULL */
     float mul, add;
@@ -887,6 +897,46 @@ int rac_lss_splat_fwd(const float *logits, const float *stats, const float *feat
                       float *out, int n_points, int B, int C, int X, int Y, int Z, void *stream);
 int rac_lss_view_bwd(const float *grad_cell, const float *logits, const float *stats, const float *feat,
                      const int32_t *cells, float *grad_feat, float *grad_logits, int BN, int C, int D, int HW, void *stream);
+
+/* ---- Radar pillar encoder: point clouds to the BEV canvas (models/racformer.py:130-177 extract_pts_feat / radar_voxelize; mmcv 1.6.0
+ * Voxelization (hard), mmdet3d 1.0.0rc6 PillarFeatureNet and PointPillarsScatter; configs/racformer_r50_nuimg_704x256_f8.py:122-139) ----
+ * All clouds of a call are packed: points [n_points][C] f32, cloud_offsets [n_clouds + 1] int32 (cloud c = rows offsets[c] ..
+ * offsets[c+1] - 1; offsets[n_clouds] <= n_points, rows past it belong to no cloud), both on the device.  Launches are sized by
+ * n_points and n_clouds * cells; nothing is read back, no float atomics (integer min / max only): capturable, bitwise reproducible.
+ *
+ * rac_pillar_voxelize_fwd: hard voxelization in the one deterministic order (mmcv's CPU path / deterministic=True): walking a
+ *   cloud's points in input order, c_j = floor((p_j - lo_j) / vs_j) in IEEE f32 (true division); a point outside [0, grid_j) on any
+ *   axis is skipped; a new cell gets the next pillar index while fewer than max_voxels exist (afterwards its points are skipped,
+ *   points of registered cells are still taken); a pillar keeps its first max_num_points points.
+ *     voxels      f32 [n_points][max_num_points][C]   pillar i of cloud c is row offsets[c] + i; zero-padded
+ *     coors       int32 [n_points][4] = (cloud, c_z, c_y, c_x); -1 in rows that hold no pillar
+ *     num_points  int32 [n_points]; 0 in rows that hold no pillar
+ *     counts      int32 [n_clouds]: pillars per cloud
+ *     amax        f32 [1]: max |value| over the in-range points (0 if none) -- the device word of the activation image's scale
+ *     workspace   int32 [2 * n_clouds * cells + n_points]
+ *   Limits: 4 <= C <= 16, 1 <= max_num_points <= 32, n_clouds * cells < 2^30, n_points * max_num_points * C < 2^31.
+ *
+ * rac_pillar_encode_fwd: PillarFeatureNet (one PFN layer, 64 channels, with_cluster_center, with_voxel_center, legacy=False, no
+ *   distance) + PointPillarsScatter in one launch per destination set.  Per pillar: mean = sum of the rows' xyz / num_points;
+ *   features [C raw | xyz - mean | x - (c_x vs_x + center_x), y and z alike] (C + 6); y = relu(wt^T f + shift) per row, wt f32 [C+6][64]
+ *   and shift [64] holding the Linear with the BatchNorm1d folded in; max over the max_num_points rows, rows >= num_points taking
+ *   part with relu(shift) (the reference zeroes their features and still runs them through Linear / BN / ReLU / max).
+ *     canvas  f32 [n_clouds][64][H][W] (PointPillarsScatter's result: canvas[cloud, :, c_y, c_x]) or NULL
+ *     image   f16 [n_clouds][H+2][W+2][2][hi 32 | lo 32] activation image of rac_conv_direct_fwd or NULL, with the scale
+ *             act_scale(bound_mul * (*amax) + bound_add) (amax may be NULL)
+ *     feats   f32 [n_rows][64]: the pillar features themselves (PillarFeatureNet.forward's result), rows without a pillar are
+ *             not written; or NULL
+ *   Any subset, at least one; canvas and image are cleared on the stream first (the image's border included), so cells without a
+ *   pillar read as zero on every call.  n_rows = rows of voxels / coors / num_points; rows whose coors are -1 are skipped.  H = grid_y, W = grid_x. */
+int rac_pillar_voxelize_fwd(const float *points, const int32_t *cloud_offsets, float *voxels, int32_t *coors, int32_t *num_points,
+                            int32_t *counts, float *amax, int32_t *workspace, int n_points, int n_clouds, int C, float lo_x,
+                            float lo_y, float lo_z, float vs_x, float vs_y, float vs_z, int grid_x, int grid_y, int grid_z,
+                            int max_num_points, int max_voxels, void *stream);
+int rac_pillar_encode_fwd(const float *voxels, const int32_t *coors, const int32_t *num_points, const float *wt, const float *shift,
+                          const float *amax, float bound_mul, float bound_add, float *canvas, void *image, float *feats, int n_rows,
+                          int n_clouds,
+                          int C, int max_num_points, int F, float vs_x, float vs_y, float vs_z, float center_x, float center_y,
+                          float center_z, int H, int W, void *stream);
 
 #ifdef __cplusplus
 }

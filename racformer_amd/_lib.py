@@ -66,6 +66,7 @@ SIGNATURES = {
     "rac_conv_pack_fwd": (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "rac_conv_pack_bias_fwd": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_vp]),
     "rac_conv3x3_fwd": (_i, [_vp] * 5 + [_f, _vp] + [_i] * 5 + [_vp]),
+    "rac_conv3x3_relu_cf_fwd": (_i, [_vp] * 4 + [_f, _f, _f, _vp] + [_i] * 5 + [_vp]),
     "rac_conv3x3_q16_fwd": (_i, [_vp] * 5 + [_f, _vp, _vp] + [_i] * 5 + [_vp]),
     "rac_fpn_conv_fwd": (_i, [_vp] * 4 + [_f, _vp] + [_i] * 5 + [_vp]),
     "rac_conv3x3s2_fwd": (_i, [_vp] * 4 + [_f, _vp] + [_i] * 7 + [_vp]),
@@ -95,6 +96,8 @@ SIGNATURES = {
     "rac_lss_transpose_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "rac_lss_splat_fwd": (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
     "rac_lss_view_bwd": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
+    "rac_pillar_voxelize_fwd": (_i, [_vp] * 8 + [_i] * 3 + [_f] * 6 + [_i] * 5 + [_vp]),
+    "rac_pillar_encode_fwd": (_i, [_vp] * 6 + [_f, _f, _vp, _vp, _vp] + [_i] * 5 + [_f] * 6 + [_i, _i, _vp]),
 }
 
 
@@ -132,7 +135,7 @@ class ConvDirect(ctypes.Structure):
                 ("h_out_frames", CdFrames)]
 
 
-CD_IMAGE, CD_F32, CD_GRU = 0, 1, 2
+CD_IMAGE, CD_F32, CD_GRU, CD_IMAGE_RELU, CD_F32_CF_RELU = 0, 1, 2, 3, 4
 
 
 def lib():

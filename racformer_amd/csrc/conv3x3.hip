@@ -166,8 +166,9 @@ struct ConvArgs {
     // whose contribution through the zero padding the caller folded into that map
     const float *pixel_bias_dead;
     int fpg, live, chunks_dead;
+    float scale_mul, scale_add;   // CV_OUT_NCHW_RELU only: the image's bound is scale_mul * (*amax) + scale_add (amax may be NULL)
 };
-enum { CV_OUT_NHWC = 0, CV_OUT_GROUPED = 1, CV_OUT_Q16 = 2 };
+enum { CV_OUT_NHWC = 0, CV_OUT_GROUPED = 1, CV_OUT_Q16 = 2, CV_OUT_NCHW_RELU = 3 };
 __device__ __forceinline__ cv_f4 cv_fma4(cv_f4 a, float s, cv_f4 b)
 {
     return __builtin_elementwise_fma(a, (cv_f4){s, s, s, s}, b);
@@ -178,7 +179,9 @@ __device__ __forceinline__ cv_f4 cv_fma4(cv_f4 a, float s, cv_f4 b)
 // (b*T + t) * 4 + g (models/racformer_transformer.py:112-124: what the reference builds with a reshape / permute copy of
 // the FPN's output; here the FPN's last convolution writes it).  CV_OUT_Q16: the channel-last result in the int16 block
 // storage of quant.hip (the BEV value stream as rac_bev_sampling_multi_q16_fwd reads it), quantised in the epilogue: bit for
-// bit what rac_quant_i16_fwd makes of the CV_OUT_NHWC output, without the 134 MB fp32 stream in between.
+// bit what rac_quant_i16_fwd makes of the CV_OUT_NHWC output, without the 134 MB fp32 stream in between.  CV_OUT_NCHW_RELU:
+// out [N][256][H*W] CHANNEL-FIRST = relu(conv + bias) -- the last Conv2d + folded BatchNorm2d + ReLU of the radar pillar branch
+// (radar_pillars.hip), whose input image carries the scale of a derived bound (rac_cd_scale's expression, as conv_direct.hip wrote it).
 template <int MODE>
 __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
 {
@@ -366,8 +369,28 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
     // The weights are the MFMA's A operand, so a 16x16 accumulator tile has its PIXEL on the lane (column li) and four
     // consecutive output CHANNELS (rows 4 lk + r) in the lane's registers: one 16-byte store (and one 16-byte bias load) per
     // tile instead of four 4-byte ones (round 4; the predicated 4-byte form also serialised 128 bias loads per lane).
-    const float unscale = a.w_alpha / cv_act_scale(*a.amax);
+    const float unscale = a.w_alpha / cv_act_scale(MODE == CV_OUT_NCHW_RELU ? (a.amax ? a.scale_mul * *a.amax : 0.f) + a.scale_add : *a.amax);
     const int prows = min(CV_TM, HW - tile * CV_TM);       // valid pixels of this tile
+    if (MODE == CV_OUT_NCHW_RELU) {
+        // a channel's 16 pixels of tile m are the 16 lanes li: 64-byte runs, the 8 tiles m of a wave row 512 contiguous bytes
+        float *obase = a.out + (size_t)n * CV_COUT * HW + (size_t)tile * CV_TM;
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn) {
+            const int col = 64 * wn + 16 * nn + 4 * lk;
+            const cv_f4 bv = a.bias ? *reinterpret_cast<const cv_f4 *>(a.bias + col) : (cv_f4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int p = 128 * wm + 16 * m + li;
+                if (p < prows) {
+                    const cv_f4 v = __builtin_elementwise_max(cv_fma4(acc[m][nn], unscale, bv), (cv_f4){0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        obase[(size_t)(col + r) * HW + p] = v[r];
+                }
+            }
+        }
+        return;
+    }
     if (GROUPED) {
         // wave column wn IS the group (64 channels each): slot = (n / cams) * 4 + wn, view = n % cams
         const int bt = n / a.cams, cam = n - bt * a.cams;
@@ -661,6 +684,7 @@ static int cv_launch_plain(const void *xs, const void *ws, const float *bias, co
     a.q = reinterpret_cast<short *>(q); a.qscale = qscale;
     a.N = N; a.H = H; a.W = W; a.chunks = Cin / 32; a.w_alpha = w_alpha; a.cams = 1;
     a.pixel_bias_dead = pixel_bias_dead; a.fpg = pixel_bias_dead ? frames_per_group : 0; a.live = live_per_group; a.chunks_dead = Cin_dead / 32;
+    a.scale_mul = 1.f; a.scale_add = 0.f;
     const int lds = 2 * CV_STAGE_U4 * 16;
     const dim3 grid((unsigned)(N * ((H * W + CV_TM - 1) / CV_TM)));
     if (q) {
@@ -679,6 +703,32 @@ extern "C" int rac_conv3x3_fwd(const void *xs, const void *ws, const float *bias
                                float w_alpha, float *out, int N, int H, int W, int Cin, int Cout, void *stream)
 {
     return cv_launch_plain(xs, ws, bias, pixel_bias, amax, w_alpha, out, nullptr, nullptr, N, H, W, Cin, Cout, stream, "rac_conv3x3_fwd");
+}
+
+extern "C" int rac_conv3x3_relu_cf_fwd(const void *xs, const void *ws, const float *bias, const float *amax, float scale_mul, float scale_add,
+                                       float w_alpha, float *out, int N, int H, int W, int Cin, int Cout, void *stream)
+{
+    const char *what = "rac_conv3x3_relu_cf_fwd";
+    RAC_CHECK_ARG(Cout == CV_COUT, "%s: built for %d output channels (got %d)", what, CV_COUT, Cout);
+    RAC_CHECK_ARG(Cin > 0 && Cin % 32 == 0, "%s: Cin=%d (multiple of 32)", what, Cin);
+    RAC_CHECK_ARG(N >= 0 && H > 0 && W > 0, "%s: N=%d H=%d W=%d", what, N, H, W);
+    RAC_CHECK_ARG(scale_mul >= 0.f && scale_add >= 0.f, "%s: scale constants must be >= 0", what);
+    if (N == 0)
+        return 0;
+    RAC_CHECK_ARG(xs && ws && out, "%s: null pointer", what);
+    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(bias) & 15) == 0, "%s: bias must be 16-byte aligned", what);
+    ConvArgs a;
+    a.xs = reinterpret_cast<const uint4 *>(xs);
+    a.ws = reinterpret_cast<const uint4 *>(ws);
+    a.bias = bias; a.pixel_bias = nullptr; a.amax = amax; a.out = out; a.q = nullptr; a.qscale = nullptr;
+    a.N = N; a.H = H; a.W = W; a.chunks = Cin / 32; a.w_alpha = w_alpha; a.cams = 1;
+    a.pixel_bias_dead = nullptr; a.fpg = 0; a.live = 0; a.chunks_dead = 0; a.scale_mul = scale_mul; a.scale_add = scale_add;
+    const int lds = 2 * CV_STAGE_U4 * 16;
+    if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_CONV3X3_CF, reinterpret_cast<const void *>(conv3x3_f16x3_kernel<CV_OUT_NCHW_RELU>), lds))
+        return rc_attr;
+    hipLaunchKernelGGL(conv3x3_f16x3_kernel<CV_OUT_NCHW_RELU>, dim3((unsigned)(N * ((H * W + CV_TM - 1) / CV_TM))), dim3(512), lds,
+                       (hipStream_t)stream, a);
+    return rac_launch_status(what);
 }
 
 extern "C" int rac_conv3x3_q16_fwd(const void *xs, const void *ws, const float *bias, const float *pixel_bias, const float *amax,
@@ -719,7 +769,7 @@ extern "C" int rac_fpn_conv_fwd(const void *xs, const void *ws, const float *bia
     a.ws = reinterpret_cast<const uint4 *>(ws);
     a.bias = bias; a.pixel_bias = nullptr; a.amax = amax; a.out = out;
     a.N = num_images; a.H = H; a.W = W; a.chunks = Cin / 32; a.w_alpha = w_alpha; a.cams = num_cams; a.q = nullptr; a.qscale = nullptr;
-    a.pixel_bias_dead = nullptr; a.fpg = 0; a.live = 0; a.chunks_dead = 0;
+    a.pixel_bias_dead = nullptr; a.fpg = 0; a.live = 0; a.chunks_dead = 0; a.scale_mul = 1.f; a.scale_add = 0.f;
     const int lds = 2 * CV_STAGE_U4 * 16;
     if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_FPN_CONV, reinterpret_cast<const void *>(conv3x3_f16x3_kernel<CV_OUT_GROUPED>), (int)(lds)))
         return rc_attr;

@@ -73,7 +73,10 @@ __device__ __forceinline__ float cd_scale(const rac_cd_scale &s)
 // LDS: two chunk buffers [9 taps][NT tiles][16 rows][8 slots of 16 B], slot s of row r at position s ^ ((r >> 1) & 7) (16-byte
 // fragment reads without bank conflicts; LDS-DMA writes a wave-instruction's 1 KB linearly, so the permutation sits on the source
 // side, as in gemm_split.hip).
-template <int STRIDE, int NT, int PT, int MODE, int D, int KCH>
+//   EPI 0: the epilogues as described; 1: ReLU on conv + bias (+ pixel_map) first (RAC_CD_IMAGE_RELU); 2: ReLU and a CHANNEL-FIRST
+//       fp32 store out_f32 [N][Cout][OH*OW] (RAC_CD_F32_CF_RELU: 16 consecutive pixels of a channel per store instruction and
+//       accumulator register, 64-byte runs) -- Conv2d + folded BatchNorm2d + ReLU of the radar branch (radar_pillars.hip)
+template <int STRIDE, int NT, int PT, int MODE, int D, int KCH, int EPI = 0>
 __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
 {
     static_assert(9 % D == 0, "ring depth must divide the 9 taps of a chunk");
@@ -246,7 +249,17 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
                 cd_f4 add = a.bias ? *reinterpret_cast<const cd_f4 *>(a.bias + c) : (cd_f4){0.f, 0.f, 0.f, 0.f};
                 if (a.pixel_map)
                     add += *reinterpret_cast<const cd_f4 *>(a.pixel_map + (size_t)p * a.Cout + c);
-                *reinterpret_cast<cd_f4 *>(o + c) = __builtin_elementwise_fma(acc[nn][j], us4, add);
+                cd_f4 v = __builtin_elementwise_fma(acc[nn][j], us4, add);
+                if constexpr (EPI != 0)
+                    v = __builtin_elementwise_max(v, (cd_f4){0.f, 0.f, 0.f, 0.f});
+                if constexpr (EPI == 2) {
+                    float *ocf = a.out_f32 + ((size_t)n * a.Cout + c) * npix + p;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        ocf[(size_t)r * npix] = v[r];
+                } else {
+                    *reinterpret_cast<cd_f4 *>(o + c) = v;
+                }
             }
             continue;
         }
@@ -270,7 +283,10 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
             for (int nn = 0; nn < NT; ++nn) {
                 const int c = co0[nn] + 4 * lk;
                 const cd_f4 bv = a.bias ? *reinterpret_cast<const cd_f4 *>(a.bias + c) : (cd_f4){0.f, 0.f, 0.f, 0.f};
-                store_img(c, __builtin_elementwise_fma(acc[nn][j], us4, bv));
+                cd_f4 v = __builtin_elementwise_fma(acc[nn][j], us4, bv);
+                if constexpr (EPI != 0)
+                    v = __builtin_elementwise_max(v, (cd_f4){0.f, 0.f, 0.f, 0.f});
+                store_img(c, v);
             }
             continue;
         }
@@ -343,26 +359,26 @@ __global__ __launch_bounds__(256) void upsample2x_image_kernel(const float *__re
 
 static bool cd_host_scale_ok(const rac_cd_scale &s) { return s.mul >= 0.f && s.add >= 0.f; }
 
-template <int STRIDE, int NT, int PT, int MODE, int KCH>
+template <int STRIDE, int NT, int PT, int MODE, int KCH, int EPI = 0>
 static int cd_launch(const CdArgs &a, int attr_id, hipStream_t st)
 {
     // ring depth 3 (measured at 1 / 3 / 9 with tools/exp_convdirect.py: 39.9 / 31.7 / 31.1 us for the downsample, no difference elsewhere)
     constexpr int D = 3;
     constexpr int lds = KCH > 0 ? 2 * 9 * NT * 128 * 16 : 0;
-    const void *fn = reinterpret_cast<const void *>(conv_direct_kernel<STRIDE, NT, PT, MODE, D, KCH>);
+    const void *fn = reinterpret_cast<const void *>(conv_direct_kernel<STRIDE, NT, PT, MODE, D, KCH, EPI>);
     if (lds > 48 * 1024)
         if (const int rc = rac_set_dynamic_lds_once(attr_id, fn, lds))
             return rc;
     const int npix = a.OH * a.OW, ptiles = (npix + 64 * PT - 1) / (64 * PT);
     const int cblocks = MODE == RAC_CD_GRU ? 4 : a.Cout / (16 * NT);
-    hipLaunchKernelGGL((conv_direct_kernel<STRIDE, NT, PT, MODE, D, KCH>), dim3((unsigned)(a.N * ptiles * cblocks)), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((conv_direct_kernel<STRIDE, NT, PT, MODE, D, KCH, EPI>), dim3((unsigned)(a.N * ptiles * cblocks)), dim3(256), lds, st, a);
     return 0;
 }
 
 extern "C" int rac_conv_direct_fwd(const rac_conv_direct *d, void *stream)
 {
     RAC_CHECK_ARG(d, "rac_conv_direct_fwd: null descriptor");
-    RAC_CHECK_ARG(d->mode >= RAC_CD_IMAGE && d->mode <= RAC_CD_GRU && (d->conv_stride == 1 || d->conv_stride == 2),
+    RAC_CHECK_ARG(d->mode >= RAC_CD_IMAGE && d->mode <= RAC_CD_F32_CF_RELU && (d->conv_stride == 1 || d->conv_stride == 2),
                   "rac_conv_direct_fwd: mode=%d conv_stride=%d", d->mode, d->conv_stride);
     RAC_CHECK_ARG(d->N >= 0 && d->H > 0 && d->W > 0 && d->H % d->conv_stride == 0 && d->W % d->conv_stride == 0,
                   "rac_conv_direct_fwd: N=%d H=%d W=%d", d->N, d->H, d->W);
@@ -404,20 +420,27 @@ extern "C" int rac_conv_direct_fwd(const rac_conv_direct *d, void *stream)
     RAC_CHECK_ARG(d->Cout > 0 && d->Cout % 64 == 0, "rac_conv_direct_fwd: Cout=%d (a multiple of 64)", d->Cout);
     RAC_CHECK_ARG(((reinterpret_cast<uintptr_t>(d->bias) | reinterpret_cast<uintptr_t>(d->pixel_map) | reinterpret_cast<uintptr_t>(d->out_f32)) & 15) == 0,
                   "rac_conv_direct_fwd: bias / pixel_map / out_f32 must be 16-byte aligned");
-    if (d->mode == RAC_CD_IMAGE) {
+    if (d->mode == RAC_CD_IMAGE || d->mode == RAC_CD_IMAGE_RELU) {
         RAC_CHECK_ARG(d->out_img && d->out_chunk0 >= 0 && d->out_chunk0 * 32 + d->Cout <= d->out_chunks_total * 32,
                       "rac_conv_direct_fwd: output image has no room for %d channels from chunk %d", d->Cout, d->out_chunk0);
         if (d->conv_stride == 2) {
+            RAC_CHECK_ARG(d->mode == RAC_CD_IMAGE, "rac_conv_direct_fwd: the ReLU image mode is built for stride 1");
             RAC_CHECK_ARG(k == 8 || k == 2 || k == 3, "rac_conv_direct_fwd: stride 2 is instantiated for 2 / 3 / 8 input chunks, got %d", k);
             rc = k == 8 ? cd_launch<2, 4, 1, RAC_CD_IMAGE, 8>(a, RAC_ATTR_CD_S2_8, st)
                         : (k == 2 ? cd_launch<2, 4, 1, RAC_CD_IMAGE, 2>(a, RAC_ATTR_CD_S2_2, st) : cd_launch<2, 4, 1, RAC_CD_IMAGE, 3>(a, RAC_ATTR_CD_S2_3, st));
         } else {
             RAC_CHECK_ARG(k == 2, "rac_conv_direct_fwd: stride-1 image mode is instantiated for 2 input chunks, got %d", k);
-            rc = cd_launch<1, 4, 4, RAC_CD_IMAGE, 2>(a, RAC_ATTR_CD_IMG_2, st);
+            rc = d->mode == RAC_CD_IMAGE ? cd_launch<1, 4, 4, RAC_CD_IMAGE, 2>(a, RAC_ATTR_CD_IMG_2, st)
+                                         : cd_launch<1, 4, 4, RAC_CD_IMAGE, 2, 1>(a, RAC_ATTR_CD_IMG_2_RELU, st);
         }
         return rc ? rc : rac_launch_status("rac_conv_direct_fwd(image)");
     }
     RAC_CHECK_ARG(d->out_f32 && d->conv_stride == 1, "rac_conv_direct_fwd: the f32 mode needs out_f32 and stride 1");
+    if (d->mode == RAC_CD_F32_CF_RELU) {
+        RAC_CHECK_ARG(k == 2 && !d->pixel_map, "rac_conv_direct_fwd: the channel-first ReLU mode is built for 2 input chunks and no pixel map, got %d", k);
+        rc = cd_launch<1, 4, 2, RAC_CD_F32, 2, 2>(a, RAC_ATTR_CD_F32_2_CF_RELU, st);
+        return rc ? rc : rac_launch_status("rac_conv_direct_fwd(f32 channel-first)");
+    }
     RAC_CHECK_ARG(k == 1 || k == 2 || k == 4, "rac_conv_direct_fwd: the f32 mode is instantiated for 1 / 2 / 4 input chunks, got %d", k);
     rc = k == 2 ? cd_launch<1, 4, 2, RAC_CD_F32, 2>(a, RAC_ATTR_CD_F32_2, st)
                 : (k == 1 ? cd_launch<1, 4, 2, RAC_CD_F32, 1>(a, RAC_ATTR_CD_F32_1, st) : cd_launch<1, 4, 2, RAC_CD_F32, 4>(a, RAC_ATTR_CD_F32_4, st));

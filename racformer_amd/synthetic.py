@@ -404,3 +404,39 @@ def make_state_dict(cfg: RigConfig, seed=0, scheme="tamed_normal"):
     _note_fan_in(shapes)
     fn = _param_values if scheme == "tamed_normal" else _param_values_torch_default
     return {k: torch.from_numpy(fn(k, shp, seed).astype(np.float32)) for k, shp in shapes.items()}
+
+
+# ------------------------------------------------------------------ radar clouds
+def make_radar_points(n_clouds, n_points, seed=0, grid=128, voxel=0.8, edge_fraction=0.1, width=7):
+    """Seeded radar clouds for the pillar encoder (racformer_amd/radar_pillars.py): a list of ``n_clouds`` float32 tensors
+    [n, ``width``] (x, y, z, then rcs / velocity-like columns) on a ``grid`` x ``grid`` map of ``voxel``-sized cells centred
+    on the origin.  ``n_points``: one count or one per cloud (0 = an empty cloud).  Of each cloud about
+      * ``edge_fraction`` lie on exact cell edges (x or y = k * voxel in float32, k over the whole grid, both borders included),
+      * ``edge_fraction`` / 2 lie just outside one of the four faces (or on the upper border itself, which is outside),
+      * a fifth crowd into three cells (more points than a pillar holds),
+    the rest is uniform over the range.  z is NOT zero (the encoder treats it as 0)."""
+    counts = [int(n_points)] * n_clouds if np.isscalar(n_points) else [int(n) for n in n_points]
+    assert len(counts) == n_clouds
+    half = np.float32(grid * voxel / 2)
+    vs = np.float32(voxel)
+    out = []
+    for i, n in enumerate(counts):
+        rng = np.random.default_rng([seed, i, 0x7ada7])
+        p = np.empty((n, width), dtype=np.float32)
+        p[:, :2] = rng.random((n, 2), dtype=np.float32) * (2 * half) - half
+        p[:, 2] = rng.random(n, dtype=np.float32) * 8 - 5
+        p[:, 3:] = rng.standard_normal((n, width - 3), dtype=np.float32) * np.float32(3.0)
+        n_edge, n_out, n_crowd = int(n * edge_fraction), int(n * edge_fraction / 2), n // 5
+        sel = rng.permutation(n)
+        e, o, c = sel[:n_edge], sel[n_edge:n_edge + n_out], sel[n_edge + n_out:n_edge + n_out + n_crowd]
+        k = rng.integers(-(grid // 2), grid // 2 + 1, size=n_edge).astype(np.float32)
+        p[e, rng.integers(0, 2, size=n_edge)] = k * vs
+        face = rng.integers(0, 4, size=n_out)
+        beyond = np.where(rng.random(n_out) < 0.5, np.float32(0), rng.random(n_out, dtype=np.float32) * np.float32(2.0))
+        p[o, face % 2] = np.where(face < 2, np.nextafter(-half, np.float32(-np.inf)) - beyond, half + beyond).astype(np.float32)
+        cells = rng.integers(0, grid, size=(3, 2))
+        which = rng.integers(0, 3, size=n_crowd)
+        p[c, :2] = ((cells[which] - grid // 2).astype(np.float32) + rng.random((n_crowd, 2), dtype=np.float32) * np.float32(0.98)
+                    + np.float32(0.01)) * vs
+        out.append(torch.from_numpy(p))
+    return out

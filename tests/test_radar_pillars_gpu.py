@@ -1,0 +1,363 @@
+"""racformer_amd/radar_pillars.py on the GPU against the restatement tests/radar_pillars_ref.py: voxelization bit for bit, pillar
+features and canvas within 4 x the restatement's own float32 error, each convolution layer teacher-forced under the criterion of
+tests/test_conv_direct_gpu.py, the whole branch under a bound derived from the weights, repeatability and graph replay.
+
+Measured on an MI355X (the tests print their figures): canvas E_ref 2.3e-5 / kernel error 2.1e-5 on the f8 rig, 3.8e-6 / 2.5e-6 on
+the 16 x 16 rig; convolution layers 2e-6 .. 1.8e-5 against allowances of 1.6e-5 .. 1.9e-4; end to end 1.6e-5 (f8) and 3.7e-6
+(16 x 16) against derived bounds of 24 and 4.4 -- the derived bound multiplies three layer gains of about 40 and is far from tight."""
+import numpy as np
+import pytest
+import torch
+
+import radar_pillars_ref as R
+from racformer_amd import _lib
+from racformer_amd import radar_pillars as RP
+from racformer_amd import synthetic as syn
+from test_conv_direct_gpu import act_scale, image_values
+from test_radar_pillars_ref import edge_points, encoder, hand_points
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RATIO = 4.0                         # the project's ratio for a reordered fp32 sum (tests/test_lss_view_gpu.py, tests/test_fused_gpu.py)
+CONV_RTOL = 4e-6                    # tests/test_conv_direct_gpu.py
+IMAGE_RES = 2.0 ** -22              # hi + lo of f16 at the image's scale, relative to the bound
+
+
+def small_clouds(seed=5):
+    return syn.make_radar_points(4, [0, 1, 40, 300], seed=seed, grid=16, edge_fraction=0.2)
+
+
+VOX_RIGS = {
+    "hand": (R.HAND, lambda: [torch.from_numpy(hand_points())]),
+    "edges": (R.F8, lambda: [torch.from_numpy(edge_points())]),
+    "small": (R.SMALL, small_clouds),
+    "small_p3": (dict(R.SMALL, max_num_points=3), small_clouds),
+    "small_cap5": (dict(R.SMALL, max_voxels=5), small_clouds),
+    "f8": (R.F8, lambda: syn.make_radar_points(2, 1500, seed=7, edge_fraction=0.1)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(VOX_RIGS))
+def test_1_voxelization_is_exact(name):
+    cfg, make = VOX_RIGS[name]
+    clouds = make()
+    want_v, want_c, want_n = R.voxelize_batch(clouds, **cfg)
+    enc = encoder(cfg, R.make_state_dict(1)).to(DEV)
+    got_v, got_n, got_c = enc.radar_voxelize([c.to(DEV) for c in clouds])
+    torch.cuda.synchronize()
+    assert got_c.dtype == torch.int32 and got_n.dtype == torch.int32
+    assert torch.equal(got_c.cpu(), want_c) and torch.equal(got_n.cpu(), want_n)
+    assert torch.equal(got_v.cpu().view(torch.int32), want_v.view(torch.int32))              # bitwise
+    if name in ("small", "small_p3"):
+        assert int(want_n.max()) == cfg["max_num_points"]                                    # overflow pillars exist
+    if name == "small_cap5":
+        assert [int((want_c[:, 0] == b).sum()) for b in range(4)] == [0, 1, 5, 5]            # the cap binds
+    # one cloud through the drop-in function: (z, y, x) coors, and the packed form's padding and counts
+    one = clouds[-1].to(DEV)
+    v1, c1, n1 = RP.hard_voxelize(one, cfg["voxel_size"], cfg["point_cloud_range"], cfg["max_num_points"], cfg["max_voxels"])
+    w1 = R.hard_voxelize(clouds[-1].numpy(), **cfg)
+    assert np.array_equal(v1.cpu().numpy(), w1[0]) and np.array_equal(c1.cpu().numpy(), w1[1]) and np.array_equal(n1.cpu().numpy(), w1[2])
+    v2, c2, n2 = enc.radar_voxel_layer(one)                                               # the module: the same call
+    assert torch.equal(v2, v1) and torch.equal(c2, c1) and torch.equal(n2, n1)
+    pts, off = RP.pack_clouds([c.to(DEV) for c in clouds])
+    pv = RP.voxelize_packed(pts, off, RP.voxel_geom(cfg["voxel_size"], cfg["point_cloud_range"]), cfg["max_num_points"], cfg["max_voxels"])
+    counts = [int((want_c[:, 0] == b).sum()) for b in range(len(clouds))]
+    assert pv.counts.cpu().tolist() == counts
+    pad = (pv.coors[:, 0] < 0).cpu()
+    assert int((~pad).sum()) == sum(counts)
+    assert bool((pv.coors.cpu()[pad] == -1).all()) and bool((pv.num_points.cpu()[pad] == 0).all()) and bool((pv.voxels.cpu()[pad] == 0).all())
+
+
+# ------------------------------------------------------------------------------------------------ pillar features and canvas
+CANVAS_RIGS = {
+    "small": (R.SMALL, lambda: small_clouds(6)),
+    "f8": (R.F8, lambda: syn.make_radar_points(2, 1500, seed=8, edge_fraction=0.1)),
+}
+
+
+def in_range_absmax(clouds, cfg):
+    """max |value| over the points inside the range (z taken as 0): the A of the image bound"""
+    lo, vs = np.asarray(cfg["point_cloud_range"][:3], np.float32), np.asarray(cfg["voxel_size"], np.float32)
+    grid = np.asarray(R.grid_of(cfg["voxel_size"], cfg["point_cloud_range"]), np.float32)
+    best = 0.0
+    for c in clouds:
+        p = c.numpy().copy()
+        p[:, 2] = 0
+        cell = np.floor((p[:, :3] - lo) / vs)
+        ok = ((cell >= 0) & (cell < grid)).all(axis=1)
+        if ok.any():
+            best = max(best, float(np.abs(p[ok]).max()))
+    return best
+
+
+def pfn_bound(sd, cfg, A):
+    """max-row L1 of the folded PFN weights * (2 A + R) + the largest positive shift, in float64 from the weights"""
+    k = "radar_voxel_encoder.pfn_layers.0."
+    g = sd[k + "norm.weight"].double() / torch.sqrt(sd[k + "norm.running_var"].double() + 1e-3)
+    shift = sd[k + "norm.bias"].double() - sd[k + "norm.running_mean"].double() * g
+    l1 = float((sd[k + "linear.weight"].double().abs().sum(dim=1) * g.abs()).max())
+    Rr = max(abs(float(v)) for v in cfg["point_cloud_range"])
+    return l1 * (2 * A + Rr) + max(float(shift.max()), 0.0)
+
+
+@pytest.mark.parametrize("name", sorted(CANVAS_RIGS))
+def test_2_canvas_and_image(name):
+    """canvas against float64 within 4 x E_ref; empty cells exactly 0; the image destination equals the canvas within the image
+    format's resolution, its border is 0, and a second call with fewer pillars leaves nothing behind."""
+    cfg, make = CANVAS_RIGS[name]
+    clouds = make()
+    sd = R.make_state_dict(2)
+    enc = encoder(cfg, sd).to(DEV)
+    v, c, n = R.voxelize_batch(clouds, zero_z=True, **cfg)
+    c64, e_ref = R.canvas_e_ref(sd, cfg, v, c, n, len(clouds))
+    pts, off = RP.pack_clouds([p.to(DEV) for p in clouds], zero_z=True)
+    canvas = enc.canvas_packed(pts, off)
+    torch.cuda.synchronize()
+    err = float((canvas.double().cpu() - c64).abs().max())
+    print(f"canvas[{name}]: E_ref {e_ref:.3g}, kernel {err:.3g} (allowed {RATIO * e_ref:.3g})")
+    assert err <= RATIO * e_ref
+    occupied = torch.zeros(len(clouds), c64.shape[2], c64.shape[3], dtype=torch.bool)
+    occupied[c[:, 0].long(), c[:, 2].long(), c[:, 3].long()] = True
+    assert bool((canvas.cpu().permute(0, 2, 3, 1)[~occupied] == 0).all())
+    # PillarFeatureNet.forward alone: the pillar rows
+    feats = enc.radar_voxel_encoder(v.to(DEV), n.to(DEV), c.to(DEV))
+    want = R.Stages(sd, torch.float64, **cfg).pillar_features(v, c, n)
+    assert float((feats.double().cpu() - want).abs().max()) <= RATIO * e_ref
+
+    def image_of(cl):
+        from racformer_amd.fused import act_image
+        gx, gy, _ = enc.radar_voxel_layer.geom.grid
+        p, o = RP.pack_clouds([q.to(DEV) for q in cl], zero_z=True)
+        pv = RP.voxelize_packed(p, o, enc.radar_voxel_layer.geom, cfg["max_num_points"], cfg["max_voxels"])
+        img = act_image("t_radar_pfn", len(cl), gy, gx, 64, torch.device(DEV))
+        cv = torch.empty(len(cl), 64, gy, gx, device=DEV)
+        enc.radar_voxel_encoder.encode(pv.voxels, pv.coors, pv.num_points, len(cl), gy, gx, amax=pv.amax, canvas=cv, image=img)
+        torch.cuda.synchronize()
+        A = in_range_absmax(cl, cfg)
+        assert float(pv.amax) == np.float32(A)
+        mul, add = enc.radar_voxel_encoder.image_bound()
+        bound = pfn_bound(sd, cfg, A)
+        assert abs(mul * A + add - bound) <= 1e-5 * bound                     # the module's bound is the derived one
+        vals, border = image_values(img, act_scale(float(np.float32(mul) * np.float32(A) + np.float32(add))))
+        return vals, border, cv.double().cpu(), bound
+
+    vals, border, cv, bound = image_of(clouds)
+    assert torch.equal(cv.float(), canvas.cpu())                              # both destinations of one launch agree, bit for bit
+    assert border == 0.0 and float(cv.max()) <= bound
+    assert float((vals - cv).abs().max()) <= IMAGE_RES * bound
+    fewer = [p[: p.shape[0] // 3] for p in clouds]
+    vals2, border2, cv2, bound2 = image_of(fewer)
+    assert border2 == 0.0 and float((vals2 - cv2).abs().max()) <= IMAGE_RES * bound2
+    assert int((cv2 != 0).sum()) < int((cv != 0).sum()) and bool((vals2[cv2 == 0] == 0).all())      # no stale cell
+
+
+# ------------------------------------------------------------------------------------------------ convolution layers
+def ragged_stage_inputs(sd):
+    """a 12 x 20 map (range 16 m x 9.6 m): uniform points, two clouds"""
+    cfg = dict(R.SMALL, point_cloud_range=[-8.0, -4.8, -5.0, 8.0, 4.8, 3.0])
+    rng = np.random.default_rng(12)
+    clouds = [torch.from_numpy((rng.random((n, 7), dtype=np.float32) * np.float32(2) - 1) * np.asarray([8, 4.8, 1, 3, 3, 3, 3], np.float32))
+              for n in (150, 60)]
+    return cfg, clouds
+
+
+@pytest.fixture(scope="module")
+def stage_rigs():
+    """name -> (float64 Stages, [stage inputs float64 x 4]): the oracle's stages, computed once"""
+    sd = R.make_state_dict(4)
+    out = {}
+    for name, cfg, clouds in (("16x16", R.SMALL, small_clouds(3)[1:]), ("12x20",) + ragged_stage_inputs(sd),
+                              ("128x128", R.F8, syn.make_radar_points(1, 1500, seed=9))):
+        st = R.Stages(sd, torch.float64, **cfg)
+        v, c, n = R.voxelize_batch(clouds, zero_z=True, **cfg)
+        out[name] = (st, st.stack_stages(st.canvas(v, c, n, len(clouds))))
+    return sd, out
+
+
+@pytest.mark.parametrize("layer", [0, 1, 2])
+@pytest.mark.parametrize("name", ["16x16", "12x20", "128x128"])
+def test_3_conv_layer_teacher_forced(stage_rigs, name, layer):
+    """relu(BN(conv(x))) of the oracle's previous stage, in float64, against the kernel on the same input: layers 0 and 1 into an
+    activation image (RAC_CD_IMAGE_RELU), layer 2 channel-first fp32 (rac_conv3x3_relu_cf_fwd and RAC_CD_F32_CF_RELU)."""
+    from racformer_amd.fused import ConvImage, act_image
+    sd, rigs = stage_rigs
+    st, stages = rigs[name]
+    x = stages[layer].float()
+    frames, _, H, W = x.shape
+    want = st.conv_layer(layer, x.double())
+    conv, bn = torch.nn.Conv2d(64, want.shape[1], 3, padding=1, bias=False), torch.nn.BatchNorm2d(want.shape[1])
+    conv.load_state_dict({"weight": sd[f"radar_bev_conv.{layer}.conv.weight"]})
+    bn.load_state_dict({k: sd[f"radar_bev_conv.{layer}.bn.{k}"] for k in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")})
+    packed = RP.pack_conv_bn(conv.to(DEV), bn.to(DEV).eval())
+    xg = x.to(DEV)
+    img = ConvImage(frames, H, W, 64, torch.device(DEV))
+    img.begin([xg]).pack(xg, 0)
+    scale = (img.amax, 1.0, 0.0)
+    if layer == 2:
+        # the LDS-staged kernel (rac_conv3x3_relu_cf_fwd, what the encoder uses at 256 channels) and the direct one
+        got = RP.conv_bn_relu(packed, img.xs, scale, frames, H, W, out=torch.empty(frames, 256, H, W, device=DEV)).double().cpu()
+        direct = RP.conv_bn_relu(packed, img.xs, scale, frames, H, W, out=torch.empty(frames, 256, H, W, device=DEV), staged=False)
+        assert float((direct.double().cpu() - want).abs().max()) <= CONV_RTOL * float(want.abs().max())
+    else:
+        out = act_image("t_radar_conv", frames, H, W, 64, torch.device(DEV))
+        s_out = RP.next_scale(scale, packed)
+        RP.conv_bn_relu(packed, img.xs, scale, frames, H, W, out_img=out, out_scale=s_out)
+        torch.cuda.synchronize()
+        got, border = image_values(out, act_scale(float(np.float32(s_out[1]) * np.float32(float(img.amax)) + np.float32(s_out[2]))))
+        assert border == 0.0
+    err, top = float((got - want).abs().max()), float(want.abs().max())
+    print(f"conv layer {layer} [{name}]: error {err:.3g}, allowed {CONV_RTOL * top:.3g}")
+    assert top > 0 and err <= CONV_RTOL * top
+
+
+def test_4_existing_conv_modes_unchanged(stage_rigs):
+    """RAC_CD_F32 and RAC_CD_IMAGE, which share the kernel source with the two new modes: still within the float64 criterion, and
+    the new modes are exactly their ReLU (the same accumulators: bit for bit)."""
+    from racformer_amd.fused import ConvImage, act_image, conv_direct
+    sd, rigs = stage_rigs
+    st, stages = rigs["12x20"]
+    x = stages[1].float()
+    frames, _, H, W = x.shape
+    conv = torch.nn.Conv2d(64, 64, 3, padding=1)
+    conv.load_state_dict({"weight": sd["radar_bev_conv.1.conv.weight"], "bias": sd["radar_bev_conv.1.bn.bias"]})
+    want = torch.nn.functional.conv2d(x.double(), conv.weight.double(), conv.bias.double(), padding=1).detach()
+    from racformer_amd.fused import pack_conv3x3_weight
+    ws, alpha = pack_conv3x3_weight(conv.weight.to(DEV), cout=64)
+    bias = conv.bias.detach().to(DEV)
+    xg = x.to(DEV)
+    img = ConvImage(frames, H, W, 64, torch.device(DEV))
+    img.begin([xg]).pack(xg, 0)
+    scale = (img.amax, 1.0, 0.0)
+    l1, bmax = float(conv.weight.detach().abs().sum(dim=(1, 2, 3)).max()), float(bias.abs().max())
+    s_out = (img.amax, l1, bmax)
+    cl = torch.empty(frames, H * W, 64, device=DEV)
+    conv_direct(_lib.CD_F32, frames, H, W, img.xs, 2, 2, ws, alpha, 64, scale, bias=bias, out_f32=cl)
+    cf = torch.empty(frames, 64, H, W, device=DEV)
+    conv_direct(_lib.CD_F32_CF_RELU, frames, H, W, img.xs, 2, 2, ws, alpha, 64, scale, bias=bias, out_f32=cf)
+    a, b = act_image("t_radar_m0", frames, H, W, 64, torch.device(DEV)), act_image("t_radar_m3", frames, H, W, 64, torch.device(DEV))
+    conv_direct(_lib.CD_IMAGE, frames, H, W, img.xs, 2, 2, ws, alpha, 64, scale, bias=bias, out_img=a, out_chunks_total=2, out_scale=s_out)
+    conv_direct(_lib.CD_IMAGE_RELU, frames, H, W, img.xs, 2, 2, ws, alpha, 64, scale, bias=bias, out_img=b, out_chunks_total=2, out_scale=s_out)
+    torch.cuda.synchronize()
+    tol = CONV_RTOL * float(want.abs().max())
+    got_cl = cl.view(frames, H, W, 64).permute(0, 3, 1, 2)
+    assert float((got_cl.double().cpu() - want).abs().max()) <= tol
+    so = act_scale(l1 * float(img.amax) + bmax)
+    va, border_a = image_values(a, so)
+    vb, border_b = image_values(b, so)
+    assert border_a == 0.0 and border_b == 0.0 and float((va - want).abs().max()) <= tol
+    assert bool((want < 0).any()) and torch.equal(torch.relu(got_cl), cf) and torch.equal(torch.relu(va), vb)
+
+
+def test_4b_staged_kernel_old_epilogue_unchanged(stage_rigs):
+    """rac_conv3x3_fwd (channel-last, no ReLU), which shares its kernel source with rac_conv3x3_relu_cf_fwd: still within the
+    float64 criterion on a ragged 12 x 20 map, and the new entry point is exactly its ReLU, transposed."""
+    from racformer_amd.fused import ConvImage, pack_conv3x3_weight
+    sd, rigs = stage_rigs
+    _, stages = rigs["12x20"]
+    x = stages[2].float()
+    frames, _, H, W = x.shape
+    w = sd["radar_bev_conv.2.conv.weight"]
+    bias = sd["radar_bev_conv.2.bn.bias"].to(DEV).contiguous()
+    want = torch.nn.functional.conv2d(x.double(), w.double(), bias.double().cpu(), padding=1)
+    ws, alpha = pack_conv3x3_weight(w.to(DEV))
+    xg = x.to(DEV)
+    img = ConvImage(frames, H, W, 64, torch.device(DEV))
+    img.begin([xg]).pack(xg, 0)
+    old = img.conv(ws, alpha, bias).permute(0, 3, 1, 2)
+    new = RP.conv_bn_relu((ws, alpha, bias, 0.0, 0.0), img.xs, (img.amax, 1.0, 0.0), frames, H, W, out=torch.empty(frames, 256, H, W, device=DEV))
+    assert float((old.double().cpu() - want).abs().max()) <= CONV_RTOL * float(want.abs().max())
+    assert bool((want < 0).any()) and torch.equal(torch.relu(old), new)
+
+
+# ------------------------------------------------------------------------------------------------ end to end
+E2E_RIGS = {
+    "small_b2_t3": (R.SMALL, 2, 3, lambda: syn.make_radar_points(6, [200, 0, 300, 1, 120, 40], seed=13, grid=16, edge_fraction=0.2)),
+    "f8_b1_t2": (R.F8, 1, 2, lambda: syn.make_radar_points(2, 1500, seed=14, edge_fraction=0.1)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(E2E_RIGS))
+def test_5_end_to_end(name):
+    """points -> [B, T, 256, H, W] against the float64 restatement's torch.stack(..., dim=1).  The bound is derived: the sum over
+    the four stages of the stage's own tolerance (canvas: 4 x E_ref + the image format's resolution of the pillar bound; each
+    convolution layer: 4e-6 of its float64 output's maximum), each multiplied by the product of the later layers' max-row L1
+    norms of the folded weights (ReLU is 1-Lipschitz in the max norm)."""
+    cfg, B, T, make = E2E_RIGS[name]
+    clouds = make()
+    frames = [[clouds[t * B + b] for b in range(B)] for t in range(T)]
+    sd = R.make_state_dict(5)
+    enc = encoder(cfg, sd).to(DEV)
+    before = [c.clone() for c in clouds]
+    got = enc([[c.to(DEV) for c in fr] for fr in frames])
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(clouds, before))
+    want, stages = R.forward(sd, cfg, frames, torch.float64)
+    H, W = want.shape[-2:]
+    assert got.shape == (B, T, 256, H, W) and got.dtype == torch.float32 and got.is_contiguous()
+    st = R.Stages(sd, torch.float64, **cfg)
+    e_ref = 0.0
+    for fr in frames:
+        v, c, n = R.voxelize_batch(fr, zero_z=True, **cfg)
+        e_ref = max(e_ref, R.canvas_e_ref(sd, cfg, v, c, n, B)[1])
+    tol = [RATIO * e_ref + IMAGE_RES * pfn_bound(sd, cfg, in_range_absmax(clouds, cfg))]
+    tol += [CONV_RTOL * max(float(s[i + 1].abs().max()) for s in stages) for i in range(3)]
+    gain = [st.folded_conv_l1(i) for i in range(3)]
+    bound = tol[0] * gain[0] * gain[1] * gain[2] + tol[1] * gain[1] * gain[2] + tol[2] * gain[2] + tol[3]
+    err = float((got.double().cpu() - want).abs().max())
+    print(f"end to end [{name}]: error {err:.3g}, derived bound {bound:.3g} (stage tolerances {tol}, gains {gain})")
+    assert err <= bound
+    if name == "small_b2_t3":
+        # cloud 1 (t = 0, b = 1) is empty: its frame is the stack's response to zeros
+        zeros = st.stack_stages(torch.zeros(1, 64, H, W, dtype=torch.float64))[-1][0]
+        conv_only = tol[1] * gain[1] * gain[2] + tol[2] * gain[2] + tol[3]
+        assert float((got[1, 0].double().cpu() - zeros).abs().max()) <= conv_only
+        # extract_pts_feat: one frame, the same numbers
+        one = enc.extract_pts_feat([c.to(DEV) for c in frames[1]])
+        assert torch.equal(one, got[:, 1])
+        # a call that holds exactly one pillar, and one that holds none
+        single = enc.extract_pts_feat([clouds[3].to(DEV)])
+        assert float((single.double().cpu() - R.forward(sd, cfg, [[clouds[3]]], torch.float64)[0][:, 0]).abs().max()) <= bound
+        none = enc.extract_pts_feat([clouds[1].to(DEV)])
+        assert float((none[0].double().cpu() - zeros).abs().max()) <= conv_only
+    # the torch-ops route on the device computes the same branch
+    loose = encoder(cfg, sd, fused=False).to(DEV)([[c.to(DEV) for c in fr] for fr in frames])
+    assert float((loose.double().cpu() - want).abs().max()) <= bound
+
+
+def test_6_bitwise_repeatable_and_graph_replay():
+    """Two eager runs give the same bits; a single-stream capture replays to the eager result, also after the packed cloud
+    buffer was overwritten in place with other points (same row bound, other pillar counts: the counts live on the device)."""
+    cfg = R.SMALL
+    sd = R.make_state_dict(6)
+    enc = encoder(cfg, sd).to(DEV)
+    a = [c.to(DEV) for c in syn.make_radar_points(3, [300, 0, 100], seed=20, grid=16, edge_fraction=0.2)]
+    b = [c.to(DEV) for c in syn.make_radar_points(3, [60, 200, 140], seed=21, grid=16, edge_fraction=0.2)]
+    pa, oa = RP.pack_clouds(a, zero_z=True)
+    pb, ob = RP.pack_clouds(b, zero_z=True)
+    assert pa.shape == pb.shape
+    geom = enc.radar_voxel_layer.geom
+    counts = [RP.voxelize_packed(p, o, geom, cfg["max_num_points"], cfg["max_voxels"]).counts.cpu().tolist() for p, o in ((pa, oa), (pb, ob))]
+    assert counts[0] != counts[1]
+    want_a, again = enc.encode_packed(pa, oa).clone(), enc.encode_packed(pa, oa).clone()
+    assert torch.equal(want_a, again)
+    want_b = enc.encode_packed(pb, ob).clone()
+    assert not torch.equal(want_a, want_b)
+    s_p, s_o = pa.clone(), oa.clone()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side), torch.no_grad():
+        for _ in range(2):
+            enc.encode_packed(s_p, s_o)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph), torch.no_grad():
+        got = enc.encode_packed(s_p, s_o)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(got, want_a)
+    s_p.copy_(pb)
+    s_o.copy_(ob)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(got, want_b)

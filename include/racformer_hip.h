@@ -77,7 +77,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 24
+#define RAC_ABI_VERSION 25
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -897,6 +897,55 @@ int rac_lss_splat_fwd(const float *logits, const float *stats, const float *feat
                       float *out, int n_points, int B, int C, int X, int Y, int Z, void *stream);
 int rac_lss_view_bwd(const float *grad_cell, const float *logits, const float *stats, const float *feat,
                      const int32_t *cells, float *grad_feat, float *grad_logits, int BN, int C, int D, int HW, void *stream);
+
+/* ---- LSS depth branch: radar depth / RCS priors and the depth loss (models/necks/view_transformer_racformer.py:593-699
+ * get_downsampled_depth / get_downsampled_rcs / get_depth_loss / forward, models/necks/focalloss.py:114-125) ------------------
+ * Maps are [BN, H, W] f32, feature pixels [BN, h, w] with h = H / ds, w = W / ds; index maps int32.  All pointers are device
+ * pointers.  Every launch is sized by shapes, nothing is read back, no floating-point sum is atomic: capturable into a graph and
+ * bitwise reproducible.
+ *
+ * rac_lss_pool_bins_fwd: one pass over the full-resolution maps, each value read once from the [BN, H, W] layout.
+ *   depth (or NULL) -> pooled [BN,h,w] f32: min over the ds x ds block with zeros replaced by 1e5; NaN if any element is NaN
+ *                      bins   [BN,h,w]: idx = -0.5 + 0.5 sqrt(1 + 8 (d - depth_lo) / depth_bin_size) in IEEE f32 (true division,
+ *                      correctly rounded square root), truncated toward zero; depth_bins where idx < 0, idx > depth_bins or idx
+ *                      is not finite.  depth_bin_size = float(2 (hi - lo) / (n (n + 1))), computed in double by the caller.
+ *   rcs (or NULL)   -> rcs_class [BN,h,w]: m = max over the block with values < rcs_lo replaced by -1e5 (NaN wins);
+ *                      r = (m - rcs_offset) / rcs_bin_size with rcs_offset = float(lo - bin), rcs_bin_size = float(bin);
+ *                      class max(trunc(r) - 1, -1) for -1 <= r < rcs_bins + 1, else -1.  Class -1 (an all-below-range block, a
+ *                      maximum >= hi, NaN) is "no class": an all-zero one-hot row, where the reference's F.one_hot raises.
+ *   H % ds == 0, W % ds == 0, 1 <= ds <= 1024 (RAC_E_UNSUPPORTED beyond).
+ *
+ * rac_lss_prior_fwd: out [BN, (D+1)+E, hw], the tensor DepthNet.forward concatenates behind its features (:558):
+ *   channels 0..D   the one-hot radar depth grid: 1 where bins == channel (rad_dep_grids, :690-693)
+ *   channels D+1..  weight[e, class] + bias[e], bias[e] alone for class -1: the 1x1 rcs_embedding of the one-hot RCS map,
+ *                   which is never built.  weight [E, n_rcs], bias [E].
+ *
+ * rac_lss_prior_bwd: grad_out [BN, (D+1)+E, hw] -> grad_weight [E, n_rcs] (sum over the pixels of each class), grad_bias [E]
+ *   (sum over all pixels); both fully written.  The pixels are cut into up to 32 contiguous runs (8 segments of 4), each summed
+ *   in ascending pixel order, the runs added in ascending order (a second launch adds the segments); grad_bias is the sum of a
+ *   run's class sums in a fixed tree.  The one-hot channels carry no gradient.  workspace: 8 * E * (n_rcs + 1) f32 scratch.
+ *   n_rcs <= 256.
+ *
+ * rac_lss_depth_loss_fwd: logits [BN, D, hw] (channel-first), labels [BN*hw] (foreground: 0 <= label < D) ->
+ *   per foreground pixel l = sum_c (onehot_c + 1e-6) (-alpha) (1 - p_c)^2 log p_c on softmax / log-softmax (focalloss.py with
+ *   its one_hot(eps = 1e-6)); gamma must be 2 (RAC_E_UNSUPPORTED otherwise).
+ *   grad_unit [BN, D, hw] = dl / dlogits, unscaled; zeros at background pixels
+ *   pixel_loss [BN*hw] or NULL: l itself, 0 at background pixels
+ *   partial   [ceil(BN*hw / 64), 2] scratch: (sum of l, foreground count) per workgroup, combined in index order by a second launch
+ *   loss [1]  = weight * sum / max(1, count);   scale [1] = weight / max(1, count)
+ *
+ * rac_lss_depth_loss_bwd: grad_logits [n] = grad_unit * (scale[0] * grad_loss[0]); the three operands stay on the device. */
+int rac_lss_pool_bins_fwd(const float *depth, const float *rcs, float *pooled, int32_t *bins, int32_t *rcs_class, int BN, int H,
+                          int W, int ds, float depth_lo, float depth_bin_size, int depth_bins, float rcs_lo, float rcs_offset,
+                          float rcs_bin_size, int rcs_bins, void *stream);
+int rac_lss_prior_fwd(const int32_t *bins, const int32_t *rcs_class, const float *weight, const float *bias, float *out, int BN,
+                      int hw, int D, int E, int n_rcs, void *stream);
+int rac_lss_prior_bwd(const float *grad_out, const int32_t *rcs_class, float *workspace, float *grad_weight, float *grad_bias, int BN,
+                      int hw, int D, int E, int n_rcs, void *stream);
+int rac_lss_depth_loss_fwd(const float *logits, const int32_t *labels, float *partial, float *grad_unit, float *pixel_loss,
+                           float *loss, float *scale, int BN, int D, int hw, float alpha, float gamma, float weight, void *stream);
+int rac_lss_depth_loss_bwd(const float *grad_unit, const float *scale, const float *grad_loss, float *grad_logits, int64_t n,
+                           void *stream);
 
 /* ---- Radar pillar encoder: point clouds to the BEV canvas (models/racformer.py:130-177 extract_pts_feat / radar_voxelize; mmcv 1.6.0
  * Voxelization (hard), mmdet3d 1.0.0rc6 PillarFeatureNet and PointPillarsScatter; configs/racformer_r50_nuimg_704x256_f8.py:122-139) ----

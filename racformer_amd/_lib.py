@@ -96,6 +96,11 @@ SIGNATURES = {
     "rac_lss_transpose_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "rac_lss_splat_fwd": (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
     "rac_lss_view_bwd": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
+    "rac_lss_pool_bins_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_f, _f, _i, _f, _f, _f, _i, _vp]),
+    "rac_lss_prior_fwd": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
+    "rac_lss_prior_bwd": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
+    "rac_lss_depth_loss_fwd": (_i, [_vp] * 7 + [_i] * 3 + [_f] * 3 + [_vp]),
+    "rac_lss_depth_loss_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
     "rac_pillar_voxelize_fwd": (_i, [_vp] * 8 + [_i] * 3 + [_f] * 6 + [_i] * 5 + [_vp]),
     "rac_pillar_encode_fwd": (_i, [_vp] * 6 + [_f, _f, _vp, _vp, _vp] + [_i] * 5 + [_f] * 6 + [_i, _i, _vp]),
 }

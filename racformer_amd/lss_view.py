@@ -9,8 +9,8 @@ The output is [B, Z*C, Y, X] with channel index z*C + c, the order of ``voxel_po
 ``torch.cat(bev_feat.unbind(dim=2), 1)``.  Points of one cell are summed in ascending ``ranks_depth`` (the reference's
 ``argsort`` leaves that order unspecified); two runs give the same bits.
 
-Out of scope here: DepthNet / ASPP / SE layers, the radar depth and RCS inputs, the depth loss, and the subclass
-``LSSViewTransformerBEVDepth_racformer`` beyond what it inherits.
+Out of scope here: DepthNet / ASPP / SE layers.  The radar depth and RCS inputs, the depth loss and the subclass
+``LSSViewTransformerBEVDepth_racformer`` are in ``racformer_amd/lss_depth.py``.
 """
 from collections import namedtuple
 

@@ -221,6 +221,28 @@ def make_lss_view_inputs(n_cams=6, batch=1, input_hw=(256, 704), downsample=16, 
                 depth_digit=torch.from_numpy(logits), tran_feat=torch.from_numpy(feat))
 
 
+def make_lss_depth_inputs(n_maps=6, input_hw=(256, 704), downsample=16, depth_range=(0.0, 70.0), rcs_range=(-80.0, 64.0),
+                          radar_density=0.02, lidar_density=0.1, rcs_floor=-100.0, every_block_has_rcs=True, seed=0):
+    """Seeded inputs of the LSS depth branch: ``radar_depth`` and ``lidar_depth`` [n_maps, H, W] float32, zero where there is no
+    return and uniform on ``depth_range`` elsewhere (a share ``radar_density`` / ``lidar_density`` of the pixels), and
+    ``radar_rcs``: ``rcs_floor`` where there is no return, uniform on ``rcs_range`` at the radar's pixels.
+    ``every_block_has_rcs``: one pixel of every downsample x downsample block (its position varies) gets an RCS value inside
+    [-64, 64), so that no block is without a class (the reference's ``F.one_hot`` raises on such a block)."""
+    rng = np.random.default_rng(seed * 1000 + 81)
+    H, W = input_hw
+    shape = (n_maps, H, W)
+    hit = rng.random(shape) < radar_density
+    radar = np.where(hit, rng.uniform(*depth_range, shape), 0.0).astype(np.float32)
+    rcs = np.where(hit, rng.uniform(*rcs_range, shape), rcs_floor).astype(np.float32)
+    lidar = np.where(rng.random(shape) < lidar_density, rng.uniform(*depth_range, shape), 0.0).astype(np.float32)
+    if every_block_has_rcs:
+        h, w, ds = H // downsample, W // downsample, downsample
+        n, i, j = np.meshgrid(np.arange(n_maps), np.arange(h), np.arange(w), indexing="ij")
+        di, dj = rng.integers(0, ds, n.shape), rng.integers(0, ds, n.shape)
+        rcs[n, i * ds + di, j * ds + dj] = rng.uniform(-64.0, 63.99, n.shape).astype(np.float32)
+    return dict(radar_depth=torch.from_numpy(radar), radar_rcs=torch.from_numpy(rcs), lidar_depth=torch.from_numpy(lidar))
+
+
 # ------------------------------------------------------------------ queries
 def head_query_grid(cfg: RigConfig):
     """Polar query grid of RaCFormer_head._init_layers / generate_points

@@ -67,6 +67,7 @@
  *   rac_lsap_fwd / rac_lsap_host <- scipy.optimize.linear_sum_assignment as the assigners call it (:84)
  *   rac_det_loss_fwd  <- the targets, FocalLoss and L1Loss of loss_single / dn_loss_single with their autograd backwards
  *                        models/racformer_head.py:264-300, 326-427
+ *   rac_conv_small_* / rac_depthnet_* <- DepthNet.forward (use_dcn=False), models/necks/view_transformer_racformer.py:329-567
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -77,7 +78,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 25
+#define RAC_ABI_VERSION 26
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -986,6 +987,61 @@ int rac_pillar_encode_fwd(const float *voxels, const int32_t *coors, const int32
                           int n_clouds,
                           int C, int max_num_points, int F, float vs_x, float vs_y, float vs_z, float center_x, float center_y,
                           float center_z, int H, int W, void *stream);
+
+/* ---- DepthNet (models/necks/view_transformer_racformer.py:329-567, use_dcn=False), eval mode, BatchNorms folded by the caller:
+ * a convolution for many small maps and the per-image vectors around it (csrc/depth_net.hip).  Activations between layers are
+ * channel-last f32 rows: pixel (n, p) of a [BN, h, w] batch is row n * hw + p of ld floats.  All arithmetic is fp32 (the f32-input
+ * MFMA: an fmaf chain over each 32 input channels of a tap, the chains added in ascending (tap, channel) order); every sum has one fixed order, nothing is atomic, nothing is read back: capturable, bitwise reproducible.
+ *
+ * rac_conv_small_pack_fwd: src [BN, C, hw] channel-first -> dst rows of ld_dst floats, channels c_off .. c_off + C - 1, and zeros in
+ *   the c_pad channels behind them (padding a concatenation to the convolution's multiple of 32).  c_off + C + c_pad <= ld_dst.
+ *
+ * rac_conv_small_fwd: out = epilogue(conv(gate * in)) for one layer, described by rac_conv_small:
+ *   in, ld_in      channel-last rows, the first Cin channels of each are read; ld_in >= Cin, a multiple of 4, in 16-byte aligned
+ *   BN, H, W       maps and their size; a workgroup owns 64 pixels of one map x 64 output channels
+ *   Cin            a multiple of 32, up to 4096 (ASPP.conv1 reads its 1024 concatenated channels in one pass)
+ *   ksize          1, or 3 with padding = dilation (dilation >= 1); a tap whose offset is >= H rows or >= W columns is skipped
+ *   w, ld_w        f32 [ksize * ksize][Cin][ld_w], tap ky * 3 + kx, element [tap][ci][co] = weight[co][ci][ky][kx]; ld_w a multiple
+ *                  of 64 >= Cout (columns >= Cout are read and must exist; zeros by convention), 16-byte aligned
+ *   Cout           output channels (any count >= 1)
+ *   gate           NULL or f32 [BN][gate_channels]: input channel c < gate_channels of map n is multiplied by gate[n][c] while it is
+ *                  staged (SE gating without per-image weights); gate_channels a multiple of 32 <= Cin
+ *   epilogue, in this order, each part optional (NULL):  + bias[co]  + img_bias[n][co]  + bins_table[bins[pix]][co] for
+ *                  0 <= bins[pix] < n_bins (table [n_bins][Cout]: a one-hot input's 1x1 term as a column lookup)
+ *                  + cls_table[cls[pix] + 1][co], row 0 for a class outside 0 .. n_cls - 1 (table [n_cls + 1][Cout])
+ *                  + residual[pix][co] (channel-last rows of ld_res floats)   then ReLU if relu != 0
+ *   out            RAC_CS_CHANNEL_LAST: rows of ld_out floats, channels c_off .. c_off + Cout - 1 (the next layer's operand: a
+ *                  concatenation is written in place, never copied);  RAC_CS_CHANNEL_FIRST: [BN][ld_out][hw], channels from c_off
+ *   Any violation is RAC_E_ARG before any launch.
+ *
+ * rac_depthnet_gates_fwd: gates [branches][BN][C] = sigmoid(We relu(Wr (W2 relu(W1 x + b1) + b2) + br) + be) for x = mlp_input[n]
+ *   (f32 [BN][9]; the BatchNorm1d in front folded into W1, b1): Mlp and the SE tail of one DepthNet branch per params block
+ *   w1t [9][C] | b1 [C] | w2t [C][C] | b2 [C] | wrt [C][C] | br [C] | wet [C][C] | be [C], matrices [in][out]; C <= 1024.
+ *
+ * rac_depthnet_pool_bias_fwd: ASPP's image-pool branch as a per-image bias of ASPP.conv1: m = mean over the hw rows of map n of x
+ *   (channel-last rows of ld floats, C channels; up to 1024 / C pixel segments summed in ascending order, then added in ascending
+ *   order), y = relu(wpool_t^T m + bpool), img_bias[n][co] = sum_k wbias_t[k][co] y[k].  wpool_t [C][C], wbias_t [C][Cout], [in][out]. */
+enum { RAC_CS_CHANNEL_LAST = 0, RAC_CS_CHANNEL_FIRST = 1 };
+typedef struct {
+    const float *in;
+    const float *w;
+    const float *bias;
+    const float *img_bias;
+    const float *gate;
+    const float *residual;
+    const int32_t *bins;
+    const float *bins_table;
+    const int32_t *cls;
+    const float *cls_table;
+    float *out;
+    int BN, H, W, Cin, Cout, ksize, dilation;
+    int ld_in, ld_w, gate_channels, ld_res, n_bins, n_cls, relu, out_layout, ld_out, c_off;
+} rac_conv_small;
+int rac_conv_small_pack_fwd(const float *src, float *dst, int BN, int C, int hw, int ld_dst, int c_off, int c_pad, void *stream);
+int rac_conv_small_fwd(const rac_conv_small *d, void *stream);
+int rac_depthnet_gates_fwd(const float *mlp_input, const float *params, float *gates, int BN, int C, int branches, void *stream);
+int rac_depthnet_pool_bias_fwd(const float *x, const float *wpool_t, const float *bpool, const float *wbias_t, float *img_bias, int BN,
+                               int hw, int ld, int C, int Cout, void *stream);
 
 #ifdef __cplusplus
 }

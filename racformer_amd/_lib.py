@@ -103,6 +103,10 @@ SIGNATURES = {
     "rac_lss_depth_loss_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
     "rac_pillar_voxelize_fwd": (_i, [_vp] * 8 + [_i] * 3 + [_f] * 6 + [_i] * 5 + [_vp]),
     "rac_pillar_encode_fwd": (_i, [_vp] * 6 + [_f, _f, _vp, _vp, _vp] + [_i] * 5 + [_f] * 6 + [_i, _i, _vp]),
+    "rac_conv_small_pack_fwd": (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
+    "rac_conv_small_fwd": (_i, [_vp, _vp]),
+    "rac_depthnet_gates_fwd": (_i, [_vp] * 3 + [_i] * 3 + [_vp]),
+    "rac_depthnet_pool_bias_fwd": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
 }
 
 
@@ -141,6 +145,16 @@ class ConvDirect(ctypes.Structure):
 
 
 CD_IMAGE, CD_F32, CD_GRU, CD_IMAGE_RELU, CD_F32_CF_RELU = 0, 1, 2, 3, 4
+
+
+class ConvSmall(ctypes.Structure):
+    """rac_conv_small (include/racformer_hip.h)"""
+    _fields_ = [(n, _vp) for n in ("in_", "w", "bias", "img_bias", "gate", "residual", "bins", "bins_table", "cls", "cls_table", "out")] \
+        + [(n, _i) for n in ("BN", "H", "W", "Cin", "Cout", "ksize", "dilation", "ld_in", "ld_w", "gate_channels", "ld_res", "n_bins",
+                             "n_cls", "relu", "out_layout", "ld_out", "c_off")]
+
+
+CS_CHANNEL_LAST, CS_CHANNEL_FIRST = 0, 1
 
 
 def lib():

@@ -10,7 +10,8 @@ Three layers:
   restatement  ``pool_bins_torch``, ``radar_prior_torch``, ``softmax_focal_loss``, ``depth_loss_torch`` -- the reference's tensor
                operations on any device in the inputs' dtype (the CPU route, and what the kernels are compared and timed against)
   module       ``LSSViewTransformerBEVDepth_racformer`` with the reference's constructor arguments, method signatures and
-               state-dict keys; ``DepthNet`` itself (mmcv's DCN, mmdet's BasicBlock) is passed in as ``depth_net``
+               state-dict keys; ``depth_net`` is passed in (any module with DepthNet's forward), or built by ``from_config`` as
+               this package's ``depth_net.DepthNet`` -- on its HIP route the prior tensor is never built
 
 Index maps are int32 [B*N, h, w]: the depth bin in 0..D (D = no radar return in range: the background label of the loss and
 the last channel of the one-hot grid) and the RCS class in -1..n_rcs-1.  Class -1 is "no class" -- an all-below-range block, a
@@ -26,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .depth_net import DepthNet
 from .lss_view import LSSViewTransformer_racformer, RankTables, img2lidar_from_metas
 
 EMPTY_DEPTH, EMPTY_RCS = 1e5, -1e5
@@ -284,8 +286,10 @@ class LSSViewTransformerBEVDepth_racformer(LSSViewTransformer_racformer):
     """The reference's module (:572-699) with its constructor arguments, method signatures and state-dict keys (``frustum``,
     ``depth_net.*``, ``rcs_embedding.weight``, ``rcs_embedding.bias``).  ``depth_net``: the module to run between the priors and
     the view transform, any ``nn.Module`` with the reference's ``forward(x, radar_feats, rcs_embedding, mlp_input)`` returning
-    [B*N, D + out_channels, h, w] -- the reference's own ``DepthNet(in_channels, in_channels, out_channels, D, **depthnet_cfg)``
-    in a deployment (it needs mmcv's DCN and mmdet's BasicBlock, which this package does not depend on).
+    [B*N, D + out_channels, h, w].  ``from_config`` builds this package's ``DepthNet(in_channels, in_channels, out_channels, D,
+    **depthnet_cfg)`` as the reference's constructor does (:574-578); with it, on its HIP route, ``forward`` hands the index maps
+    and the embedding to ``DepthNet.forward_fused`` and ``rac_lss_prior_fwd`` is skipped.  Any other ``depth_net`` gets the dense
+    prior tensor.
 
     On device tensors every method runs the HIP kernels; on CPU tensors the torch restatement (the view transform included)."""
 
@@ -301,6 +305,16 @@ class LSSViewTransformerBEVDepth_racformer(LSSViewTransformer_racformer):
         self.n_rcs = int(self.grid_config["rcs"][2])
         self.rcs_embedding = nn.Conv2d(self.n_rcs, 32, kernel_size=1, padding=0)
         self.focal_alpha, self.focal_gamma = 0.25, 2.0
+
+    @classmethod
+    def from_config(cls, depthnet_cfg=dict(), **kwargs):
+        """The reference's constructor call (:574-578): the keyword arguments of this class without ``depth_net``, which is built
+        as ``DepthNet(in_channels, in_channels, out_channels, D, **depthnet_cfg)``."""
+        if "depth_net" in kwargs:
+            raise TypeError("LSSViewTransformerBEVDepth_racformer.from_config builds the depth_net itself")
+        in_channels, out_channels = kwargs.get("in_channels", 512), kwargs.get("out_channels", 64)    # (the base class's defaults)
+        net = DepthNet(in_channels, in_channels, out_channels, int(kwargs["grid_config"]["depth"][2]), **depthnet_cfg)
+        return cls(depthnet_cfg=depthnet_cfg, depth_net=net, **kwargs)
 
     def get_mlp_input(self, img_metas):
         """[B, N*T, 9] float32 on the module's device: the upper-left 3x3 of every inverted ``lidar2img`` (:584-591)."""
@@ -357,8 +371,13 @@ class LSSViewTransformerBEVDepth_racformer(LSSViewTransformer_racformer):
         B, N, C, H, W = x.shape
         x = x.reshape(B * N, C, H, W)
         _, rad_inds, rcs_class = pool_bins(self._maps(radar_depth), self._maps(radar_rcs), self.grid_config, self.downsample)
-        prior = radar_prior(rad_inds, rcs_class, self.rcs_embedding.weight, self.rcs_embedding.bias, self.D)
-        x = self.depth_net(x, prior[:, :self.D + 1], prior[:, self.D + 1:], mlp_input)
+        emb = self.rcs_embedding
+        if isinstance(self.depth_net, DepthNet) and self.depth_net.hip_route(x, mlp_input, rad_inds, rcs_class, emb.weight, emb.bias):
+            # this package's DepthNet on its kernels: the prior tensor is two table lookups inside dep_proj, never built
+            x = self.depth_net.forward_fused(x, rad_inds, rcs_class, emb.weight, emb.bias, mlp_input)
+        else:
+            prior = radar_prior(rad_inds, rcs_class, emb.weight, emb.bias, self.D)
+            x = self.depth_net(x, prior[:, :self.D + 1], prior[:, self.D + 1:], mlp_input)
         depth_digit = x[:, :self.D, ...]
         tran_feat = x[:, self.D:self.D + self.out_channels, ...]
         return self.view_transform(x, depth_digit, tran_feat, img_metas)

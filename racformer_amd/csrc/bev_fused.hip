@@ -241,7 +241,15 @@ __global__ __launch_bounds__(256, BEV_OCC) void bev_sampling_d64_kernel(const Be
             // the point's attention weight and the frame weight folded into the four tap weights.  Computed once here
             // (one thread per keypoint) instead of by each of the 16 lanes that later gather the point.
             const float wgt = sattn[(kk * Tw + (a.B > 1 ? t : 0)) * P + p] * sq[kk * T + t];
-            const float h_im = loc[1] * (float)H - 0.5f, w_im = loc[0] * (float)W - 0.5f;
+            // (the pixel coordinates rounded operation by operation, as bev_bwd_footprint and the float64 references form them: left
+            //  to the compiler they became one fma(loc, size, -0.5), which on a map whose size is not a power of two is an ulp of the
+            //  coordinate away from the location the backward differentiates at)
+            float h_im, w_im;
+            {
+#pragma clang fp contract(off)
+                h_im = loc[1] * (float)H - 0.5f;
+                w_im = loc[0] * (float)W - 0.5f;
+            }
             const bool in = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
             const float hf = floorf(h_im), wf = floorf(w_im);
             const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;

@@ -73,12 +73,15 @@ def _tap_values(value, idx, heads):
     return value[t_i, idx, h_i]
 
 
-def sampled64(value, loc, hw, f32_coords=False):
-    """bilinear(V[t], loc[q,h,t,p])[h] -> [Q,heads,T,P,64], differentiable in value and loc"""
+def sampled64(value, loc, hw, f32_coords=False, magnitude=False):
+    """bilinear(V[t], loc[q,h,t,p])[h] -> [Q,heads,T,P,64], differentiable in value and loc.  magnitude: |value| under |tap weight|,
+    the scale A of a forward's error bound"""
     H, W = hw
     s = 0
+    if magnitude:
+        value = value.abs()
     for idx, tw, _, _, ok in _taps(loc, H, W, f32_coords):
-        s = s + _tap_values(value, idx, loc.shape[1]) * (tw * ok)[..., None]
+        s = s + _tap_values(value, idx, loc.shape[1]) * ((tw.abs() if magnitude else tw) * ok)[..., None]
     return s
 
 

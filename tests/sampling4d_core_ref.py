@@ -143,16 +143,19 @@ def floors(u, v, hws):
     return torch.stack(res, -2)
 
 
-def sampled64(feats, u, v, view, f32_coords=False):
-    """bilinear(feat_l[s][view], (u, v)) per level -> [B,T,G,Q,P,L,64], differentiable in feats, u, v"""
+def sampled64(feats, u, v, view, f32_coords=False, magnitude=False):
+    """bilinear(feat_l[s][view], (u, v)) per level -> [B,T,G,Q,P,L,64], differentiable in feats, u, v.  magnitude: |feat| under
+    |tap weight|, the scale A of a forward's error bound"""
     B, T, G, Q, P = u.shape
+    if magnitude:
+        feats = [f.abs() for f in feats]
     s_i = torch.arange(B * T * G, device=u.device).reshape(B, T, G, 1, 1).expand_as(u)
     res = []
     for f in feats:
         H, W = f.shape[2:4]
         s = 0
         for hi, wi, tw, _, _, ok in _taps(u, v, H, W, f32_coords):
-            s = s + f[s_i, view, hi, wi] * (tw * ok)[..., None]
+            s = s + f[s_i, view, hi, wi] * ((tw.abs() if magnitude else tw) * ok)[..., None]
         res.append(s)
     return torch.stack(res, dim=-2)
 

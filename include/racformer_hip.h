@@ -68,6 +68,8 @@
  *   rac_det_loss_fwd  <- the targets, FocalLoss and L1Loss of loss_single / dn_loss_single with their autograd backwards
  *                        models/racformer_head.py:264-300, 326-427
  *   rac_conv_small_* / rac_depthnet_* <- DepthNet.forward (use_dcn=False), models/necks/view_transformer_racformer.py:329-567
+ *   rac_fpn_lateral_fwd / rac_conv3x3_cf_fwd <- the lateral convolutions, top-down merge and output convolutions of the image necks
+ *                        (mmdet FPN as img_neck, CustomFPN as img_lss_neck), models/necks/fpn.py:159-180, models/racformer.py:107-126
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -78,7 +80,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 26
+#define RAC_ABI_VERSION 27
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -535,6 +537,11 @@ int rac_value_proj_q16_fwd(const float *x, const void *w_image, float w_alpha, c
  * word or NULL), so an image written by rac_conv_direct_fwd can be read as it is.  Cout = 256, Cin a multiple of 32, any H*W. */
 int rac_conv3x3_relu_cf_fwd(const void *xs, const void *ws, const float *bias, const float *amax, float scale_mul, float scale_add,
                             float w_alpha, float *out, int N, int H, int W, int Cin, int Cout, void *stream);
+/* rac_conv3x3_cf_fwd: rac_conv3x3_fwd storing CHANNEL-FIRST, out [N][256][H*W] f32 = conv3x3(xs) * w_alpha / 2^e + bias[c] with no
+ * activation (the image's scale from *amax, as rac_conv3x3_fwd): bit for bit rac_conv3x3_fwd's channel-last result transposed.
+ * The output convolutions of the image necks (racformer_amd/necks.py).  Cout = 256, Cin a multiple of 32, any H*W; bias may be NULL. */
+int rac_conv3x3_cf_fwd(const void *xs, const void *ws, const float *bias, const float *amax, float w_alpha, float *out, int N, int H,
+                       int W, int Cin, int Cout, void *stream);
 int rac_absmax_fwd(const float *const *srcs, const int64_t *counts, int num, float floor_value, float *amax_out,
                    void *stream);
 int rac_conv_pack_fwd(const float *src, const float *amax, void *xs, int N, int C, int H, int W, int c_total,
@@ -564,6 +571,23 @@ int rac_conv3x3_q16_fwd(const void *xs, const void *ws, const float *bias, const
  * bias: device f32 [256] or NULL.  num_images % num_cams == 0; any H, W. */
 int rac_fpn_conv_fwd(const void *xs, const void *ws, const float *bias, const float *amax, float w_alpha, float *out,
                      int num_images, int H, int W, int Cin, int num_cams, void *stream);
+
+/* The lateral 1x1 convolution of an image-neck level with the top-down merge (mmdet FPN / CustomFPN: ConvModule(Cin, 256, 1) with
+ * bias, no norm, no activation, then laterals[i] += F.interpolate(laterals[i + 1], size=(H, W), mode='nearest');
+ * models/necks/fpn.py:159-176), read straight from the channel-first backbone map:
+ *     out[n][co][p] = sum_ci W[co][ci] * x[n][ci][p] + bias[co] + (top ? top[n][co][src(p)] : 0)
+ *   x       : device f32 [N][Cin][H*W] (the backbone stage's [B*T*N, Cin, H, W]);  Cin a multiple of 32, any H, W >= 1
+ *   w_image : device f16 line image [256][Cin/32][hi 32 | lo 32] (rac_gemm_split_pack_fwd with scale 2^s); w_alpha = 2^-s
+ *   bias    : device f32 [256] or NULL
+ *   top     : device f32 [N][256][top_h*top_w] -- the coarser level's merged lateral, i.e. the previous call's out -- or NULL;
+ *             1 <= top_h <= H, 1 <= top_w <= W.  src(p) of p = h*W + w is the legacy 'nearest' rule, per axis
+ *             min((int)floorf(dst * ((float)in / out)), in - 1) in float32 (not 'nearest-exact')
+ *   out     : device f32 [N][256][H*W], channel-first: the next finer level's top and the source of rac_absmax_fwd / rac_conv_pack_fwd
+ * Split-precision f16 MFMA (hi / lo per operand, three products, fp32 accumulate), activation scale per pixel.  No atomics; the
+ * grid depends on the shapes alone.  Cout = 256.  w_image / bias 16-byte aligned (16-byte loads of x when it is aligned and
+ * H*W % 4 == 0, 4-byte loads otherwise). */
+int rac_fpn_lateral_fwd(const float *x, const void *w_image, float w_alpha, const float *bias, const float *top, float *out, int N,
+                        int Cin, int H, int W, int top_h, int top_w, int Cout, void *stream);
 
 /* Element-wise pieces of RadarBEVTemporalEncoder (models/racformer_transformer.py:618-720).
  *   rac_gru_gate_fwd   ConvGRUCell update after the gates convolution (:705-720): gates [B,3C,H,W] (z | r | cand),

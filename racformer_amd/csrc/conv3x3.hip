@@ -168,7 +168,7 @@ struct ConvArgs {
     int fpg, live, chunks_dead;
     float scale_mul, scale_add;   // CV_OUT_NCHW_RELU only: the image's bound is scale_mul * (*amax) + scale_add (amax may be NULL)
 };
-enum { CV_OUT_NHWC = 0, CV_OUT_GROUPED = 1, CV_OUT_Q16 = 2, CV_OUT_NCHW_RELU = 3 };
+enum { CV_OUT_NHWC = 0, CV_OUT_GROUPED = 1, CV_OUT_Q16 = 2, CV_OUT_NCHW_RELU = 3, CV_OUT_NCHW = 4 };
 __device__ __forceinline__ cv_f4 cv_fma4(cv_f4 a, float s, cv_f4 b)
 {
     return __builtin_elementwise_fma(a, (cv_f4){s, s, s, s}, b);
@@ -182,6 +182,8 @@ __device__ __forceinline__ cv_f4 cv_fma4(cv_f4 a, float s, cv_f4 b)
 // bit what rac_quant_i16_fwd makes of the CV_OUT_NHWC output, without the 134 MB fp32 stream in between.  CV_OUT_NCHW_RELU:
 // out [N][256][H*W] CHANNEL-FIRST = relu(conv + bias) -- the last Conv2d + folded BatchNorm2d + ReLU of the radar pillar branch
 // (radar_pillars.hip), whose input image carries the scale of a derived bound (rac_cd_scale's expression, as conv_direct.hip wrote it).
+// CV_OUT_NCHW: the same channel-first store of conv + bias without the ReLU, on an image scaled by *amax like CV_OUT_NHWC's -- the
+// output convolutions of the image necks (racformer_amd/necks.py), bit for bit the CV_OUT_NHWC result transposed.
 template <int MODE>
 __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
 {
@@ -371,7 +373,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
     // tile instead of four 4-byte ones (round 4; the predicated 4-byte form also serialised 128 bias loads per lane).
     const float unscale = a.w_alpha / cv_act_scale(MODE == CV_OUT_NCHW_RELU ? (a.amax ? a.scale_mul * *a.amax : 0.f) + a.scale_add : *a.amax);
     const int prows = min(CV_TM, HW - tile * CV_TM);       // valid pixels of this tile
-    if (MODE == CV_OUT_NCHW_RELU) {
+    if (MODE == CV_OUT_NCHW_RELU || MODE == CV_OUT_NCHW) {
         // a channel's 16 pixels of tile m are the 16 lanes li: 64-byte runs, the 8 tiles m of a wave row 512 contiguous bytes
         float *obase = a.out + (size_t)n * CV_COUT * HW + (size_t)tile * CV_TM;
 #pragma unroll
@@ -382,7 +384,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
             for (int m = 0; m < 8; ++m) {
                 const int p = 128 * wm + 16 * m + li;
                 if (p < prows) {
-                    const cv_f4 v = __builtin_elementwise_max(cv_fma4(acc[m][nn], unscale, bv), (cv_f4){0.f, 0.f, 0.f, 0.f});
+                    cv_f4 v = cv_fma4(acc[m][nn], unscale, bv);
+                    if (MODE == CV_OUT_NCHW_RELU)
+                        v = __builtin_elementwise_max(v, (cv_f4){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         obase[(size_t)(col + r) * HW + p] = v[r];
@@ -727,6 +731,31 @@ extern "C" int rac_conv3x3_relu_cf_fwd(const void *xs, const void *ws, const flo
     if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_CONV3X3_CF, reinterpret_cast<const void *>(conv3x3_f16x3_kernel<CV_OUT_NCHW_RELU>), lds))
         return rc_attr;
     hipLaunchKernelGGL(conv3x3_f16x3_kernel<CV_OUT_NCHW_RELU>, dim3((unsigned)(N * ((H * W + CV_TM - 1) / CV_TM))), dim3(512), lds,
+                       (hipStream_t)stream, a);
+    return rac_launch_status(what);
+}
+
+extern "C" int rac_conv3x3_cf_fwd(const void *xs, const void *ws, const float *bias, const float *amax, float w_alpha, float *out, int N,
+                                  int H, int W, int Cin, int Cout, void *stream)
+{
+    const char *what = "rac_conv3x3_cf_fwd";
+    RAC_CHECK_ARG(Cout == CV_COUT, "%s: built for %d output channels (got %d)", what, CV_COUT, Cout);
+    RAC_CHECK_ARG(Cin > 0 && Cin % 32 == 0, "%s: Cin=%d (multiple of 32)", what, Cin);
+    RAC_CHECK_ARG(N >= 0 && H > 0 && W > 0, "%s: N=%d H=%d W=%d", what, N, H, W);
+    if (N == 0)
+        return 0;
+    RAC_CHECK_ARG(xs && ws && amax && out, "%s: null pointer", what);
+    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(bias) & 15) == 0, "%s: bias must be 16-byte aligned", what);
+    ConvArgs a;
+    a.xs = reinterpret_cast<const uint4 *>(xs);
+    a.ws = reinterpret_cast<const uint4 *>(ws);
+    a.bias = bias; a.pixel_bias = nullptr; a.amax = amax; a.out = out; a.q = nullptr; a.qscale = nullptr;
+    a.N = N; a.H = H; a.W = W; a.chunks = Cin / 32; a.w_alpha = w_alpha; a.cams = 1;
+    a.pixel_bias_dead = nullptr; a.fpg = 0; a.live = 0; a.chunks_dead = 0; a.scale_mul = 1.f; a.scale_add = 0.f;
+    const int lds = 2 * CV_STAGE_U4 * 16;
+    if (const int rc_attr = rac_set_dynamic_lds_once(RAC_ATTR_CONV3X3_CF_PLAIN, reinterpret_cast<const void *>(conv3x3_f16x3_kernel<CV_OUT_NCHW>), lds))
+        return rc_attr;
+    hipLaunchKernelGGL(conv3x3_f16x3_kernel<CV_OUT_NCHW>, dim3((unsigned)(N * ((H * W + CV_TM - 1) / CV_TM))), dim3(512), lds,
                        (hipStream_t)stream, a);
     return rac_launch_status(what);
 }

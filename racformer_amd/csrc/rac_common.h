@@ -17,7 +17,8 @@ enum { RAC_ATTR_GEMM_SPLIT = 0, RAC_ATTR_GENERATOR, RAC_ATTR_CONV3X3, RAC_ATTR_C
        RAC_ATTR_CD_GRU, RAC_ATTR_CD_S2_8, RAC_ATTR_CD_S2_2, RAC_ATTR_CD_S2_3, RAC_ATTR_CD_IMG_2, RAC_ATTR_CD_F32_1, RAC_ATTR_CD_F32_2,
        RAC_ATTR_CD_F32_4, RAC_ATTR_VALUE_PROJ_BIAS, RAC_ATTR_VALUE_PROJ_Q16_BIAS,
        RAC_ATTR_MIXING_BWD, RAC_ATTR_CONV3X3_WGRAD, RAC_ATTR_GENERATOR_DS, RAC_ATTR_GENERATOR4_DS, RAC_ATTR_LINEAR_WGRAD_N,
-       RAC_ATTR_LINEAR_WGRAD_W, RAC_ATTR_CD_IMG_2_RELU, RAC_ATTR_CD_F32_2_CF_RELU, RAC_ATTR_CONV3X3_CF };
+       RAC_ATTR_LINEAR_WGRAD_W, RAC_ATTR_CD_IMG_2_RELU, RAC_ATTR_CD_F32_2_CF_RELU, RAC_ATTR_CONV3X3_CF,
+       RAC_ATTR_CONV3X3_CF_PLAIN };
 
 // compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1 (straight-line code with the index usable in constexpr contexts)
 template <int I>

@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Timing of the image necks (racformer_amd/necks.py) on the f8 shapes: 48 images (8 frames x 6 cameras), backbone stages
+[256, 512, 1024, 2048] channels on 64x176, 32x88, 16x44 and 8x22 maps; ``img_neck`` = FPN over all four, ``img_lss_neck`` =
+CustomFPN over the last two.  Needs the GPU.
+
+    python tools/necks_bench.py [--out profiles/necks_f8.json] [--errors necks_errors.json]
+
+Inputs are post-ReLU-like (non-negative, about half zeros).  Routes on the same device, weights and inputs, alternating inside every
+repetition after a warm-up; medians (and the 10th / 90th percentiles: the run-to-run spread) of device-event times in microseconds:
+  per level   the lateral launch alone (rac_fpn_lateral_fwd, with the coarser level's lateral as its ``top``): workgroups, the
+              algorithmic bytes (stage map read + merged lateral written + coarser lateral re-read), achieved GB/s and its
+              fraction of 8 TB/s
+  per neck    the whole forward as hip_eager, hip_graph (one captured graph) and torch_eager (``fused=False``: the library's
+              convolutions and F.interpolate)
+--errors: the (E_ref, kernel error) pairs a `RAC_NECKS_ERRORS=<file> pytest -m gpu tests/test_necks_gpu.py` session wrote, copied
+into the record.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from racformer_amd import necks  # noqa: E402
+from racformer_amd.fpn_writer import cached_pack  # noqa: E402
+
+IMAGES = 48
+CHANNELS = [256, 512, 1024, 2048]
+MAPS = [(64, 176), (32, 88), (16, 44), (8, 22)]
+PEAK_GBS = 8000.0
+
+
+def timed(fns, reps, warmup=5):
+    """{name: {median, p10, p90} us}; the functions alternate inside every repetition"""
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ev = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            ev[k].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {}
+    for k, v in ev.items():
+        t = sorted(1e3 * a.elapsed_time(b) for a, b in v)
+        out[k] = dict(median=round(statistics.median(t), 2), p10=round(t[len(t) // 10], 2), p90=round(t[(9 * len(t)) // 10], 2))
+    return out
+
+
+def fill(m, gen):
+    with torch.no_grad():
+        for p in m.parameters():
+            fan = p[0].numel() if p.dim() > 1 else 1
+            p.copy_(torch.randn(p.shape, generator=gen) * (0.1 if p.dim() == 1 else fan ** -0.5))
+
+
+def graph_of(step):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = step()
+    graph.replay()
+    torch.cuda.synchronize()
+    return graph, captured
+
+
+def bench_neck(name, module, lib_module, xs, reps):
+    def hip_step():
+        with torch.no_grad():
+            return module(xs)
+
+    def torch_step():
+        with torch.no_grad():
+            return lib_module(xs)
+
+    with torch.no_grad():
+        assert module.hip_route(xs) and not lib_module.hip_route(xs)
+    ours, theirs = hip_step(), torch_step()
+    torch.cuda.synchronize()
+    ours_l = list(ours) if isinstance(ours, tuple) else [ours]
+    theirs_l = list(theirs) if isinstance(theirs, tuple) else [theirs]
+    diff = max(float((a - b).abs().max()) for a, b in zip(ours_l, theirs_l))
+    graph, captured = graph_of(hip_step)
+    cap_l = list(captured) if isinstance(captured, tuple) else [captured]
+    same = all(torch.equal(a, b) for a, b in zip(cap_l, ours_l))
+    times = timed({"hip_eager": hip_step, "hip_graph": graph.replay, "torch_eager": torch_step}, reps)
+    return dict(neck=name, in_channels=module.in_channels, times=times, hip_vs_torch_route_max_abs_diff=diff,
+                output_max_abs=max(float(b.abs().max()) for b in theirs_l), graph_replay_equals_eager_bitwise=bool(same))
+
+
+def bench_laterals(module, xs, reps):
+    """every lateral launch of the four-level neck alone, with the top it gets inside the forward"""
+    with torch.no_grad():
+        lat = module.laterals_hip(xs)
+    fns, rows = {}, {}
+    for i, x in enumerate(xs):
+        conv = module.lateral_convs[i].conv
+        packed = cached_pack(module._packs, ("lateral", i), conv.weight, necks.pack_lateral_weight)
+        top = lat[i + 1] if i + 1 < len(xs) else None
+        fns[f"level{i}"] = (lambda x=x, packed=packed, bias=conv.bias, top=top: necks.fpn_lateral(x, packed, bias, top))
+        n, c, h, w = x.shape
+        out_bytes = n * 256 * h * w * 4
+        tile, wgs = necks.lateral_tile_pixels(n, h, w)
+        rows[f"level{i}"] = dict(cin=c, map=[h, w], tile_pixels=tile, workgroups=wgs,
+                                 bytes=dict(x_read=x.numel() * 4, out_written=out_bytes, top_reread=top.numel() * 4 if top is not None else 0))
+    times = timed(fns, reps)
+    for k, r in rows.items():
+        total = sum(r["bytes"].values())
+        r["time"] = times[k]
+        r["achieved_GBps"] = round(total / (times[k]["median"] * 1e-6) / 1e9, 1)
+        r["fraction_of_8TBps"] = round(r["achieved_GBps"] / PEAK_GBS, 4)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "build", "necks_f8.json"))
+    ap.add_argument("--errors", default=None)
+    ap.add_argument("--reps", type=int, default=30)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "necks_bench needs the MI355X"
+    dev = "cuda:0"
+    gen = torch.Generator().manual_seed(5)
+    xs = [torch.randn(IMAGES, c, h, w, generator=gen).clamp_min_(0.0).to(dev) for c, (h, w) in zip(CHANNELS, MAPS)]
+    fpn = necks.FPN(CHANNELS, 256, 4).eval()
+    fill(fpn, gen)
+    fpn = fpn.to(dev)
+    fpn_lib = necks.FPN(CHANNELS, 256, 4, fused=False).eval().to(dev)
+    fpn_lib.load_state_dict(fpn.state_dict())
+    lss = necks.CustomFPN(CHANNELS[2:], 256, num_outs=1, start_level=0, out_ids=[0]).eval()
+    fill(lss, gen)
+    lss = lss.to(dev)
+    lss_lib = necks.CustomFPN(CHANNELS[2:], 256, num_outs=1, start_level=0, out_ids=[0], fused=False).eval().to(dev)
+    lss_lib.load_state_dict(lss.state_dict())
+    rec = dict(shape=dict(images=IMAGES, in_channels=CHANNELS, maps=MAPS, out_channels=256, zeros_fraction=round(float((xs[0] == 0).float().mean()), 3)),
+               device=torch.cuda.get_device_name(0), unit="us: median, 10th and 90th percentile of device-event times", reps=args.reps,
+               lateral_launches=bench_laterals(fpn, xs, args.reps),
+               necks=[bench_neck("img_neck (FPN)", fpn, fpn_lib, xs, args.reps),
+                      bench_neck("img_lss_neck (CustomFPN)", lss, lss_lib, xs[2:], args.reps)])
+    rec["open_work"] = [
+        "rac_fpn_lateral_fwd walks its tile's channels twice (per-pixel maxima, then products): the second walk is served by L2 / the "
+        "Infinity Cache, not measured separately; a running per-pixel maximum with an exact power-of-two rescale of the accumulators "
+        "would read x once",
+        "the deep, small levels (Cin 1024 / 2048 on 16x44 / 8x22) run 288 / 144 workgroups of 32 / 64 K steps: latency-bound, far below "
+        "the bandwidth of the large levels; no split over K (it would need a second pass or atomics)",
+        "the activation image of the 3x3 stage is still written by rac_absmax_fwd + rac_conv_pack_fwd from the merged lateral: writing it "
+        "from the lateral kernel's epilogue needs the result's absmax first",
+        "no per-level timing of the library's 1x1 convolution was taken: the comparison with the library route is per neck",
+    ]
+    if args.errors and os.path.exists(args.errors):
+        rec["tolerance_bases"] = json.load(open(args.errors))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: v for k, v in rec.items() if k != "tolerance_bases"}, indent=1))
+
+
+if __name__ == "__main__":
+    main()

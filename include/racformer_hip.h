@@ -70,6 +70,9 @@
  *   rac_conv_small_* / rac_depthnet_* <- DepthNet.forward (use_dcn=False), models/necks/view_transformer_racformer.py:329-567
  *   rac_fpn_lateral_fwd / rac_conv3x3_cf_fwd <- the lateral convolutions, top-down merge and output convolutions of the image necks
  *                        (mmdet FPN as img_neck, CustomFPN as img_lss_neck), models/necks/fpn.py:159-180, models/racformer.py:107-126
+ *   rac_resnet_stem_fwd / rac_resnet_absmax_fwd / rac_resnet_conv_fwd <- img_backbone, mmdet ResNet(depth=50, style='pytorch',
+ *                        norm_eval=True) (configs/racformer_r50_nuimg_704x256_f8.py:67-76, models/racformer.py:107-126) and the
+ *                        input normalisation of models/racformer.py:202-212
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -80,7 +83,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 27
+#define RAC_ABI_VERSION 28
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1066,6 +1069,56 @@ int rac_conv_small_fwd(const rac_conv_small *d, void *stream);
 int rac_depthnet_gates_fwd(const float *mlp_input, const float *params, float *gates, int BN, int C, int branches, void *stream);
 int rac_depthnet_pool_bias_fwd(const float *x, const float *wpool_t, const float *bpool, const float *wbias_t, float *img_bias, int BN,
                                int hw, int ld, int C, int Cout, void *stream);
+
+/* ---- The image backbone: mmdet ResNet with Bottleneck blocks (depth 50 / 101 / 152, style 'pytorch'), eval mode, BatchNorms folded
+ * by the caller (csrc/resnet.hip).  Every tensor is channel-first f32; no atomics, every sum in one fixed order, nothing read back,
+ * launch geometry from the shapes alone: capturable, bitwise reproducible.
+ *
+ * rac_resnet_stem_fwd: out = maxpool3x3/2/1(relu(conv7x7/2/3(norm(img)) + bias)), exact fp32 (an fmaf chain over (ci, ky, kx)).
+ *   img     device f32 [N][3][H][W], any H, W >= 1
+ *   w       device f32 [147][64]: element [(ci * 7 + ky) * 7 + kx][co] = folded weight[co][ci][ky][kx]; 16-byte aligned
+ *   bias    device f32 [64], the folded BatchNorm shift
+ *   norm    != 0: the convolution reads (img[:, perm[c]] - mean[c]) / std[c] as its channel c (subtract, then an IEEE float32 division,
+ *           element by element; the zero padding stays zero)
+ *   conv    device f32 scratch [N][64][Hc][Wc], Hc = (H + 6 - 7) / 2 + 1 (the convolution's output; two launches)
+ *   out     device f32 [N][64][Hp][Wp], Hp = (Hc + 2 - 3) / 2 + 1; a pool window over the border takes the maximum of its valid pixels
+ *
+ * rac_resnet_absmax_fwd: parts[n][0..63] = maxima of |x| over 64 slices of image n (x: [N] images of per_image floats).  Fixes the
+ *   power-of-two activation scale of rac_resnet_conv_fwd, which combines the 64 values itself.
+ *
+ * rac_resnet_conv_fwd: one convolution of a Bottleneck with its folded BatchNorm and epilogue,
+ *     out[n][co][q] = [relu]( sum W[co][ci][ky][kx] * in[n][ci][stride * q + (ky, kx) - pad] + bias[co] [+ residual[n][co][q]] )
+ *   ksize 1 (pad 0) or 3 (pad 1); stride 1 or 2; Cin a multiple of 32, Cout a multiple of 64, both at most 2048; any H, W >= 1,
+ *   Ho = (H + 2 pad - ksize) / stride + 1
+ *   in         device f32 [N][Cin][H*W];  out, residual (or NULL): device f32 [N][Cout][Ho*Wo]
+ *   w_image    device f16 line image [Cout][ksize*ksize*Cin/32][hi 32 | lo 32] of weight * 2^s (rac_gemm_split_pack_fwd on the weight
+ *              as [Cout][K], K index = (ky * ksize + kx) * Cin + ci); w_alpha = 2^-s; 16-byte aligned
+ *   bias       device f32 [Cout] or NULL;  amax_parts: rac_resnet_absmax_fwd of `in` (it must bound every image)
+ *   Split-precision f16 MFMA (hi / lo per operand, three products, fp32 accumulate), activation scale per image. */
+typedef struct {
+    const float *img;
+    const float *w;
+    const float *bias;
+    float *conv;
+    float *out;
+    int N, H, W, norm;
+    int perm[3];
+    float mean[3];
+    float std[3];
+} rac_resnet_stem;
+typedef struct {
+    const float *in;
+    const void *w_image;
+    const float *bias;
+    const float *residual;
+    const float *amax_parts;
+    float *out;
+    float w_alpha;
+    int N, H, W, Cin, Cout, ksize, stride, relu;
+} rac_resnet_conv;
+int rac_resnet_stem_fwd(const rac_resnet_stem *d, void *stream);
+int rac_resnet_absmax_fwd(const float *x, float *parts, int N, int64_t per_image, void *stream);
+int rac_resnet_conv_fwd(const rac_resnet_conv *d, void *stream);
 
 #ifdef __cplusplus
 }

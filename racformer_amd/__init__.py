@@ -13,3 +13,4 @@ from .lss_view import (LSSViewFunction, LSSViewTransformer_racformer, lss_cells,
 from .lss_depth import (LSSViewTransformerBEVDepth_racformer, depth_loss, pool_bins, radar_prior)  # noqa: E402,F401
 from .depth_net import DepthNet  # noqa: E402,F401
 from .necks import FPN, CustomFPN  # noqa: E402,F401
+from .resnet import ResNet  # noqa: E402,F401

@@ -109,6 +109,9 @@ SIGNATURES = {
     "rac_conv_small_fwd": (_i, [_vp, _vp]),
     "rac_depthnet_gates_fwd": (_i, [_vp] * 3 + [_i] * 3 + [_vp]),
     "rac_depthnet_pool_bias_fwd": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
+    "rac_resnet_stem_fwd": (_i, [_vp, _vp]),
+    "rac_resnet_absmax_fwd": (_i, [_vp, _vp, _i, ctypes.c_int64, _vp]),
+    "rac_resnet_conv_fwd": (_i, [_vp, _vp]),
 }
 
 
@@ -157,6 +160,21 @@ class ConvSmall(ctypes.Structure):
 
 
 CS_CHANNEL_LAST, CS_CHANNEL_FIRST = 0, 1
+
+
+class ResnetStem(ctypes.Structure):
+    """rac_resnet_stem (include/racformer_hip.h)"""
+    _fields_ = [(n, _vp) for n in ("img", "w", "bias", "conv", "out")] + [(n, _i) for n in ("N", "H", "W", "norm")] \
+        + [("perm", _i * 3), ("mean", _f * 3), ("std", _f * 3)]
+
+
+class ResnetConv(ctypes.Structure):
+    """rac_resnet_conv (include/racformer_hip.h)"""
+    _fields_ = [(n, _vp) for n in ("in_", "w_image", "bias", "residual", "amax_parts", "out")] + [("w_alpha", _f)] \
+        + [(n, _i) for n in ("N", "H", "W", "Cin", "Cout", "ksize", "stride", "relu")]
+
+
+RESNET_AMAX_PARTS = 64
 
 
 def lib():

@@ -10,7 +10,7 @@ read + 735 MB written per sample at f8).  ``FPNOutputWriter`` is that last stage
 convolution's epilogue (rac_fpn_conv_fwd: the implicit-GEMM kernel of the temporal-fusion convolution, f16 matrix cores on
 hi/lo-split operands, fp32-convolution accuracy); ``RaCFormerTransformerDecoder.pregrouped = True`` then consumes its
 output as it stands.  The lateral / top-down part of the neck is ``racformer_amd/necks.py`` (``FPN.forward_pregrouped`` runs it in front
-of this stage); the backbone stays out of scope."""
+of this stage); the backbone in front of both is ``racformer_amd/resnet.py``."""
 import torch
 import torch.nn as nn
 

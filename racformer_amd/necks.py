@@ -21,7 +21,7 @@ level.  Two routes (``depth_net.py``'s rule):
   torch   everything else -- the CPU, training, ``fused=False`` (the benchmark's baseline): ``F.conv2d`` and ``F.interpolate``.
 
 What the f8 config does not use raises ``NotImplementedError`` in the constructors.  Backward through the HIP route and bf16 are
-out of scope; so is the backbone."""
+out of scope.  The stage maps come from the backbone of ``racformer_amd/resnet.py`` (``ResNet``), channel-first as the kernels read them."""
 import math
 
 import torch

@@ -70,6 +70,8 @@
  *   rac_conv_small_* / rac_depthnet_* <- DepthNet.forward (use_dcn=False), models/necks/view_transformer_racformer.py:329-567
  *   rac_fpn_lateral_fwd / rac_conv3x3_cf_fwd <- the lateral convolutions, top-down merge and output convolutions of the image necks
  *                        (mmdet FPN as img_neck, CustomFPN as img_lss_neck), models/necks/fpn.py:159-180, models/racformer.py:107-126
+ *   rac_fpn_merge_bwd / rac_fpn_lateral_dgrad / rac_fpn_lateral_wgrad <- autograd of the same lateral stage (stop_prev_grad=0 trains
+ *                        through the necks, models/racformer.py:300)
  *   rac_resnet_stem_fwd / rac_resnet_absmax_fwd / rac_resnet_conv_fwd <- img_backbone, mmdet ResNet(depth=50, style='pytorch',
  *                        norm_eval=True) (configs/racformer_r50_nuimg_704x256_f8.py:67-76, models/racformer.py:107-126) and the
  *                        input normalisation of models/racformer.py:202-212
@@ -83,7 +85,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 28
+#define RAC_ABI_VERSION 29
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -591,6 +593,32 @@ int rac_fpn_conv_fwd(const void *xs, const void *ws, const float *bias, const fl
  * H*W % 4 == 0, 4-byte loads otherwise). */
 int rac_fpn_lateral_fwd(const float *x, const void *w_image, float w_alpha, const float *bias, const float *top, float *out, int N,
                         int Cin, int H, int W, int top_h, int top_w, int Cout, void *stream);
+
+/* Backward of the lateral stage, level by level from the finest to the coarsest (racformer_amd/necks.py walks them).  No atomics, fixed
+ * summation orders, grids from the shapes alone, nothing read back; Cout = 256, Cin a multiple of 32 from 32 to 2048, any H, W >= 1.
+ *
+ *   rac_fpn_merge_bwd     G[n][c][p] = A[n][c][p] + sum over q with src(q) == p of Gfine[n][c][q]: the gradient of a level's merged
+ *                         lateral.  a [N][C][H*W] (what the level's own 3x3 convolution sends back) or NULL; gfine [N][C][fine_h*fine_w]
+ *                         (the finer level's G) or NULL, not both NULL; fine_h >= H, fine_w >= W.  row_start [H + 1] / col_start
+ *                         [W + 1]: device int32, the fine rows / columns whose src is i are [start[i], start[i + 1]) (src is
+ *                         non-decreasing; built on the host with the forward's float32 arithmetic).  Children are added to A
+ *                         row-major, in exact float32; ranges are clamped to the fine map.
+ *   rac_fpn_lateral_dgrad dx[n][ci][p] = sum_co W[co][ci] * g[n][co][p]: the forward's kernel with K = 256 and Cin output channels.
+ *                         wt_image: f16 line image of W^T, [Cin rounded up to a multiple of 256][8][hi 32 | lo 32] -- rac_linear_pack_wt
+ *                         of W [256][Cin] with scale 2^s into its first Cin rows, the rows behind them allocated (they are read, their
+ *                         products are not stored); w_alpha = 2^-s.  Scale of g per pixel, as the forward's of x.  16-byte aligned
+ *                         image; 16-byte loads of g when it is aligned and H*W % 4 == 0.
+ *   rac_fpn_lateral_wgrad dw[co][ci] = sum_{n,p} g[n][co][p] * x[n][ci][p] and, db != NULL, db[co] = sum_{n,p} g[n][co][p].  K is cut
+ *                         into units of 32 pixels of one image (N * ceil(H*W / 32) of them) and the units into k_splits contiguous
+ *                         ranges of ceil(units / k_splits), none empty; workspace f32 [k_splits][256][Cin] + [k_splits][256] holds the
+ *                         ranges' partial sums, which a second launch adds in ascending order.  Split f16 operands with one
+ *                         power-of-two scale per channel and range (it factors out of a sum over pixels; a per-pixel scale does not). */
+int rac_fpn_merge_bwd(const float *a, const float *gfine, const int *row_start, const int *col_start, float *g, int N, int C, int H,
+                      int W, int fine_h, int fine_w, void *stream);
+int rac_fpn_lateral_dgrad(const float *g, const void *wt_image, float w_alpha, float *dx, int N, int Cin, int H, int W, int Cout,
+                          void *stream);
+int rac_fpn_lateral_wgrad(const float *g, const float *x, float *workspace, float *dw, float *db, int N, int Cin, int H, int W,
+                          int Cout, int k_splits, void *stream);
 
 /* Element-wise pieces of RadarBEVTemporalEncoder (models/racformer_transformer.py:618-720).
  *   rac_gru_gate_fwd   ConvGRUCell update after the gates convolution (:705-720): gates [B,3C,H,W] (z | r | cand),

@@ -69,6 +69,9 @@ SIGNATURES = {
     "rac_conv3x3_relu_cf_fwd": (_i, [_vp] * 4 + [_f, _f, _f, _vp] + [_i] * 5 + [_vp]),
     "rac_conv3x3_cf_fwd": (_i, [_vp] * 4 + [_f, _vp] + [_i] * 5 + [_vp]),
     "rac_fpn_lateral_fwd": (_i, [_vp, _vp, _f, _vp, _vp, _vp] + [_i] * 7 + [_vp]),
+    "rac_fpn_merge_bwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
+    "rac_fpn_lateral_dgrad": (_i, [_vp, _vp, _f, _vp] + [_i] * 5 + [_vp]),
+    "rac_fpn_lateral_wgrad": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
     "rac_conv3x3_q16_fwd": (_i, [_vp] * 5 + [_f, _vp, _vp] + [_i] * 5 + [_vp]),
     "rac_fpn_conv_fwd": (_i, [_vp] * 4 + [_f, _vp] + [_i] * 5 + [_vp]),
     "rac_conv3x3s2_fwd": (_i, [_vp] * 4 + [_f, _vp] + [_i] * 7 + [_vp]),

@@ -30,6 +30,11 @@
 // per channel the 16 lanes li store 64 contiguous bytes and gather neighbouring pixels of the coarser level, the 16 gathers of a pixel
 // tile issued together.  No atomics, nothing read back; the grid depends on the shapes alone.
 // Any H, W: 16-byte loads when H*W % 4 == 0 and x is 16-byte aligned, 4-byte loads otherwise.
+//
+// The same kernel source is the convolution's data gradient (template DG, rac_fpn_lateral_dgrad at the end of this file):
+//   dX[n][ci][p] = sum_co W[co][ci] * G[n][co][p]
+// is this GEMM with K = 256, the merged gradient G as x (per-pixel scale as above), the line image of W^T (rac_linear_pack_wt) as the
+// weights and Cin output channels in blocks of 256.  The rest of the backward is fpn_lateral_bwd.hip.
 #include "rac_common.h"
 
 typedef _Float16 fl_h8 __attribute__((ext_vector_type(8)));
@@ -48,6 +53,7 @@ struct FpnLateralArgs {
     float *out;          // [N][256][HW]
     float w_alpha, scale_h, scale_w;
     int HW, W, chunks, hc, wc, tiles_per_img;
+    int cout, nblk;      // data gradient only: output channels (rows of the weight image that are stored), blocks of 256 of them
 };
 
 __device__ __forceinline__ fl_h8 fl_tr_frag(const char *lds, int off0, int off1)
@@ -65,9 +71,14 @@ __device__ __forceinline__ int fl_swz(int r) { return ((r & 3) << 2) | ((r >> 2)
 
 // NJ: 16-pixel MFMA tiles per workgroup (8: 128 pixels, 4: 64 pixels).  VEC: 16-byte loads (H*W % 4 == 0, x 16-byte aligned).
 // HAS_TOP: the top-down term is gathered in the epilogue.
-template <int NJ, bool VEC, bool HAS_TOP>
+// DG: the data gradient of the same convolution (rac_fpn_lateral_dgrad): x is the merged gradient G [N][256][HW], the weight image that
+// of W^T (a.cout = the forward's Cin rows, padded to whole blocks of 256), out = dX [N][a.cout][HW].  The grid carries the a.nblk
+// blocks of 256 output channels innermost, so the workgroups that share a tile of G run together; channels past a.cout (a last block
+// of fewer than 256) are computed on the padding rows and not stored.  No bias, no top.
+template <int NJ, bool VEC, bool HAS_TOP, bool DG = false>
 __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArgs a)
 {
+    static_assert(!(DG && HAS_TOP), "the data gradient has no top-down term");
     constexpr int TP = 16 * NJ;            // pixels per workgroup
     constexpr int RB = 2 * TP;             // bytes per LDS row (one channel's TP pixels, f16)
     constexpr int HALF = 32 * RB;          // one of hi / lo of a stage
@@ -79,7 +90,9 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
     __shared__ __attribute__((aligned(16))) float fl_unscale[TP], fl_scale[TP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
     const int HW = a.HW, chunks = a.chunks;
-    const int n = blockIdx.x / a.tiles_per_img, tile = blockIdx.x - n * a.tiles_per_img;
+    const int bid = DG ? blockIdx.x / a.nblk : blockIdx.x;
+    const int cbase = DG ? FL_COUT * (blockIdx.x - bid * a.nblk) : 0;      // first output channel of this workgroup
+    const int n = bid / a.tiles_per_img, tile = bid - n * a.tiles_per_img;
     const int p0 = tile * TP;
     const float *__restrict__ xn = a.x + (size_t)n * chunks * 32 * HW;
 
@@ -172,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
     };
 
     // weight fragments of this wave's 64 output channels: tile i = rows 64 wave + 16 i + li, chunk lk of the line's hi / lo half
-    const char *__restrict__ wrow = a.w + (size_t)(64 * wave + li) * chunks * 128 + lk * 16;
+    const char *__restrict__ wrow = a.w + (size_t)(cbase + 64 * wave + li) * chunks * 128 + lk * 16;
     const size_t wstep = (size_t)16 * chunks * 128;
     fl_h8 wh[4], wl[4], nwh[4], nwl[4];
     auto wload = [&](int c) {
@@ -246,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
     // ---- epilogue.  Accumulator tile (i, j): rows 4 lk + r = output channels (the MFMA's A operand), column li = pixel: per channel
     // the 16 lanes li store 64 contiguous bytes, and gather at most 16 neighbouring pixels of the coarser level.  The 16 gathers of a
     // pixel tile are issued together, ahead of its stores.
-    float *__restrict__ on = a.out + (size_t)n * FL_COUT * HW;
+    float *__restrict__ on = a.out + (size_t)n * (DG ? a.cout : FL_COUT) * HW + (size_t)cbase * HW;
     const int tplane = a.hc * a.wc;
     const float *__restrict__ tn = HAS_TOP ? a.top + (size_t)n * FL_COUT * tplane : nullptr;
     fl_f4 bv[4];
@@ -274,6 +287,8 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
         if (live) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
+                if (DG && cbase + 64 * wave + 16 * i >= a.cout)      // (wave-uniform: a.cout is a multiple of 32)
+                    continue;
                 const fl_f4 v = __builtin_elementwise_fma(acc[i][j], (fl_f4){us, us, us, us}, bv[i]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -312,6 +327,7 @@ extern "C" int rac_fpn_lateral_fwd(const float *x, const void *w_image, float w_
     a.scale_h = top ? (float)top_h / (float)H : 1.f;
     a.scale_w = top ? (float)top_w / (float)W : 1.f;
     a.HW = HW; a.W = W; a.chunks = Cin / 32; a.hc = top ? top_h : 1; a.wc = top ? top_w : 1; a.tiles_per_img = tiles;
+    a.cout = FL_COUT; a.nblk = 1;
     const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     const dim3 grid((unsigned)(N * tiles));
     hipStream_t st = (hipStream_t)stream;
@@ -325,5 +341,37 @@ extern "C" int rac_fpn_lateral_fwd(const float *x, const void *w_image, float w_
     if (wide) FL_GO(8);
     else FL_GO(4);
 #undef FL_GO
+    return rac_launch_status(what);
+}
+
+// dX[n][ci][p] = sum_co W[co][ci] * G[n][co][p]: the forward's GEMM with K = 256 and Cin output channels, on the image of W^T.
+extern "C" int rac_fpn_lateral_dgrad(const float *g, const void *wt_image, float w_alpha, float *dx, int N, int Cin, int H, int W,
+                                     int Cout, void *stream)
+{
+    const char *what = "rac_fpn_lateral_dgrad";
+    RAC_CHECK_ARG(Cout == FL_COUT, "%s: built for %d output channels (got %d)", what, FL_COUT, Cout);
+    RAC_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cin <= 2048, "%s: Cin=%d (a multiple of 32 from 32 to 2048)", what, Cin);
+    RAC_CHECK_ARG(N >= 0 && H >= 1 && W >= 1 && (long)H * W < (1l << 30), "%s: N=%d H=%d W=%d", what, N, H, W);
+    if (N == 0)
+        return 0;
+    RAC_CHECK_ARG(g && wt_image && dx, "%s: null pointer", what);
+    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(wt_image) & 15) == 0, "%s: wt_image must be 16-byte aligned", what);
+    RAC_CHECK_ARG(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx)) & 3) == 0, "%s: g / dx must be 4-byte aligned", what);
+    const int HW = H * W, nblk = (Cin + FL_COUT - 1) / FL_COUT;
+    const bool wide = (long)N * ((HW + 127) / 128) * nblk >= 256;      // the forward's rule, over all the workgroups
+    const int tp = wide ? 128 : 64, tiles = (HW + tp - 1) / tp;
+    RAC_CHECK_ARG((long)N * tiles * nblk < (1l << 31), "%s: %ld workgroups", what, (long)N * tiles * nblk);
+    FpnLateralArgs a;
+    a.x = g; a.w = reinterpret_cast<const char *>(wt_image); a.bias = nullptr; a.top = nullptr; a.out = dx;
+    a.w_alpha = w_alpha; a.scale_h = 1.f; a.scale_w = 1.f;
+    a.HW = HW; a.W = W; a.chunks = FL_COUT / 32; a.hc = 1; a.wc = 1; a.tiles_per_img = tiles;
+    a.cout = Cin; a.nblk = nblk;
+    const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    const dim3 grid((unsigned)(N * tiles * nblk));
+    hipStream_t st = (hipStream_t)stream;
+    if (wide && vec) hipLaunchKernelGGL((fpn_lateral_kernel<8, true, false, true>), grid, dim3(256), 0, st, a);
+    else if (wide) hipLaunchKernelGGL((fpn_lateral_kernel<8, false, false, true>), grid, dim3(256), 0, st, a);
+    else if (vec) hipLaunchKernelGGL((fpn_lateral_kernel<4, true, false, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((fpn_lateral_kernel<4, false, false, true>), grid, dim3(256), 0, st, a);
     return rac_launch_status(what);
 }

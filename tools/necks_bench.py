@@ -4,6 +4,7 @@
 CustomFPN over the last two.  Needs the GPU.
 
     python tools/necks_bench.py [--out profiles/necks_f8.json] [--errors necks_errors.json]
+    python tools/necks_bench.py --train [--out profiles/necks_grad_f8.json] [--errors necks_grad_errors.json]
 
 Inputs are post-ReLU-like (non-negative, about half zeros).  Routes on the same device, weights and inputs, alternating inside every
 repetition after a warm-up; medians (and the 10th / 90th percentiles: the run-to-run spread) of device-event times in microseconds:
@@ -14,6 +15,16 @@ repetition after a warm-up; medians (and the 10th / 90th percentiles: the run-to
               convolutions and F.interpolate)
 --errors: the (E_ref, kernel error) pairs a `RAC_NECKS_ERRORS=<file> pytest -m gpu tests/test_necks_gpu.py` session wrote, copied
 into the record.
+
+--train: the training leg instead -- forward plus backward of both necks under autograd with a fixed output gradient per level, every
+parameter requiring a gradient, none to the stage-0 input (``frozen_stages=1``), the weights' layout packs cached:
+  per neck    hip (``fused_grad = True``: ``_NeckCore``) against torch (``fused_grad = False``: the library's convolutions and their
+              backward) -- the same module, weights and inputs, alternating inside every repetition; and the largest difference between
+              the two routes' gradients, relative to the gradient's largest element
+  per level   every backward launch group of the HIP route alone: the 3x3 data gradient (absmax + pack of the output gradient + the
+              convolution), the merge, the 3x3 weight gradient (re-pack of the lateral + both launches), the lateral weight / bias
+              gradient (both launches) and the lateral data gradient
+With --train, --errors copies what `RAC_NECKS_GRAD_ERRORS=<file> pytest -m gpu tests/test_necks_grad_gpu.py` wrote.
 """
 import argparse
 import json
@@ -128,13 +139,118 @@ def bench_laterals(module, xs, reps):
     return rows
 
 
+def _outs(out):
+    return list(out) if isinstance(out, tuple) else [out]
+
+
+def bench_training(name, module, xs, reps, gen):
+    """forward + backward of one neck: the HIP route against the torch route of the same module"""
+    dev = xs[0].device
+    for p in module.parameters():
+        p.requires_grad_(True)
+    xg = [xs[0]] + [x.clone().requires_grad_() for x in xs[1:]]
+    levels = module.out_levels
+    gouts = [torch.randn(xs[i].shape[0], 256, *xs[i].shape[2:], generator=gen).to(dev) for i in levels]
+    leaves = xg[1:] + list(module.parameters())
+
+    def step(switch):
+        module.fused_grad = switch
+        for t in leaves:
+            t.grad = None
+        torch.autograd.backward(_outs(module(xg)), gouts)
+
+    def grads_of(switch):
+        step(switch)
+        torch.cuda.synchronize()
+        return [t.grad.clone() for t in leaves]
+
+    module.fused_grad = True
+    assert module.hip_grad_route(xg)
+    ours, theirs = grads_of(True), grads_of(False)
+    diff = max(float((a - b).abs().max()) / float(b.abs().max()) for a, b in zip(ours, theirs))
+    times = timed({"hip": lambda: step(True), "torch": lambda: step(False)}, reps, warmup=3)
+    module.fused_grad = False
+
+    # the backward's launch groups, level by level, on the tensors a backward sees
+    from racformer_amd import fused
+    with torch.no_grad():
+        lat = module.laterals_hip(xg)
+        fns, g_fine = {}, None
+        for i, x in enumerate(xg):
+            n, cin, h, w = x.shape
+            a = None
+            if i in levels:
+                j = levels.index(i)
+                go, ow = gouts[j], module.fpn_convs[j].conv.weight
+                ws, alpha, _ = cached_pack(module._packs, ("fpn_dgrad", j), ow, fused.pack_conv3x3_dgrad_weight)
+
+                def conv_dgrad(go=go, ws=ws, alpha=alpha, n=n, h=h, w=w):
+                    img = fused.ConvImage(n, h, w, 256, dev).begin([go]).pack(go, 0)
+                    return img, necks._conv3x3_cf(img, ws, alpha)
+
+                img, a = conv_dgrad()
+
+                def conv_wgrad(g_img=img, x=lat[i], n=n, h=h, w=w):       # (the gradient's image as the data gradient's group packed it)
+                    with fused.scratch_namespace((None, "neck_lateral")):
+                        x_img = fused.ConvImage(n, h, w, 256, dev).begin([x]).pack(x, 0)
+                    return fused.conv3x3_wgrad(x_img, g_img)
+
+                fns[f"level{i}.conv3x3_dgrad"] = conv_dgrad
+                fns[f"level{i}.conv3x3_wgrad"] = conv_wgrad
+            if g_fine is not None:
+                fns[f"level{i}.merge"] = (lambda a=a, gf=g_fine, size=(h, w): necks.fpn_merge_backward(a, gf, size=size))
+                g = necks.fpn_merge_backward(a, g_fine, size=(h, w))
+            else:
+                g = a
+            g_fine = g
+            fns[f"level{i}.lateral_wgrad"] = (lambda g=g, x=x.detach(): necks.fpn_lateral_wgrad(g, x))
+            if i > 0:
+                packed = cached_pack(module._packs, ("lateral_t", i), module.lateral_convs[i].conv.weight, necks.pack_lateral_weight_t)
+                fns[f"level{i}.lateral_dgrad"] = (lambda g=g, packed=packed, cin=cin: necks.fpn_lateral_dgrad(g, packed, cin))
+        launches = timed(fns, reps, warmup=3)
+    for k, v in launches.items():
+        i = int(k[5:k.index(".")])
+        n, cin, h, w = xg[i].shape
+        v.update(cin=cin, map=[h, w])
+        if k.endswith("lateral_wgrad"):
+            v["k_splits"] = necks.lateral_wgrad_k_splits(n, h, w, cin)
+    return dict(neck=name, in_channels=module.in_channels, times=times, hip_over_torch=round(times["hip"]["median"] / times["torch"]["median"], 3),
+                routes_max_gradient_difference_of_largest_element=diff, backward_launch_groups=launches,
+                backward_launch_groups_sum=round(sum(v["median"] for v in launches.values()), 2))
+
+
+def main_train(args):
+    dev = "cuda:0"
+    gen = torch.Generator().manual_seed(5)
+    xs = [torch.randn(IMAGES, c, h, w, generator=gen).clamp_min_(0.0).to(dev) for c, (h, w) in zip(CHANNELS, MAPS)]
+    fpn = necks.FPN(CHANNELS, 256, 4)
+    fill(fpn, gen)
+    lss = necks.CustomFPN(CHANNELS[2:], 256, num_outs=1, start_level=0, out_ids=[0])
+    fill(lss, gen)
+    rec = dict(shape=dict(images=IMAGES, in_channels=CHANNELS, maps=MAPS, out_channels=256),
+               device=torch.cuda.get_device_name(0), unit="us: median, 10th and 90th percentile of device-event times", reps=args.reps,
+               leg="forward + backward under autograd, every parameter with a gradient, none to the stage-0 input, packs cached; "
+                   "hip = fused_grad on, torch = fused_grad off (the library's convolutions), same module, weights and inputs",
+               necks=[bench_training("img_neck (FPN)", fpn.to(dev), xs, args.reps, gen),
+                      bench_training("img_lss_neck (CustomFPN)", lss.to(dev), xs[2:], args.reps, gen)])
+    if args.errors and os.path.exists(args.errors):
+        rec["tolerance_bases"] = json.load(open(args.errors))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: v for k, v in rec.items() if k != "tolerance_bases"}, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="the training leg (forward + backward) instead of the forward record")
     ap.add_argument("--out", default=os.path.join(ROOT, "build", "necks_f8.json"))
     ap.add_argument("--errors", default=None)
     ap.add_argument("--reps", type=int, default=30)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "necks_bench needs the MI355X"
+    if args.train:
+        return main_train(args)
     dev = "cuda:0"
     gen = torch.Generator().manual_seed(5)
     xs = [torch.randn(IMAGES, c, h, w, generator=gen).clamp_min_(0.0).to(dev) for c, (h, w) in zip(CHANNELS, MAPS)]

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float *__restrict__ a
             y.z = (x[k].z - mean) * rstd * g.z + b.z;
             y.w = (x[k].w - mean) * rstd * g.w + b.w;
             if (relu) {
-                y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f);
+                y.x = rac_relu(y.x); y.y = rac_relu(y.y); y.z = rac_relu(y.z); y.w = rac_relu(y.w);
             }
             if (post) {
                 const rac_f4 w = rac_ld4(post + (size_t)row * dim + c * 4);
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void add_ln_many_kernel(const float *__restric
     const rac_f4 g = rac_ld4(gamma + lane * 4), b = rac_ld4(beta + lane * 4);
     rac_f4 y = {d0 * rstd * g.x + b.x, d1 * rstd * g.y + b.y, d2 * rstd * g.z + b.z, d3 * rstd * g.w + b.w};
     if (relu) {
-        y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f);
+        y.x = rac_relu(y.x); y.y = rac_relu(y.y); y.z = rac_relu(y.z); y.w = rac_relu(y.w);
     }
     if (post) {
         const rac_f4 w = rac_ld4(post + (size_t)row * 256 + lane * 4);
@@ -227,8 +227,8 @@ __global__ __launch_bounds__(256) void pe_head_kernel(const float *__restrict__ 
     const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
     const float rstd = 1.f / sqrtf(aln_wave_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) / 256.f + eps);
     const rac_f4 g = rac_ld4(gamma + lane * 4), b = rac_ld4(beta + lane * 4);
-    rac_f4 y = {fmaxf(d0 * rstd * g.x + b.x, 0.f), fmaxf(d1 * rstd * g.y + b.y, 0.f), fmaxf(d2 * rstd * g.z + b.z, 0.f),
-                fmaxf(d3 * rstd * g.w + b.w, 0.f)};
+    rac_f4 y = {rac_relu(d0 * rstd * g.x + b.x), rac_relu(d1 * rstd * g.y + b.y), rac_relu(d2 * rstd * g.z + b.z),
+                rac_relu(d3 * rstd * g.w + b.w)};
     *reinterpret_cast<rac_f4 *>(out + (size_t)row * 256 + lane * 4) = y;
 }
 

@@ -161,6 +161,13 @@ struct alignas(8) rac_h4 {
     _Float16 x, y, z, w;
 };
 
+// ReLU as torch.relu computes it: a NaN stays a NaN (fmaxf(NaN, 0) is 0, which turns a poisoned row into clean zeros); every
+// other value, -0 included, is fmaxf's bit for bit.
+__device__ __forceinline__ float rac_relu(float v)
+{
+    return v != v ? v : fmaxf(v, 0.f);
+}
+
 __device__ __forceinline__ void rac_split_f16(float v, _Float16 &hi, _Float16 &lo)
 {
     hi = (_Float16)v;

@@ -267,8 +267,8 @@ __global__ __launch_bounds__(256) void layer_boundary_kernel(const float *__rest
     const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
     const float rstd = 1.f / sqrtf(lb_wave_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) / 256.f + eps);
     const rac_f4 g = rac_ld4(gamma + lane * 4), b = rac_ld4(beta + lane * 4);
-    rac_f4 y = {fmaxf(d0 * rstd * g.x + b.x, 0.f), fmaxf(d1 * rstd * g.y + b.y, 0.f), fmaxf(d2 * rstd * g.z + b.z, 0.f),
-                fmaxf(d3 * rstd * g.w + b.w, 0.f)};
+    rac_f4 y = {rac_relu(d0 * rstd * g.x + b.x), rac_relu(d1 * rstd * g.y + b.y), rac_relu(d2 * rstd * g.z + b.z),
+                rac_relu(d3 * rstd * g.w + b.w)};
     *reinterpret_cast<rac_f4 *>(h_out + (size_t)i * 256 + lane * 4) = y;
 }
 

@@ -121,7 +121,7 @@ __device__ __forceinline__ void rowgemm_body(const rac_rowgemm &d, int rows, flo
                     v.z = d2 * rstd * gm.z + bt.z; v.w = d3 * rstd * gm.w + bt.w;
                 }
                 if (g.relu) {
-                    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                    v.x = rac_relu(v.x); v.y = rac_relu(v.y); v.z = rac_relu(v.z); v.w = rac_relu(v.w);
                 }
                 if (g.post && row < rows) {
                     const rac_f4 w = rac_ld4(g.post + (size_t)row * g.ld_post + lane * 4);
@@ -205,7 +205,7 @@ __device__ __forceinline__ void rowgemm_body(const rac_rowgemm &d, int rows, flo
             const int row = row0 + 16 * m + 4 * lk + r;
             float v = (acc[m][0][r] + acc[m][1][r]) + bv;
             if (relu)
-                v = fmaxf(v, 0.f);
+                v = rac_relu(v);
             if (row < rows && col < d.N)
                 d.out[(size_t)row * d.ld_out + col] = v;
         }

@@ -39,6 +39,44 @@ def _dest(t, query_bbox, width):
     return torch.empty(query_bbox.shape[:2] + (width,), device=query_bbox.device, dtype=torch.float32)
 
 
+def _sized(who, name, t, numel, what):
+    """An optional row-wise operand holds exactly the float32 elements its kernel reads (checked on any device, before a pointer
+    is taken)."""
+    if t is None:
+        return
+    if t.dtype != torch.float32 or t.numel() != numel:
+        raise RuntimeError(f"{who}: {name} must hold {what} float32 elements, got {tuple(t.shape)} {t.dtype}")
+
+
+def _row_operand(who, name, t, width=256):
+    """A row operand of a row GEMM: [rows, width] or [B, Q, width] -> the rows it holds."""
+    if t.dim() not in (2, 3) or t.shape[-1] != width:
+        raise RuntimeError(f"{who}: {name} must be [rows, {width}] or [B, Q, {width}], got {tuple(t.shape)}")
+    return int(torch.Size(t.shape[:-1]).numel())
+
+
+def _pe_operands(who, linear, norm):
+    """The position encoder's head as its kernels are built: Linear(3 -> 256), LayerNorm(256)."""
+    if tuple(linear.weight.shape) != (256, 3) or linear.weight.dtype != torch.float32:
+        raise RuntimeError(f"{who}: linear.weight must be float32 [256, 3], got {tuple(linear.weight.shape)}")
+    _sized(who, "linear.bias", linear.bias, 256, "256")
+    _sized(who, "norm.weight", norm.weight, 256, "256")
+    _sized(who, "norm.bias", norm.bias, 256, "256")
+    if linear.bias is None or norm.weight is None or norm.bias is None:
+        raise RuntimeError(f"{who}: linear.bias, norm.weight and norm.bias are read by the kernel and must be present")
+
+
+def _boxes_and_times(who, proposal, delta, time_diff_safe):
+    """proposal, delta float32 [B,Q,10]; time_diff_safe float32 [B,T] (the kernels read entry [b, 1] where T > 1)."""
+    if proposal.dim() != 3 or proposal.shape[-1] != 10 or proposal.dtype != torch.float32:
+        raise RuntimeError(f"{who}: proposal must be float32 [B, Q, 10], got {tuple(proposal.shape)}")
+    if tuple(delta.shape) != tuple(proposal.shape) or delta.dtype != torch.float32:
+        raise RuntimeError(f"{who}: delta must be float32 and shaped like proposal {tuple(proposal.shape)}, got {tuple(delta.shape)}")
+    if time_diff_safe.dim() != 2 or time_diff_safe.shape[0] != proposal.shape[0] or time_diff_safe.shape[1] < 1 \
+            or time_diff_safe.dtype != torch.float32:
+        raise RuntimeError(f"{who}: time_diff_safe must be float32 [B = {proposal.shape[0]}, T], got {tuple(time_diff_safe.shape)}")
+
+
 def box_prep(query_bbox, pc_range):
     """[B,Q,10] polar boxes -> [B,Q,8] (cx,cy,cz,w,l,h,cos yaw,sin yaw), once per decoder layer."""
     _lib.require_gpu(query_bbox, what="box_prep")
@@ -541,6 +579,7 @@ def mixing_backward(x, params, grad_out, in_points, n_groups, out_points=128, ep
 def refine_fused(proposal, delta, time_diff_safe, num_ray):
     """refine_bbox + velocity / time_diff + theta_d2xy in one launch.
     -> (bbox_pred [B,Q,10] polar, bbox_xy [B,Q,10] normalised xy)."""
+    _boxes_and_times("refine_fused", proposal, delta, time_diff_safe)
     proposal, delta = proposal.contiguous(), delta.contiguous()
     _lib.require_gpu(proposal, delta, time_diff_safe, what="refine_fused")
     B, Q, _ = proposal.shape
@@ -640,15 +679,19 @@ def head_finish_fused(cls_scores, bbox_xy, pc_range):
 def layer_boundary_fused(proposal, delta, time_diff_safe, num_ray, pc_range, pe_linear, pe_norm, xy_out=None):
     """refine_fused + box_prep + pe_head for the refined boxes in one launch (rac_layer_boundary_fwd).
     -> (bbox_pred [B,Q,10], bbox_xy [B,Q,10], box_table [B,Q,8], pe_head output [B,Q,256])."""
+    _boxes_and_times("layer_boundary_fused", proposal, delta, time_diff_safe)
+    _pe_operands("layer_boundary_fused", pe_linear, pe_norm)
     proposal, delta = proposal.contiguous(), delta.contiguous()
-    _lib.require_gpu(proposal, delta, time_diff_safe, what="layer_boundary_fused")
+    _lib.require_gpu(proposal, delta, time_diff_safe, pe_linear.weight, pe_linear.bias, pe_norm.weight, pe_norm.bias,
+                     what="layer_boundary_fused")
     B, Q, _ = proposal.shape
     pred = torch.empty_like(proposal)
     if xy_out is None:
         xy = torch.empty_like(proposal)
     else:
-        if tuple(xy_out.shape) != tuple(proposal.shape) or not xy_out.is_contiguous() or xy_out.dtype != torch.float32:
-            raise RuntimeError("layer_boundary_fused: xy_out must be a contiguous float32 tensor shaped like the boxes")
+        if tuple(xy_out.shape) != tuple(proposal.shape) or not xy_out.is_contiguous() or xy_out.dtype != torch.float32 \
+                or not xy_out.is_cuda:
+            raise RuntimeError("layer_boundary_fused: xy_out must be a contiguous float32 CUDA tensor shaped like the boxes")
         xy = xy_out
     table = torch.empty(B, Q, 8, device=proposal.device, dtype=torch.float32)
     h = torch.empty(B, Q, pe_linear.weight.shape[0], device=proposal.device, dtype=torch.float32)
@@ -670,38 +713,58 @@ def add_ln(a, norm, residual=None, bias=None, relu=False, num_partials=1, post=N
     ``split=True``: also returns the f16 [rows, 3*dim + SPLIT_BIAS_PAD] = [hi | hi | lo | 1 1 0..] image of
     ``out * SPLIT_ACT_SCALE`` (A operand of a split GEMM, see ``split_weight_f16``); with ``split_lines`` the image is the
     line image [rows, dim/32 * 64] = [hi 32 | lo 32] per 32 columns that ``generator_fused`` reads."""
-    _lib.require_gpu(norm.weight, what="add_ln")
     dim = a.shape[-1]
     if num_partials > 1:
+        if a.dim() < 2 or a.shape[0] != num_partials:
+            raise RuntimeError(f"add_ln: a must be [{num_partials}, ..., dim] with num_partials={num_partials}, got {tuple(a.shape)}")
+        rows = a.numel() // dim // num_partials
+    else:
+        rows = int(torch.Size(a.shape[:-1]).numel())
+    # the kernels read rows * dim elements of residual / post and dim of bias, gamma and beta, whatever the tensors hold
+    _sized("add_ln", "residual", residual, rows * dim, f"rows * dim = {rows} * {dim}")
+    _sized("add_ln", "post", post, rows * dim, f"rows * dim = {rows} * {dim}")
+    _sized("add_ln", "bias", bias, dim, f"dim = {dim}")
+    _sized("add_ln", "norm.weight", norm.weight, dim, f"dim = {dim}")
+    _sized("add_ln", "norm.bias", norm.bias, dim, f"dim = {dim}")
+    if a.dtype != torch.float32:
+        raise RuntimeError(f"add_ln: a must be float32, got {a.dtype}")
+    if out is not None:
+        if out.dtype != torch.float32 or out.dim() < 1 or out.stride(-1) != 1 or out.shape[-1] != dim or out.numel() != rows * dim:
+            raise RuntimeError(f"add_ln: out must be a float32 [{rows} rows, {dim}] view with unit inner stride, got {tuple(out.shape)}")
+        if any(out.stride(i) != out.shape[i + 1] * out.stride(i + 1) for i in range(out.dim() - 2)):
+            raise RuntimeError("add_ln: out's rows must be equally strided")
+    if num_partials > 1:
         a = a.contiguous()
-        rows, ld_a, shape = a.numel() // dim // num_partials, dim, a.shape[1:]
+        ld_a, shape = dim, a.shape[1:]
     else:
         if a.stride(-1) != 1 or not a.is_cuda:
             raise RuntimeError("add_ln: input must be a CUDA tensor with unit inner stride")
-        lead = a.shape[:-1]
-        rows, shape = int(torch.Size(lead).numel()), a.shape
+        shape = a.shape
         ld_a = a.stride(-2) if a.dim() > 1 else dim
         if a.dim() > 2 and a.stride(0) != a.shape[1] * a.stride(1):
             raise RuntimeError("add_ln: rows must be equally strided")
     if residual is not None:
         residual = residual.contiguous()
-        if residual.numel() == rows * dim:
-            shape = residual.shape
+        shape = residual.shape
     if post is not None:
         post = post.contiguous()
+    # every pointer the kernel takes is a device pointer (contiguous where the kernel assumes it)
+    _lib.require_gpu(norm.weight, norm.bias, *[t for t in (residual, post, bias) if t is not None],
+                     *([a] if num_partials > 1 else []), what="add_ln")
     if out is None:
         out = torch.empty(shape, device=a.device, dtype=torch.float32)
         ld_out = dim
     else:
-        if out.stride(-1) != 1 or out.shape[-1] != dim:
-            raise RuntimeError("add_ln: out must have unit inner stride and the normalised width")
-        ld_out = out.stride(-2)
+        if not out.is_cuda:
+            raise RuntimeError("racformer_amd.add_ln: out must be a CUDA tensor (HIP device); the hot path has no CPU fallback")
+        ld_out = out.stride(-2) if out.dim() > 1 else dim
     if split:
         width = 2 * dim if split_lines else 3 * dim + SPLIT_BIAS_PAD
         if split_out is None:
             split_out = torch.empty(rows, width, device=a.device, dtype=torch.float16)
-        elif split_out.dtype != torch.float16 or not split_out.is_contiguous() or tuple(split_out.shape) != (rows, width):
-            raise RuntimeError(f"add_ln: split_out must be a contiguous f16 [{rows}, {width}] tensor")
+        elif split_out.dtype != torch.float16 or not split_out.is_contiguous() or tuple(split_out.shape) != (rows, width) \
+                or not split_out.is_cuda:
+            raise RuntimeError(f"add_ln: split_out must be a contiguous f16 CUDA [{rows}, {width}] tensor")
     rc = _lib.lib().rac_add_ln_fwd(_lib.ptr(a), num_partials, rows * dim, ld_a, float(a_scale),
                                    _lib.ptr(residual) if residual is not None else None,
                                    _lib.ptr(bias) if bias is not None else None, _lib.ptr(norm.weight), _lib.ptr(norm.bias),
@@ -742,8 +805,14 @@ def split_weight_f16(weight, bias=None):
 
 def pe_head(x3, linear, norm):
     """relu(LayerNorm(linear(x3))) for the 3-wide position-encoder input, one launch.  x3: [..., 3] view."""
+    if x3.dim() < 2 or x3.shape[-1] != 3 or x3.dtype != torch.float32:
+        raise RuntimeError(f"pe_head: x3 must be a float32 [..., 3] view, got {tuple(x3.shape)}")
+    _pe_operands("pe_head", linear, norm)
     if x3.stride(-1) != 1 or not x3.is_cuda:
         raise RuntimeError("pe_head: input must be a CUDA tensor with unit inner stride")
+    if x3.dim() > 2 and any(x3.stride(i) != x3.shape[i + 1] * x3.stride(i + 1) for i in range(x3.dim() - 2)):
+        raise RuntimeError("pe_head: rows must be equally strided")
+    _lib.require_gpu(linear.weight, linear.bias, norm.weight, norm.bias, what="pe_head")
     rows = int(torch.Size(x3.shape[:-1]).numel())
     out = torch.empty(x3.shape[:-1] + (linear.weight.shape[0],), device=x3.device, dtype=torch.float32)
     rc = _lib.lib().rac_pe_head_fwd(_lib.ptr(x3), x3.stride(-2), _lib.ptr(linear.weight), _lib.ptr(linear.bias),
@@ -1131,9 +1200,10 @@ def upsample2x_fused(x):
 
 # ------------------------------------------------------------------------------------------- row GEMMs
 def _rows2d(t, what):
-    """-> (tensor kept alive, pointer, row stride) of a float32 CUDA [rows, W] / [B, Q, W] view with unit inner stride."""
-    if not t.is_cuda or t.dtype != torch.float32 or t.stride(-1) != 1:
-        raise RuntimeError(f"racformer_amd.rowgemm({what}): expected a float32 CUDA tensor with unit inner stride")
+    """-> (tensor kept alive, pointer, row stride) of a float32 [rows, W] / [B, Q, W] view with unit inner stride (rowgemm_launch
+    refuses anything that is not on the GPU)."""
+    if t.dtype != torch.float32 or t.stride(-1) != 1:
+        raise RuntimeError(f"racformer_amd.rowgemm({what}): expected a float32 tensor with unit inner stride")
     if t.dim() == 3:
         if t.stride(0) != t.shape[1] * t.stride(1):
             raise RuntimeError(f"racformer_amd.rowgemm({what}): rows must be equally strided")
@@ -1151,17 +1221,36 @@ def row_seg(a, num_partials=1, a_scale=1.0, bias0=None, residual=None, norm=None
     [relu](LN_norm(a_scale * sum_p a[p] + bias0 + residual)) [+ post]; ``a`` is [rows,256] (any row stride) or, with
     num_partials = S > 1, a contiguous [S, rows, 256].  ``x_out`` / ``split_out``: destinations for the finished rows
     (fp32 [rows,256] / f16 [rows, 768 + SPLIT_BIAS_PAD] for a K-concatenated library GEMM, or -- ``split_lines`` -- the f16
-    line image [rows, 8, hi 32 | lo 32] that ``generator_fused`` reads)."""
+    line image [rows, 8, hi 32 | lo 32] that ``generator_fused`` reads).
+    Every operand's width is checked here, before a pointer is taken; the rows each one holds are kept for rowgemm_launch,
+    which knows how many the kernel reads.  The description is for rowgemm_launch only: neither the row counts nor the device of
+    its tensors have been checked yet, so it is not safe to hand to rac_rowgemm_fwd directly."""
+    who = "row_seg"
+    held = {}
+    if num_partials > 1:
+        if a.dim() < 2 or not a.is_contiguous() or a.shape[0] != num_partials or a.shape[-1] != 256 or a.dtype != torch.float32:
+            raise RuntimeError(f"row_seg: a (partials) must be a contiguous float32 [{num_partials}, rows, 256] tensor, got {tuple(a.shape)}")
+        held["a"] = a.numel() // num_partials // 256
+    else:
+        held["a"] = _row_operand(who, "a", a)
+    for name, t in (("residual", residual), ("post", post), ("x_out", x_out)):
+        if t is not None:
+            held[name] = _row_operand(who, name, t)
+    _sized(who, "bias0", bias0, 256, "256")
+    if norm is not None:
+        _sized(who, "norm.weight", norm.weight, 256, "256")
+        _sized(who, "norm.bias", norm.bias, 256, "256")
+    if split_out is not None:
+        width = 512 if split_lines else 768 + SPLIT_BIAS_PAD
+        if split_out.dtype != torch.float16 or not split_out.is_contiguous() or split_out.shape[-1] != width:
+            raise RuntimeError(f"row_seg: split_out must be a contiguous f16 [rows, {width}] tensor")
+        held["split_out"] = split_out.numel() // width
     g = _lib.RowSeg()
     keep = []
     if num_partials > 1:
-        if not a.is_contiguous() or a.shape[0] != num_partials or a.shape[-1] != 256:
-            raise RuntimeError("row_seg: partials must be a contiguous [S, rows, 256] tensor")
         g.a, g.ld_a, g.partial_stride = ctypes.c_void_p(a.data_ptr()), 256, a.numel() // num_partials
         keep.append(a)
     else:
-        if a.shape[-1] != 256:
-            raise RuntimeError("row_seg: segments are 256 wide")
         t, g.a, g.ld_a = _rows2d(a, "a")
         g.partial_stride = 0
         keep.append(t)
@@ -1174,6 +1263,7 @@ def row_seg(a, num_partials=1, a_scale=1.0, bias0=None, residual=None, norm=None
         keep.append(t)
     if norm is not None:
         g.gamma, g.beta, g.eps = ctypes.c_void_p(norm.weight.data_ptr()), ctypes.c_void_p(norm.bias.data_ptr()), float(norm.eps)
+        keep += [norm.weight, norm.bias]
     if post is not None:
         t, g.post, g.ld_post = _rows2d(post, "post")
         keep.append(t)
@@ -1181,39 +1271,56 @@ def row_seg(a, num_partials=1, a_scale=1.0, bias0=None, residual=None, norm=None
         t, g.x_out, g.ld_xout = _rows2d(x_out, "x_out")
         keep.append(t)
     if split_out is not None:
-        width = 512 if split_lines else 768 + SPLIT_BIAS_PAD
-        if split_out.dtype != torch.float16 or not split_out.is_contiguous() or split_out.shape[-1] != width:
-            raise RuntimeError(f"row_seg: split_out must be a contiguous f16 [rows, {width}] tensor")
         g.split_out, g.split_scale = ctypes.c_void_p(split_out.data_ptr()), SPLIT_ACT_SCALE
         g.split_pad, g.split_layout = (0, 1) if split_lines else (SPLIT_BIAS_PAD, 0)
         keep.append(split_out)
-    g._keep = keep
+    g._keep, g._held = keep, held
     return g
 
 
 def row_gemm(segs, weight, bias, out, relu_from=None):
-    """out = [relu on columns >= relu_from](cat(segs) @ weight.T + bias); weight [N, 256*len(segs)] contiguous."""
-    d = _lib.RowGemm()
+    """out = [relu on columns >= relu_from](cat(segs) @ weight.T + bias); weight [N, 256*len(segs)] contiguous.
+    Like row_seg's, the description is for rowgemm_launch only, which checks the row counts and that every tensor is on the GPU."""
+    if weight.dim() != 2 or weight.shape[1] != 256 * len(segs) or not weight.is_contiguous() or weight.dtype != torch.float32:
+        raise RuntimeError("row_gemm: weight must be a contiguous float32 [N, 256 * segments] tensor")
     N, K = weight.shape
-    if K != 256 * len(segs) or not weight.is_contiguous() or not weight.is_cuda or weight.dtype != torch.float32:
-        raise RuntimeError("row_gemm: weight must be a contiguous float32 CUDA [N, 256 * segments] tensor")
+    _sized("row_gemm", "bias", bias, N, f"N = {N}")
+    if out.dim() not in (2, 3) or out.shape[-1] != N:
+        raise RuntimeError(f"row_gemm: out must be [rows, N = {N}], got {tuple(out.shape)}")
+    d = _lib.RowGemm()
     for i, g in enumerate(segs):
         d.seg[i] = g
     d.num_seg, d.N = len(segs), N
     d.w = ctypes.c_void_p(weight.data_ptr())
     d.b = ctypes.c_void_p(bias.data_ptr()) if bias is not None else None
     t, d.out, d.ld_out = _rows2d(out, "out")
-    if out.shape[-1] != N:
-        raise RuntimeError("row_gemm: out must be [rows, N]")
     d.relu_from = N if relu_from is None else int(relu_from)
     d._keep = [segs, weight, bias, t]
+    d._out_rows = int(torch.Size(out.shape[:-1]).numel())
     return d
 
 
 def rowgemm_launch(descs, rows):
-    """One launch for up to 3 independent row GEMMs over the same rows."""
+    """One launch for up to 3 independent row GEMMs over the same rows.  Refuses a launch whose kernel would read or write
+    past an operand: every operand of every segment, and ``out``, holds at least ``rows`` rows (their widths were checked
+    when the segments were described)."""
+    rows = int(rows)
+    for i, d in enumerate(descs):
+        segs, weight, bias, out = d._keep
+        for s, g in enumerate(segs):
+            for name, held in g._held.items():
+                if held < rows:
+                    raise RuntimeError(f"rowgemm_launch: GEMM {i} segment {s}: {name} holds {held} rows, the launch covers {rows}")
+        if d._out_rows < rows:
+            raise RuntimeError(f"rowgemm_launch: GEMM {i}: out holds {d._out_rows} rows, the launch covers {rows}")
+    for i, d in enumerate(descs):
+        segs, weight, bias, out = d._keep
+        tensors = [weight, out] + ([bias] if bias is not None else []) + [t for g in segs for t in g._keep]
+        if not all(t.is_cuda for t in tensors):
+            raise RuntimeError(f"racformer_amd.rowgemm_launch: GEMM {i}: every operand must be a CUDA tensor (HIP device); "
+                               "the hot path has no CPU fallback")
     arr = (_lib.RowGemm * len(descs))(*descs)
-    rc = _lib.lib().rac_rowgemm_fwd(arr, len(descs), int(rows), _lib.stream_ptr())
+    rc = _lib.lib().rac_rowgemm_fwd(arr, len(descs), rows, _lib.stream_ptr())
     _lib.check(rc, "rac_rowgemm_fwd")
 
 

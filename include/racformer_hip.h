@@ -75,6 +75,8 @@
  *   rac_resnet_stem_fwd / rac_resnet_absmax_fwd / rac_resnet_conv_fwd <- img_backbone, mmdet ResNet(depth=50, style='pytorch',
  *                        norm_eval=True) (configs/racformer_r50_nuimg_704x256_f8.py:67-76, models/racformer.py:107-126) and the
  *                        input normalisation of models/racformer.py:202-212
+ *   rac_resnet_conv_dgrad / rac_resnet_conv_wgrad / rac_resnet_relu_bwd <- autograd of the same Bottleneck stages (frozen_stages=1,
+ *                        norm_eval=True: the stem and layer1 need no backward, the BatchNorms stay folded)
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -85,7 +87,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 29
+#define RAC_ABI_VERSION 30
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1147,6 +1149,50 @@ typedef struct {
 int rac_resnet_stem_fwd(const rac_resnet_stem *d, void *stream);
 int rac_resnet_absmax_fwd(const float *x, float *parts, int N, int64_t per_image, void *stream);
 int rac_resnet_conv_fwd(const rac_resnet_conv *d, void *stream);
+
+/* ---- Backward of one Bottleneck convolution (csrc/resnet_bwd.hip): what training through the backbone needs behind the frozen stem.
+ * BatchNorms stay folded (norm_eval: the forward under autograd is the folded convolution); W below is the FOLDED weight, the caller
+ * turns dW / db into the gradients of the convolution weight and the BatchNorm affine (resnet.fold_bn_backward).  Channel-first f32, no
+ * float atomics, every sum in one fixed order, launch geometry from the shapes alone, nothing read back; every argument is checked
+ * before any launch.  Sizes: H x W is the convolution's INPUT map, Ho x Wo its output, Ho = (H + 2 pad - ksize) / stride + 1 (both are
+ * arguments and must agree: 7 and 8 both map to 4); ksize 1 (pad 0) or 3 (pad 1); stride 1 or 2; any H, W >= 1.
+ *
+ * rac_resnet_conv_dgrad: the data gradient with the backward's element-wise work in its epilogue,
+ *     out[n][ci][p] = M( sum_{co,ky,kx} W[co][ci][ky][kx] * g[n][co][q] [+ add[n][ci][p]] ),  stride * q + (ky, kx) - pad == p
+ *   Cin a multiple of 64, Cout a multiple of 32, both at most 2048
+ *   g          device f32 [N][Cout][Ho*Wo];  out, add (or NULL), mask (or NULL): device f32 [N][Cin][H*W]
+ *   w_image    device f16 line image [Cin][ksize*ksize*Cout/32][hi 32 | lo 32] of W^T * 2^s: rac_gemm_split_pack_fwd on [Cin][K] with
+ *              K index = ((ksize - 1 - ky) * ksize + (ksize - 1 - kx)) * Cout + co (the taps flipped); w_alpha = 2^-s; 16-byte aligned
+ *   amax_parts rac_resnet_absmax_fwd of g (one power-of-two scale per image, as in the forward)
+ *   add        the identity branch or an outside gradient, added before the mask
+ *   mask       the convolution's own post-ReLU input: an element with mask <= 0 is +0 exactly (the ReLU backward of the layer in front)
+ *   Split-precision f16 MFMA (hi / lo per operand, three products, fp32 accumulate).
+ *
+ * rac_resnet_conv_wgrad: dW[co][ci][ky][kx] = sum_{n,q} g[n][co][q] * x[n][ci][stride * q + (ky, kx) - pad],  db[co] = sum_{n,q} g[n][co][q]
+ *   Cout a multiple of 64, Cin a multiple of 32, both at most 2048
+ *   g          device f32 [N][Cout][Ho*Wo];  x device f32 [N][Cin][H*W]
+ *   dw         device f32 [Cout][Cin][ksize][ksize];  db device f32 [Cout] or NULL
+ *   k_splits   K = N * Ho * Wo in units of 32 pixels of one image (N * ceil(Ho * Wo / 32) units) is cut into k_splits contiguous
+ *              ranges of ceil(units / k_splits) units; 1 <= k_splits <= units and no range may be empty
+ *   workspace  device f32 [k_splits][ksize*ksize][Cout][Cin] + [k_splits][Cout]: the ranges' partial sums, added in ascending range
+ *              order by a second launch.  Bitwise reproducible for equal k_splits.
+ *   Both operands split f16, one power-of-two scale per channel and K range.
+ *
+ * rac_resnet_relu_bwd: out[i] = y[i] > 0 ? a[i] [+ b[i]] : +0 for count elements (b may be NULL; out may alias a or b). */
+typedef struct {
+    const float *g;
+    const void *w_image;
+    const float *add;
+    const float *mask;
+    const float *amax_parts;
+    float *out;
+    float w_alpha;
+    int N, H, W, Ho, Wo, Cin, Cout, ksize, stride;
+} rac_resnet_dgrad;
+int rac_resnet_conv_dgrad(const rac_resnet_dgrad *d, void *stream);
+int rac_resnet_conv_wgrad(const float *g, const float *x, float *workspace, float *dw, float *db, int N, int Cin, int H, int W, int Cout,
+                          int Ho, int Wo, int ksize, int stride, int k_splits, void *stream);
+int rac_resnet_relu_bwd(const float *y, const float *a, const float *b, float *out, int64_t count, void *stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,9 @@ SIGNATURES = {
     "rac_resnet_stem_fwd": (_i, [_vp, _vp]),
     "rac_resnet_absmax_fwd": (_i, [_vp, _vp, _i, ctypes.c_int64, _vp]),
     "rac_resnet_conv_fwd": (_i, [_vp, _vp]),
+    "rac_resnet_conv_dgrad": (_i, [_vp, _vp]),
+    "rac_resnet_conv_wgrad": (_i, [_vp] * 5 + [_i] * 10 + [_vp]),
+    "rac_resnet_relu_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
 }
 
 
@@ -175,6 +178,12 @@ class ResnetConv(ctypes.Structure):
     """rac_resnet_conv (include/racformer_hip.h)"""
     _fields_ = [(n, _vp) for n in ("in_", "w_image", "bias", "residual", "amax_parts", "out")] + [("w_alpha", _f)] \
         + [(n, _i) for n in ("N", "H", "W", "Cin", "Cout", "ksize", "stride", "relu")]
+
+
+class ResnetDgrad(ctypes.Structure):
+    """rac_resnet_dgrad (include/racformer_hip.h)"""
+    _fields_ = [(n, _vp) for n in ("g", "w_image", "add", "mask", "amax_parts", "out")] + [("w_alpha", _f)] \
+        + [(n, _i) for n in ("N", "H", "W", "Ho", "Wo", "Cin", "Cout", "ksize", "stride")]
 
 
 RESNET_AMAX_PARTS = 64

@@ -19,7 +19,26 @@ rule, ``hip_route`` tells):
           atomics, nothing read back, one stream; intermediates live in the scratch namespace in force
           (``fused.scratch_namespace``), allocated once per shape; only the returned stage maps are new tensors.  Folded and packed
           weights are cached per convolution until one of its five tensors (weight, BatchNorm affine, running statistics) changes.
-  torch   everything else -- the CPU, training, ``fused=False`` (the timing tool's baseline): ``F.conv2d`` / ``F.batch_norm``.
+  HIP, training   the same conditions with autograd recording for a parameter, the class attribute ``fused_grad`` set (opt-in,
+          default False; ``hip_grad_route``), a frozen stem (``frozen_stages >= 0``) and images that need no gradient: one
+          ``torch.autograd.Function`` (``_ResNetCore``) over the whole backbone.  ``norm_eval`` keeps every BatchNorm on its running
+          statistics, so the forward under autograd is the folded-convolution forward above, bit for bit (``forward_hip_train``): the
+          stem and every stage before the first one with a trainable parameter run on scratch as before, from that stage on each
+          block's ``x, t1, t2, y`` are new tensors, saved for the backward (no scratch buffer is saved; ``with_cp`` is ignored: no
+          activation checkpointing on this route).  The backward (csrc/resnet_bwd.hip) walks the blocks last to first; per block, from
+          the masked gradient ``g3`` of its output: the weight gradient of ``conv3`` from ``(g3, t2)``, ``gt2 = dgrad(conv3; mask =
+          t2)``, the weight gradient and the stride-aware data gradient of ``conv2`` (``gt1``, masked by ``t1``), the weight gradient of
+          ``conv1``, the identity branch (``dgrad(downsample; add = the outside gradient of the stage map below)`` and the downsample's
+          weight gradient, or ``g3`` itself) and ``gx = dgrad(conv1; add = identity gradient, mask = x)``, the next block's ``g3``.
+          ``rac_resnet_conv_dgrad`` carries the ReLU backward and the adds in its epilogue; ``rac_resnet_relu_bwd`` covers the
+          network's last block and a stage output whose only gradient comes from outside.  ``rac_resnet_conv_wgrad`` gives the folded
+          weight's and shift's gradients, ``fold_bn_backward`` (float64 torch, rounded once) turns them into those of the convolution
+          weight and the BatchNorm affine.  Every launch is skipped where nothing asks for its result (frozen parameters, a ``None``
+          output gradient, the data gradient into the first trainable block's input).  No atomics, fixed summation orders: two runs
+          give the same bits.  Open point: ``pack_conv_weight`` / ``pack_conv_weight_t`` read the weight maximum back once per weight
+          version, which in training is once per convolution and step (a device-side weight scale is not built).
+  torch   everything else -- the CPU, training without ``fused_grad``, a trainable stem, images that require a gradient,
+          ``fused=False`` (the timing tool's baseline): ``F.conv2d`` / ``F.batch_norm``.
 
 ``input_norm = dict(mean, std, to_rgb)`` (``data_aug['img_norm_cfg']``) makes the stem apply models/racformer.py:202-212 --
 ``(x[:, [2, 1, 0]] - mean) / std``, subtract and then a float32 division -- while it stages the image (no pass of its own over the
@@ -29,8 +48,8 @@ What the f8 configuration does not use raises ``NotImplementedError`` in the con
 ``deep_stem``, ``avg_down``, ``dcn``, ``plugins``, ``conv_cfg``, dilations, other norm types, ``in_channels != 3``.  ``with_cp`` is
 accepted (ignored on the HIP route).
 
-Out of scope: a HIP backward (training takes the torch route, as for the necks and ``DepthNet``); bf16 / fp16 storage; VoVNet and the
-reference's ``CustomResNet``; ``GridMask`` and the colour augmentation (training only); ``pad_multiple`` (a no-op at 256 x 704); fusing
+Out of scope: a backward for the stem and the max pool, training-mode BatchNorm (``norm_eval=False``), activation checkpointing on the
+HIP route, fusing a Bottleneck's backward into fewer kernels; bf16 / fp16 storage; VoVNet and the reference's ``CustomResNet``; ``GridMask`` and the colour augmentation (training only); ``pad_multiple`` (a no-op at 256 x 704); fusing
 a whole Bottleneck into one kernel; writing the necks' operands from the last block's epilogue (DESIGN.md 3.21 lists the last two as
 open points)."""
 import ctypes
@@ -39,6 +58,7 @@ import math
 import torch
 import torch.nn as nn
 import torch.utils.checkpoint as cp
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import fused as _fused
@@ -138,6 +158,240 @@ def conv_fwd(x, packed, bias, ksize, stride, residual=None, relu=True, out=None,
     return out
 
 
+# ------------------------------------------------------------------------------------------------------- backward, functional
+def conv_wgrad_k_splits(n, ho, wo, cin, cout, ksize):
+    """Number of K ranges of rac_resnet_conv_wgrad for a shape (n images, output map ho x wo): about 512 workgroups (two per CU) over
+    the taps and the launcher's tiles (128 co x 128 ci where Cout is a multiple of 128 and Cin at least 128, 64 x 64 below), in units of
+    32 output pixels of one image, none empty.  A function of the shape alone: a shape always sums in the same order."""
+    units = n * ((ho * wo + 31) // 32)
+    tile = 128 if cout % 128 == 0 and cin >= 128 else 64
+    tiles = ksize * ksize * (cout // tile) * (-(-cin // tile))
+    want = max(1, min(units, 512 // tiles))
+    per = -(-units // want)
+    return -(-units // per)
+
+
+def pack_conv_weight_t(weight):
+    """Folded convolution weight [Cout, Cin, k, k] fp32 (device) -> (f16 line image [Cin, k*k*Cout/32, 64] of its transpose with the
+    taps flipped, K = (flipped tap, co), times 2^s; 2^-s) for rac_resnet_conv_dgrad (rac_gemm_split_pack_fwd's image)."""
+    co, ci, kh, kw = weight.shape
+    w = weight.detach().float().flip(2, 3).permute(1, 2, 3, 0).reshape(ci, kh * kw * co).contiguous()
+    amax = float(w.abs().max())
+    if co % 32 != 0 or not w.is_cuda or amax != amax or amax == float("inf"):
+        raise RuntimeError("resnet.pack_conv_weight_t: a device weight with Cout a multiple of 32 and finite values is needed")
+    s = 13 - math.frexp(amax)[1] + 1 if amax > 0.0 else 0
+    img = torch.empty(ci, kh * kw * co // 32, 64, device=w.device, dtype=torch.float16)
+    _lib.check(_lib.lib().rac_gemm_split_pack_fwd(_lib.ptr(w), _lib.ptr(img), ci, kh * kw * co, float(2.0 ** s), _lib.stream_ptr()),
+               "rac_gemm_split_pack_fwd")
+    return img, 2.0 ** (-s)
+
+
+def _grad_maps(what, *tensors):
+    _lib.require_gpu(*tensors, what=what)
+    if any(t.dtype != torch.float32 or t.dim() != 4 for t in tensors):
+        raise RuntimeError(f"{what}: contiguous float32 [n, C, H, W] tensors expected")
+
+
+def conv_dgrad(g, packed_t, ksize, stride, size, add=None, mask=None, parts=None):
+    """g float32 device [n, Cout, Ho, Wo] (the gradient of a convolution's output), ``packed_t`` = pack_conv_weight_t of its folded
+    weight, ``size`` = (H, W) of the convolution's input -> [n, Cin, H, W] = the gradient of that input [+ add], zero where
+    ``mask <= 0`` (rac_resnet_absmax_fwd of g unless ``parts`` is given, then rac_resnet_conv_dgrad)."""
+    extra = [t for t in (add, mask) if t is not None]
+    _grad_maps("resnet.conv_dgrad", g, *extra)
+    n, cout, ho, wo = g.shape
+    h, w = int(size[0]), int(size[1])
+    img, alpha = packed_t
+    cin = img.shape[0]
+    if img.shape[1] * 32 != ksize * ksize * cout or conv_out_size(h, w, ksize, stride) != (ho, wo):
+        raise RuntimeError("resnet.conv_dgrad: g must be [n, Cout, Ho, Wo] of the packed weight's convolution on an H x W input")
+    if any(tuple(t.shape) != (n, cin, h, w) for t in extra):
+        raise RuntimeError("resnet.conv_dgrad: add and mask must be float32 [n, Cin, H, W]")
+    if parts is None:
+        parts = image_absmax(g)
+    out = torch.empty(n, cin, h, w, device=g.device, dtype=torch.float32)
+    d = _lib.ResnetDgrad(_lib.ptr(g), _lib.ptr(img), _lib.ptr(add) if add is not None else None,
+                         _lib.ptr(mask) if mask is not None else None, _lib.ptr(parts), _lib.ptr(out), float(alpha), n, h, w, ho, wo,
+                         cin, cout, ksize, stride)
+    _lib.check(_lib.lib().rac_resnet_conv_dgrad(ctypes.byref(d), _lib.stream_ptr()), "rac_resnet_conv_dgrad")
+    return out
+
+
+def conv_wgrad(g, x, ksize, stride, bias=True, k_splits=None):
+    """g float32 device [n, Cout, Ho, Wo], x [n, Cin, H, W] (the convolution's input) -> (dW [Cout, Cin, k, k], db [Cout] or None): the
+    gradients of the folded weight and shift (rac_resnet_conv_wgrad: partial sums per range of pixels, added in a fixed order)."""
+    _grad_maps("resnet.conv_wgrad", g, x)
+    n, cin, h, w = x.shape
+    cout, ho, wo = g.shape[1:]
+    if g.shape[0] != n or conv_out_size(h, w, ksize, stride) != (ho, wo):
+        raise RuntimeError("resnet.conv_wgrad: g must be [n, Cout, Ho, Wo] of the convolution of x")
+    k = conv_wgrad_k_splits(n, ho, wo, cin, cout, ksize) if k_splits is None else int(k_splits)
+    work = torch.empty(max(k, 1) * (ksize * ksize * cout * cin + cout), device=x.device, dtype=torch.float32)
+    dw = torch.empty(cout, cin, ksize, ksize, device=x.device, dtype=torch.float32)
+    db = torch.empty(cout, device=x.device, dtype=torch.float32) if bias else None
+    _lib.check(_lib.lib().rac_resnet_conv_wgrad(_lib.ptr(g), _lib.ptr(x), _lib.ptr(work), _lib.ptr(dw), _lib.ptr(db) if bias else None,
+                                                n, cin, h, w, cout, ho, wo, ksize, stride, k, _lib.stream_ptr()), "rac_resnet_conv_wgrad")
+    return dw, db
+
+
+def relu_bwd(y, a, b=None):
+    """y, a[, b] float32 device tensors of one shape -> where(y > 0, a [+ b], 0) (rac_resnet_relu_bwd)."""
+    given = [t for t in (y, a, b) if t is not None]
+    _lib.require_gpu(*given, what="resnet.relu_bwd")
+    if any(t.dtype != torch.float32 or t.shape != y.shape for t in given) or y.numel() < 1:
+        raise RuntimeError("resnet.relu_bwd: non-empty float32 tensors of one shape expected")
+    out = torch.empty_like(y)
+    _lib.check(_lib.lib().rac_resnet_relu_bwd(_lib.ptr(y), _lib.ptr(a), _lib.ptr(b) if b is not None else None, _lib.ptr(out),
+                                              y.numel(), _lib.stream_ptr()), "rac_resnet_relu_bwd")
+    return out
+
+
+def fold_bn_backward(dw_folded, db_folded, weight, bn, need=None):
+    """Backward of ``fold_bn``: the gradients of the folded weight W' = W * s and shift b' = beta - mean * s (s = gamma / sqrt(var +
+    eps)) -> (dW, dgamma, dbeta) = (dW' * s, (sum_{ci,ky,kx} dW' * W - mean * db') / sqrt(var + eps), db'), in float64, rounded to
+    float32 once.  Only what requires a gradient is computed (``need`` = three flags; default: the tensors' ``requires_grad``), the
+    rest is None; ``db_folded`` may be None where neither BatchNorm gradient is needed."""
+    nw, ng, nb = (weight.requires_grad, bn.weight.requires_grad, bn.bias.requires_grad) if need is None else need
+    inv = 1.0 / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    dw = dgamma = dbeta = None
+    if nw:
+        s = bn.weight.detach().double() * inv
+        dw = (dw_folded.double() * s.view(-1, 1, 1, 1)).float()
+    if ng:
+        dot = (dw_folded.double() * weight.detach().double()).sum(dim=(1, 2, 3))
+        dgamma = ((dot - bn.running_mean.detach().double() * db_folded.double()) * inv).float()
+    if nb:
+        dbeta = db_folded.double().float()
+    return dw, dgamma, dbeta
+
+
+def trainable_blocks(model):
+    """[(stage, block)] of every Bottleneck from the first stage with a parameter that requires a gradient on, in forward order."""
+    stages = [getattr(model, name) for name in model.res_layers]
+    first = next((i for i, st in enumerate(stages) if any(p.requires_grad for p in st.parameters())), len(stages))
+    return [(i, b) for i in range(first, len(stages)) for b in range(len(stages[i]))]
+
+
+def forward_hip_train(model, x):
+    """The HIP forward as the autograd route runs it: x [n, 3, H, W] -> (outs, saved).  ``outs``: the ``out_indices`` stage maps, bit
+    for bit ``forward_hip``'s.  ``saved``: one ``(x, t1, t2, y)`` per block of ``trainable_blocks(model)``, in forward order -- the
+    block's input, its two post-ReLU intermediates and its post-ReLU output, all new tensors (a block's ``y`` is the next block's
+    ``x``); the backward takes its ReLU decisions from them.  The stem and the stages before run on scratch."""
+    _lib.require_gpu(x.contiguous(), what="ResNet")
+    blocks = trainable_blocks(model)
+    first = blocks[0][0] if blocks else len(model.res_layers)
+    h = model.stem_hip(x)
+    outs, saved = [], []
+    for i in range(len(model.res_layers)):
+        if i < first:
+            h = model.stage_hip(i, h)
+        else:
+            if i == first and (i == 0 or i - 1 not in model.out_indices):
+                h = h.clone()                    # (the stage's input is scratch: the backward reads it long after)
+            for b in range(len(getattr(model, model.res_layers[i]))):
+                h = model.block_hip(i, b, h, save=saved)
+        if i in model.out_indices:
+            outs.append(h)
+    return tuple(outs), saved
+
+
+class _ResNetCore(torch.autograd.Function):
+    """The backbone's HIP forward under autograd: apply(model, x, *(conv.weight, bn.weight, bn.bias per convolution of
+    ``trainable_blocks``, in ``Bottleneck.convs()`` order)) -> the ``out_indices`` stage maps, bit for bit the no-grad route's.  Saved:
+    ``forward_hip_train``'s tensors (the parameters and running statistics are read from the modules).  The backward walks the blocks last to first (module docstring); each launch
+    runs only where ``ctx.needs_input_grad`` asks for its result or for something behind it; a ``None`` output gradient adds nothing.
+    Nothing is read back but the weight maxima of the transposed packs (once per weight version).  The launchers are looked up as
+    this module's globals at call time."""
+
+    @staticmethod
+    def forward(ctx, model, x, *params):
+        outs, saved = forward_hip_train(model, x)
+        ctx.model, ctx.blocks = model, trainable_blocks(model)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*[t for blk in saved for t in blk])
+        first = ctx.blocks[0][0]
+        stages = [i for i in range(len(model.res_layers)) if i in model.out_indices]
+        ctx.mark_non_differentiable(*[o for o, i in zip(outs, stages) if i < first])      # (as on the torch route: frozen stages)
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gouts):
+        model, blocks = ctx.model, ctx.blocks
+        saved = [ctx.saved_tensors[4 * k:4 * k + 4] for k in range(len(blocks))]
+        flags = ctx.needs_input_grad[2:]
+        # per block: {convolution name: (position of its three parameters, the three flags)}
+        need, pos = [], 0
+        for i, b in blocks:
+            per = {}
+            for name, _, _ in getattr(model, model.res_layers[i])[b].convs():
+                per[name] = (pos, tuple(flags[pos:pos + 3]))
+                pos += 3
+            need.append(per)
+        grads = [None] * pos
+        wanted = [k for k, per in enumerate(need) if any(any(f) for _, f in per.values())]
+        if not wanted:
+            return (None, None, *grads)
+        first = wanted[0]
+        outside = {}                                              # stage -> its map's gradient from outside, or None
+        for j, i in enumerate(i for i in range(len(model.res_layers)) if i in model.out_indices):
+            outside[i] = gouts[j].contiguous() if gouts[j] is not None else None
+
+        def below(k):
+            """the outside gradient of block k's input, if that is a stage map"""
+            i, b = blocks[k]
+            return outside.get(i - 1) if b == 0 else None
+
+        def conv_of(k, name):
+            i, b = blocks[k]
+            return next((c, m) for n, c, m in getattr(model, model.res_layers[i])[b].convs() if n == name)
+
+        def param_grads(k, name, g, xin, ksize, stride):
+            at, (nw, ng, nb) = need[k][name]
+            if not (nw or ng or nb):
+                return
+            conv, bn = conv_of(k, name)
+            dw, db = conv_wgrad(g, xin, ksize, stride, bias=bool(ng or nb))
+            grads[at:at + 3] = fold_bn_backward(dw, db, conv.weight, bn, (nw, ng, nb))
+
+        def packed_t(k, name):
+            return model._pack(blocks[k] + (name, "t"), *conv_of(k, name), pack_conv_weight_t)[0]
+
+        top = outside.get(blocks[-1][0])
+        g3 = relu_bwd(saved[-1][3], top) if top is not None else None
+        for k in range(len(blocks) - 1, first - 1, -1):
+            i, b = blocks[k]
+            blk = getattr(model, model.res_layers[i])[b]
+            x, t1, t2, y = saved[k]
+            need_dx = k > first
+            if g3 is None:
+                # nothing arrives from above: the block's input may still be a stage map with a gradient of its own
+                if need_dx and below(k) is not None:
+                    g3 = relu_bwd(x, below(k))
+                continue
+            n1, n2 = any(need[k]["conv1"][1]), any(need[k]["conv2"][1])
+            param_grads(k, "conv3", g3, t2, 1, 1)
+            parts3 = image_absmax(g3) if (need_dx or n1 or n2) else None
+            gt1 = None
+            if need_dx or n1 or n2:
+                gt2 = conv_dgrad(g3, packed_t(k, "conv3"), 1, 1, t2.shape[2:], mask=t2, parts=parts3)
+                param_grads(k, "conv2", gt2, t1, 3, blk.stride)
+                if need_dx or n1:
+                    gt1 = conv_dgrad(gt2, packed_t(k, "conv2"), 3, blk.stride, t1.shape[2:], mask=t1)
+                    param_grads(k, "conv1", gt1, x, 1, 1)
+            if blk.downsample is not None:
+                param_grads(k, "downsample", g3, x, 1, blk.stride)
+            if not need_dx:
+                break
+            if blk.downsample is not None:
+                gid = conv_dgrad(g3, packed_t(k, "downsample"), 1, blk.stride, x.shape[2:], add=below(k), parts=parts3)
+            else:
+                if below(k) is not None:
+                    raise RuntimeError("ResNet: a stage whose first block has no downsample is not supported by the HIP backward")
+                gid = g3
+            g3 = conv_dgrad(gt1, packed_t(k, "conv1"), 1, 1, x.shape[2:], add=gid, mask=x)
+        return (None, None, *grads)
+
+
 def norm_args(input_norm):
     """``input_norm`` -> (perm, mean, std) lists of three, or None."""
     if input_norm is None:
@@ -214,7 +468,10 @@ class Bottleneck(nn.Module):
 class ResNet(nn.Module):
     """mmdet 2.28.2's ``ResNet`` for the Bottleneck depths, with its constructor arguments, defaults and state-dict keys
     (``conv1.weight``, ``bn1.*``, ``layer{s}.{b}.conv{1,2,3}.weight``, ``layer{s}.{b}.bn{1,2,3}.*``,
-    ``layer{s}.{b}.downsample.{0.weight,1.*}``), plus ``fused`` and the attribute ``input_norm`` (module docstring)."""
+    ``layer{s}.{b}.downsample.{0.weight,1.*}``), plus ``fused`` and the attributes ``input_norm`` and ``fused_grad`` (module
+    docstring)."""
+
+    fused_grad = False      # opt-in: run the HIP route under autograd as well (``hip_grad_route``); off, training takes the torch route
 
     def __init__(self, depth, in_channels=3, stem_channels=None, base_channels=64, num_stages=4, strides=(1, 2, 2, 2),
                  dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style='pytorch', deep_stem=False, avg_down=False, frozen_stages=-1,
@@ -308,8 +565,8 @@ class ResNet(nn.Module):
         return self
 
     # ------------------------------------------------------------------------------------------------------------------ routes
-    def hip_route(self, x):
-        """True if this call runs on the kernels (the conditions of the module docstring)."""
+    def _kernels_fit(self, x):
+        """The conditions of both HIP routes that have nothing to do with gradients."""
         if not self.fused or self.stem_channels != 64 or self.base_channels % 64 != 0 or self.feat_dim > 2048:
             return False
         if any(s not in (1, 2) for s in self.strides[:self.num_stages]):
@@ -320,15 +577,36 @@ class ResNet(nn.Module):
             return False
         if any(m.training for m in self.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)):
             return False
+        return True
+
+    def hip_route(self, x):
+        """True if this call runs on the kernels (the conditions of the module docstring)."""
+        if not self._kernels_fit(x):
+            return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
         return True
+
+    def hip_grad_route(self, x):
+        """True if this call runs on the kernels under autograd: ``fused_grad``, the kernels fit, autograd records for a parameter, the
+        stem is frozen and the images need no gradient."""
+        if not self.fused_grad:
+            return False
+        if not self._kernels_fit(x) or not torch.is_grad_enabled() or x.requires_grad or self.frozen_stages < 0:
+            return False
+        if any(p.requires_grad for m in (self.conv1, self.bn1) for p in m.parameters()):
+            return False
+        return any(p.requires_grad for p in self.parameters())
 
     def forward(self, x):
         """x [B*T*N, 3, H, W] -> tuple of [B*T*N, C_i, H_i, W_i], one per member of ``out_indices``."""
         if self.hip_route(x):
             with torch.no_grad():
                 return self.forward_hip(x)
+        if self.hip_grad_route(x):
+            params = [p for i, b in trainable_blocks(self) for _, conv, bn in getattr(self, self.res_layers[i])[b].convs()
+                      for p in (conv.weight, bn.weight, bn.bias)]
+            return _ResNetCore.apply(self, x, *params)
         if self.input_norm is not None:
             x = apply_input_norm(x, self.input_norm)
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
@@ -340,15 +618,18 @@ class ResNet(nn.Module):
         return tuple(outs)
 
     # --------------------------------------------------------------------------------------------------------------- HIP route
-    def _pack(self, key, conv, bn):
-        """Folded and packed operands of one convolution, kept until one of its five tensors is replaced, written in place or moved."""
+    def _pack(self, key, conv, bn, packer=None):
+        """Folded and packed operands of one convolution, kept until one of its five tensors is replaced, written in place or moved.
+        ``packer``: the packing of the folded weight (default: the forward's)."""
         tensors = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
         sig = tuple((t.data_ptr(), t._version, str(t.device)) for t in tensors)
         hit = self._packs.get(key)
         if hit is None or hit[0] != sig:
             with torch.no_grad():
                 w, shift = fold_bn(conv.weight, bn)
-                hit = self._packs[key] = (sig, (pack_stem_weight(w) if key == "stem" else pack_conv_weight(w), shift))
+                if packer is None:
+                    packer = pack_stem_weight if key == "stem" else pack_conv_weight
+                hit = self._packs[key] = (sig, (packer(w), shift))
         return hit[1]
 
     def stem_hip(self, x):
@@ -358,9 +639,9 @@ class ResNet(nn.Module):
         (_, _), (hp, wp) = stem_sizes(x.shape[2], x.shape[3])
         return stem_fwd(x, w147, bias, self.input_norm, out=_scratch("stem_out", (x.shape[0], 64, hp, wp), x.device))
 
-    def block_hip(self, i, b, x, out=None):
+    def block_hip(self, i, b, x, out=None, save=None):
         """Bottleneck b of stage i on the kernels: three or four convolutions, each behind the per-image maximum of its input.
-        ``out`` None: a new tensor."""
+        ``out`` None: a new tensor.  ``save``: a list that receives ``(x, t1, t2, y)``, the two intermediates then new tensors too."""
         blk = getattr(self, self.res_layers[i])[b]
         n, dev = x.shape[0], x.device
         parts = _scratch("amax", (n, _lib.RESNET_AMAX_PARTS), dev)
@@ -368,17 +649,21 @@ class ResNet(nn.Module):
         h, w = x.shape[2], x.shape[3]
         ho, wo = conv_out_size(h, w, 3, blk.stride)
         image_absmax(x, parts)
-        t1 = conv_fwd(x, *pk["conv1"], 1, 1, out=_scratch("t1", (n, blk.planes, h, w), dev), parts=parts)
+        keep = save is not None
+        t1 = conv_fwd(x, *pk["conv1"], 1, 1, out=None if keep else _scratch("t1", (n, blk.planes, h, w), dev), parts=parts)
         identity = x
         if blk.downsample is not None:
             identity = conv_fwd(x, *pk["downsample"], 1, blk.stride, relu=False,
                                 out=_scratch("down", (n, blk.planes * EXPANSION, ho, wo), dev), parts=parts)
         image_absmax(t1, parts)
-        t2 = conv_fwd(t1, *pk["conv2"], 3, blk.stride, out=_scratch("t2", (n, blk.planes, ho, wo), dev), parts=parts)
+        t2 = conv_fwd(t1, *pk["conv2"], 3, blk.stride, out=None if keep else _scratch("t2", (n, blk.planes, ho, wo), dev), parts=parts)
         image_absmax(t2, parts)
         if out is None:
             out = torch.empty(n, blk.planes * EXPANSION, ho, wo, device=dev, dtype=torch.float32)
-        return conv_fwd(t2, *pk["conv3"], 1, 1, residual=identity, out=out, parts=parts)
+        y = conv_fwd(t2, *pk["conv3"], 1, 1, residual=identity, out=out, parts=parts)
+        if keep:
+            save.append((x, t1, t2, y))
+        return y
 
     def stage_hip(self, i, x):
         """Stage i (``layer{i + 1}``) on the kernels; the result is a new tensor if i is in ``out_indices``, scratch otherwise.  Block

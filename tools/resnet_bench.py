@@ -13,7 +13,13 @@ spread) of device-event times in microseconds:
                        arithmetic in MAC, the executed FLOP (three f16 products per MAC in the stages, one fp32 fma in the stem),
                        achieved TFLOP/s and GB/s
   whole forward        hip_eager, hip_graph (one captured graph) and torch_eager
---errors: the (E_ref, err) pairs a `RAC_RESNET_ERRORS=<file> pytest -m gpu tests/test_resnet_gpu.py` session wrote; their largest
+--grad: forward + backward instead (``ResNet(50, frozen_stages=1)`` in ``train()``, one random output gradient per stage), with
+``fused_grad`` on and off on the same model and inputs, and the peak allocated memory of either route; the weights do not change between
+the repetitions, so the once-per-weight-version packing (and its read-back of the weight maximum) is not in these times.  --errors then
+names the figures a `RAC_RESNET_GRAD_ERRORS=<file> pytest -m gpu tests/test_resnet_grad_gpu.py` session wrote; they are copied into the
+record.
+    python tools/resnet_bench.py --grad --images 48 --out profiles/resnet_grad_f8.json [--errors resnet_grad_errors.json]
+--errors (without --grad): the (E_ref, err) pairs a `RAC_RESNET_ERRORS=<file> pytest -m gpu tests/test_resnet_gpu.py` session wrote; their largest
 err / E_ref per group goes into the record.
 """
 import argparse
@@ -172,15 +178,84 @@ def bench(images, reps, dev):
                 parts=rows)
 
 
+def bench_grad(images, reps, dev):
+    """Forward + backward of ResNet(50, frozen_stages=1) in train() with ``fused_grad`` on and off: one model, weights, inputs and one
+    random output gradient per stage; the routes alternate inside every repetition.  Rows: the whole step, and the step with only the
+    last one, two and three stages trainable (the forward is the same in all: the increments are what a stage's backward costs)."""
+    gen = torch.Generator().manual_seed(9)
+    m = resnet.ResNet(50, frozen_stages=1, norm_eval=True)
+    fill(m, gen)
+    m = m.to(dev).train()
+    m.input_norm = NORM
+    x = (torch.rand(images, 3, H, W, generator=gen) * 255.0).to(dev)
+    with torch.no_grad():
+        shapes = [tuple(o.shape) for o in m(x)]
+    gouts = [torch.randn(s, generator=gen).to(dev) for s in shapes]
+
+    def trainable_from(stage):
+        for i, name in enumerate(m.res_layers):
+            for p in getattr(m, name).parameters():
+                p.requires_grad_(i >= stage)
+
+    def step(switch, stage):
+        def run():
+            m.fused_grad = switch
+            trainable_from(stage)
+            for p in m.parameters():
+                p.grad = None
+            assert m.hip_grad_route(x) == switch
+            outs = m(x)
+            pairs = [(o, g) for o, g in zip(outs, gouts) if o.requires_grad]
+            torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
+        return run
+
+    rows, fns = {}, {}
+    for stage in (1, 2, 3):
+        key = "layer%d..4" % (stage + 1) if stage < 3 else "layer4"
+        fns[f"{key}:hip"], fns[f"{key}:torch"] = step(True, stage), step(False, stage)
+    t = timed(fns, reps, warmup=2)
+    peak = {}
+    for route, switch in (("hip", True), ("torch", False)):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        step(switch, 1)()
+        torch.cuda.synchronize()
+        peak[route] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+    for key in ("layer4", "layer3..4", "layer2..4"):
+        rows[key] = dict(hip=t[f"{key}:hip"], torch=t[f"{key}:torch"],
+                         faster="hip" if t[f"{key}:hip"]["median"] < t[f"{key}:torch"]["median"] else "torch")
+    inc = {}
+    for name, a, b in (("layer4", "layer4", None), ("layer3", "layer3..4", "layer4"), ("layer2", "layer2..4", "layer3..4")):
+        d = {r: round(rows[a][r]["median"] - (rows[b][r]["median"] if b else 0.0), 1) for r in ("hip", "torch")}
+        d["faster"] = "hip" if d["hip"] < d["torch"] else "torch"
+        inc[name] = d
+    return dict(images=images, forward_plus_backward=rows, increment_per_stage=inc, peak_allocated_GiB=peak,
+                note="increment_per_stage: layer4 = the step with only layer4 trainable (it contains the whole forward), layer3 and "
+                     "layer2 = what making that stage trainable as well adds (its backward and the tensors it keeps)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "build", "resnet_f8.json"))
     ap.add_argument("--errors", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--images", type=int, nargs="+", default=[48, 6])
+    ap.add_argument("--grad", action="store_true", help="forward + backward with fused_grad on and off (profiles/resnet_grad_f8.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "resnet_bench needs the MI355X"
     _lib.lib()
+    if args.grad:
+        rec = dict(shape=dict(image=[3, H, W], depth=50, frozen_stages=1, norm_eval=True, input_norm=NORM),
+                   device=torch.cuda.get_device_name(0), unit="us: median, 10th and 90th percentile of device-event times",
+                   reps=args.reps, runs=[bench_grad(n, args.reps, "cuda:0") for n in args.images])
+        if args.errors and os.path.exists(args.errors):
+            rec["test_figures"] = json.load(open(args.errors))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print(json.dumps({k: v for k, v in rec.items() if k != "test_figures"}, indent=1))
+        return
     rec = dict(shape=dict(image=[3, H, W], depth=50, input_norm=NORM), device=torch.cuda.get_device_name(0),
                unit="us: median, 10th and 90th percentile of device-event times", reps=args.reps,
                runs=[bench(n, args.reps, "cuda:0") for n in args.images])

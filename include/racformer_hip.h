@@ -87,7 +87,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 30
+#define RAC_ABI_VERSION 31
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1193,6 +1193,21 @@ int rac_resnet_conv_dgrad(const rac_resnet_dgrad *d, void *stream);
 int rac_resnet_conv_wgrad(const float *g, const float *x, float *workspace, float *dw, float *db, int N, int Cin, int H, int W, int Cout,
                           int Ho, int Wo, int ksize, int stride, int k_splits, void *stream);
 int rac_resnet_relu_bwd(const float *y, const float *a, const float *b, float *out, int64_t count, void *stream);
+
+/* The streaming detector's window gather (csrc/frames.hip; racformer_amd/detector.py, RaCFormer.simple_test_online): the front end's
+ * per-frame outputs live in one ring of n_slots frames per tensor kind, the decoder reads T frames of every kind as one contiguous
+ * window.  For every tensor k < n_tensors and frame t < T:
+ *     outs[k][t * frame_bytes[k] ..] = rings[k][slots[t] * frame_bytes[k] ..]          (frame_bytes[k] bytes)
+ *   rings, outs : HOST arrays of n_tensors device pointers, 16-byte aligned; ring k holds n_slots frames, out k holds T frames
+ *   frame_bytes : HOST int64 [n_tensors], positive multiples of 16 (a frame of the pyramid in the sampling layout at B = 1 is one
+ *                 contiguous block [G, N, H, W, 64] of rac_fpn_conv_fwd's output; a BEV frame is [C, Y, X])
+ *   slots       : HOST int32 [T], each in [0, n_slots); repeated slots are allowed
+ * All tables travel as kernel arguments: no device table, no upload, no synchronisation, no allocation -- capturable.  One launch for
+ * all tensors, 16 bytes per lane on both sides, workgroups divided among the tensors in proportion to their bytes.
+ * Limits: n_tensors <= 8, T <= 16.  Refused with RAC_E_ARG before any HIP call: a null pointer, a frame_bytes that is not a positive
+ * multiple of 16, a misaligned pointer, a slot outside [0, n_slots), n_tensors or T out of range. */
+int rac_frames_gather(int n_tensors, const void *const *rings, void *const *outs, const int64_t *frame_bytes, const int32_t *slots,
+                      int T, int n_slots, void *stream);
 
 #ifdef __cplusplus
 }

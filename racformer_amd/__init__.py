@@ -14,3 +14,4 @@ from .lss_depth import (LSSViewTransformerBEVDepth_racformer, depth_loss, pool_b
 from .depth_net import DepthNet  # noqa: E402,F401
 from .necks import FPN, CustomFPN  # noqa: E402,F401
 from .resnet import ResNet  # noqa: E402,F401
+from .detector import RaCFormer  # noqa: E402,F401

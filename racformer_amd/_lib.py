@@ -118,6 +118,7 @@ SIGNATURES = {
     "rac_resnet_conv_dgrad": (_i, [_vp, _vp]),
     "rac_resnet_conv_wgrad": (_i, [_vp] * 5 + [_i] * 10 + [_vp]),
     "rac_resnet_relu_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
+    "rac_frames_gather": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
 }
 
 

@@ -1787,3 +1787,27 @@ def lsap_host(cost_gq=None, cost_qg=None):
                                   ctypes.cast(ctypes.pointer(steps), ctypes.c_void_p))
     _lib.check(rc, "rac_lsap_host")
     return mq, mg, u, v, steps.value
+
+
+# ------------------------------------------------------------------------------------------- streaming frame memory
+def frames_gather(rings, outs, slots):
+    """The streaming detector's window from its frame memory in one launch (rac_frames_gather): for every pair
+    (``rings[k]`` [n_slots, *frame], ``outs[k]`` whose leading dimensions hold ``len(slots)`` frames of that shape) and every t,
+    frame t of ``outs[k]`` = frame ``slots[t]`` of ``rings[k]``.  Contiguous device tensors, a frame a multiple of 16 bytes; up to 8
+    tensors and 16 frames.  ``slots``: host integers -- they travel as kernel arguments, nothing is uploaded."""
+    rings, outs, slots = list(rings), list(outs), [int(s) for s in slots]
+    if len(rings) != len(outs) or not rings:
+        raise RuntimeError("frames_gather: one out per ring, at least one")
+    _lib.require_gpu(*rings, *outs, what="frames_gather")
+    n_slots, T = int(rings[0].shape[0]), len(slots)
+    fb = []
+    for r, o in zip(rings, outs):
+        frame = r[0].numel() * r.element_size() if r.shape[0] else 0
+        if r.shape[0] != n_slots or r.dtype != o.dtype or o.numel() * o.element_size() != T * frame:
+            raise RuntimeError("frames_gather: every ring holds n_slots frames and every out len(slots) frames of its ring's dtype and size")
+        fb.append(frame)
+    n = len(rings)
+    rc = _lib.lib().rac_frames_gather(n, (ctypes.c_void_p * n)(*[r.data_ptr() for r in rings]), (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]),
+                                      (ctypes.c_int64 * n)(*fb), (ctypes.c_int32 * max(T, 1))(*slots), T, n_slots, _lib.stream_ptr())
+    _lib.check(rc, "rac_frames_gather")
+    return outs

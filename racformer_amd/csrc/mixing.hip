@@ -227,7 +227,7 @@ __device__ __forceinline__ void mix_f32_core(const MixArgs &a, float *smem, int 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = 16 * m + lk * 4 + r;
-            const float y = fmaxf((acc1[m][r] - mean1) * rstd1, 0.f);
+            const float y = rac_relu((acc1[m][r] - mean1) * rstd1);
             sY[row * MIX_MS + 16 * wave + li] = row < P ? y : 0.f;
         }
     __syncthreads();
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_kernel(const MixArgs a)
     for (int m = 0; m < 8; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            sO[(16 * m + lk * 4 + r) * MIX_C + 16 * wave + li] = fmaxf((st.acc2[m][r] - st.mean2) * st.rstd2, 0.f);
+            sO[(16 * m + lk * 4 + r) * MIX_C + 16 * wave + li] = rac_relu((st.acc2[m][r] - st.mean2) * st.rstd2);
     __syncthreads();
     mix_write_out(a, sO, q, g, tid);
 }
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
             const int row = 16 * m + lk * 4 + r, col = 16 * wave + li;
             const float bh = (st.acc2[m][r] - st.mean2) * st.rstd2;
             if (b.z_out)
-                b.z_out[item_off * MIX_OUT * MIX_C + row * MIX_C + col] = fmaxf(bh, 0.f);
+                b.z_out[item_off * MIX_OUT * MIX_C + row * MIX_C + col] = rac_relu(bh);
             const float g2 = bh > 0.f ? gdz[row * MIX_C + col] : 0.f;
             s_g += g2;
             s_gb += g2 * bh;
@@ -559,7 +559,16 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
 //   * x @ M: both operands as three bf16 terms (24 significant bits, fp32 exponent range: the sampled image
 //     features are data, nothing bounds them), the six products down to 2^-16 relative kept (truncation 2^-23);
 //   * S @ Y: two f16 terms each (22 bits), products hi*hi + hi*lo + lo*hi (truncation 2^-22).  Y is LayerNorm
-//     output (|Y| < 79); |S| is bounded by the caller from the generator's weights (AdaptiveMixing.split_packs);
+//     output (|Y| < 79); |S| is bounded by the caller from the generator's weights (AdaptiveMixing.split_packs) -- from above
+//     only.  S * param_scale is split as it is, so below |S| = 2^-3 its lo half is an f16 subnormal and S carries an absolute
+//     error of up to 2^-25 whatever its size, which the second LayerNorm magnifies as it brings B back to O(1).  Measured
+//     (tests/test_mixing_fwd_f64_gpu.py, profiles/mixing_fwd_f64.json; error in units of 2^-24 of the largest output, the
+//     float32 restatement's own is 3.3 - 5.9 throughout): 3.2 - 5.2 for std(S) >= 2^-4, 17 - 19 at 2^-6, 56 - 76 at 2^-8,
+//     220 - 245 at 2^-10, 870 - 1090 at 2^-12: fp32 grade (within 4 x the restatement's error) down to std(S) = 2^-6, not below;
+//     by the tests' criterion with the subnormal floor taken out of its representation term, outside from 2^-8 down at P = 7
+//     and at 2^-12 at P = 96.  A per-item power-of-two scale of S (rac_act_scale of the item's max |S|, B multiplied by the
+//     exact inverse) removes this and was measured at +1.0 us on 83.5 us per f8 launch against a run-to-run spread of 0.2 us
+//     (profiles/mixing_fwd_s_scale_ab.json): left out, the tests assert the kernel to be as accurate as this representation allows;
 //   * x and S are converted once while being staged (LDS holds the 16-bit images, conflict-free row strides
 //     of 160 / 224 bytes for ds_read_b128 fragment reads);
 //   * wave w's slab of M (64 x 16) goes straight from global memory into B fragments (no LDS);
@@ -593,6 +602,17 @@ __device__ __forceinline__ void mix_split_bf16(float v, __bf16 &t1, __bf16 &t2, 
    workgroups share a CU's 160 KB */
 #define MIXH_REGION_BYTES (MIXH_S_BYTES > MIXH_X_BYTES ? MIXH_S_BYTES : MIXH_X_BYTES)
 #define MIXH_LDS_BYTES (MIXH_REGION_BYTES + 64)
+
+// relu(d * 2 * half_r) as rac_relu gives it -- a NaN stays a NaN, every other result is fmaxf's bits -- at fmaxf's cost.  With
+// h = d * half_r (half_r = 0.5f / std: the halving is exact), h + |h| is 2h for h > 0, +0 for h <= 0 (-0 included) and NaN for a
+// NaN; doubling is exact too, so 2h is the rounded d / std itself (only a result below 2^-125, a subnormal h, may lose its last
+// bit).  rac_relu's compare and select on top of the maximum cost this kernel 3 % of its time (profiles/mixing_fwd_s_scale_ab.json).
+__device__ __forceinline__ float mix_relu_ln(float d, float half_r)
+{
+#pragma clang fp contract(off)   // (fma(d, half_r, |h|) would add the product's rounding error where the sum has to be 2h or 0)
+    const float h = d * half_r;
+    return h + fabsf(h);
+}
 
 __device__ __forceinline__ void mix_split4(const rac_f4 v, float scale, rac_h4 &hi, rac_h4 &lo)
 {
@@ -752,7 +772,7 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = 2 * t + h, row = 16 * m + lk * 4 + r;
-                const float y = row < P ? fmaxf((acc1[m][r] - mean1) * rstd1, 0.f) : 0.f;
+                const float y = row < P ? mix_relu_ln(acc1[m][r] - mean1, 0.5f * rstd1) : 0.f;
                 _Float16 yh, yl;
                 rac_split_f16(y, yh, yl);
                 bYh[t][4 * h + r] = yh;
@@ -798,7 +818,7 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     for (int m = 0; m < 8; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            sO[(16 * m + lk * 4 + r) * MIX_C + 16 * wave + li] = fmaxf((acc2[m][r] - mean2) * rstd2, 0.f);
+            sO[(16 * m + lk * 4 + r) * MIX_C + 16 * wave + li] = mix_relu_ln(acc2[m][r] - mean2, 0.5f * rstd2);
     __syncthreads();
     mix_write_out(a, sO, q, g, tid);
 }

@@ -77,11 +77,13 @@ def _mean(t):
     return t.mean(dim=(-2, -1), keepdim=True)
 
 
-def _ln_scale(t, At, h, r):
-    """relative error scale of r = 1/sqrt(var + eps) and the scale of h = (t - mean) r, given A_t for t"""
+def _ln_scale(t, At, h, r, own=2.0):
+    """relative error scale of r = 1/sqrt(var + eps) and the scale of h = (t - mean) r, given A_t for t.  ``own``: the roundings
+    of r itself, in the unit A_t is counted in (0: A_t is an absolute perturbation of t and only its first-order image is
+    wanted, as tests/mixing_fwd_ref.py pushes the operand truncations of the split-precision kernel through the chain)"""
     d = (t - _mean(t)).abs()
     At_c = At + _mean(At)
-    r_rel = _mean(d * At_c) * r * r + 2.0
+    r_rel = _mean(d * At_c) * r * r + own
     return r * At_c + h.abs() * r_rel, r_rel
 
 

@@ -385,8 +385,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
                 const int p = 128 * wm + 16 * m + li;
                 if (p < prows) {
                     cv_f4 v = cv_fma4(acc[m][nn], unscale, bv);
-                    if (MODE == CV_OUT_NCHW_RELU)
-                        v = __builtin_elementwise_max(v, (cv_f4){0.f, 0.f, 0.f, 0.f});
+                    if (MODE == CV_OUT_NCHW_RELU)      // (rac_relu: a NaN stays a NaN, as torch.relu keeps it; the vector maximum returns 0)
+                        v = (cv_f4){rac_relu(v[0]), rac_relu(v[1]), rac_relu(v[2]), rac_relu(v[3])};
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         obase[(size_t)(col + r) * HW + p] = v[r];

@@ -62,6 +62,11 @@ __device__ __forceinline__ float cd_scale(const rac_cd_scale &s)
 {
     return rac_act_scale((s.amax ? s.mul * *s.amax : 0.f) + s.add);
 }
+// the ReLU epilogues: rac_relu per component -- a NaN stays a NaN, as torch.relu keeps it (the vector maximum returns 0 for one)
+__device__ __forceinline__ cd_f4 cd_relu4(cd_f4 v)
+{
+    return (cd_f4){rac_relu(v[0]), rac_relu(v[1]), rac_relu(v[2]), rac_relu(v[3])};
+}
 
 // Workgroup = 4 waves = 64 PT consecutive output pixels of one frame x one block of 16 NT output channels.
 //   NT  16-channel accumulator tiles per wave (A operand tiles, read from LDS)
@@ -251,7 +256,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
                     add += *reinterpret_cast<const cd_f4 *>(a.pixel_map + (size_t)p * a.Cout + c);
                 cd_f4 v = __builtin_elementwise_fma(acc[nn][j], us4, add);
                 if constexpr (EPI != 0)
-                    v = __builtin_elementwise_max(v, (cd_f4){0.f, 0.f, 0.f, 0.f});
+                    v = cd_relu4(v);
                 if constexpr (EPI == 2) {
                     float *ocf = a.out_f32 + ((size_t)n * a.Cout + c) * npix + p;
 #pragma unroll
@@ -285,7 +290,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
                 const cd_f4 bv = a.bias ? *reinterpret_cast<const cd_f4 *>(a.bias + c) : (cd_f4){0.f, 0.f, 0.f, 0.f};
                 cd_f4 v = __builtin_elementwise_fma(acc[nn][j], us4, bv);
                 if constexpr (EPI != 0)
-                    v = __builtin_elementwise_max(v, (cd_f4){0.f, 0.f, 0.f, 0.f});
+                    v = cd_relu4(v);
                 store_img(c, v);
             }
             continue;

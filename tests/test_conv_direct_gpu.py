@@ -1,7 +1,9 @@
 """rac_conv_direct_fwd / rac_upsample2x_image_fwd / rac_conv3x3_temporal_fwd (round 5: the ConvGRU branch of
 RadarBEVTemporalEncoder, models/racformer_transformer.py:645-656, 674-720, on own kernels) against float64 convolutions and the
-torch modules they replace.  Every mode of the direct convolution, both strides, compile-time and run-time chunk counts, ragged
-pixel tiles, frame maps; the GRU update against ConvGRUCell; the fold of the constant hidden half against the explicit image."""
+torch modules they replace.  The image, f32 and GRU modes of the direct convolution, both strides, several of the instantiated chunk
+counts (the chunk count is a template parameter: every K loop is straight-line code, csrc/conv_direct.hip, rac_conv_direct_fwd), ragged
+pixel tiles, frame maps; the GRU update against ConvGRUCell; the fold of the constant hidden half against the explicit image.
+Every instantiation, element by element against float64: tests/test_conv_fwd_f64_gpu.py."""
 import math
 
 import pytest
@@ -35,8 +37,8 @@ def image_values(img, scale):
 @pytest.mark.parametrize("N,T,Tv,H,W,cin", [(8, 8, 4, 32, 32, 256), (4, 4, 2, 16, 24, 64), (3, 3, 3, 12, 20, 96)])
 def test_stride2_image_mode_vs_float64(N, T, Tv, H, W, cin):
     """The downsample convolution out of the fusion image's x half (of the LIVE frames of each group) into an activation image whose
-    scale comes from the weights' bound; cin = 256 takes the straight-line K loop (8 chunks), the others the run-time loop; 12 x 20
-    maps leave a ragged last pixel tile (60 output pixels)."""
+    scale comes from the weights' bound; cin = 256 / 64 / 96 are the instantiations with 8 / 2 / 3 chunks; 12 x 20 maps leave a
+    ragged last pixel tile (60 output pixels)."""
     from racformer_amd.fused import ConvImage, act_image, conv_direct, pack_conv3x3_weight
     g = torch.Generator().manual_seed(N * H + cin)
     conv = torch.nn.Conv2d(cin, 64, 3, stride=2, padding=1)

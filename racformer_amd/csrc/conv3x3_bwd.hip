@@ -29,12 +29,7 @@
 //   K split: the N*H image rows are dealt out in `k_splits` contiguous ranges; workgroup (range p, tile) writes its partial sums
 //   to workspace[p][tap][co][Cin], and a second launch adds the ranges in ascending p -- a fixed order, no float atomics: two runs
 //   give the same bits.
-#include "rac_common.h"
-
-typedef _Float16 cb_h8 __attribute__((ext_vector_type(8)));
-typedef float cb_f4 __attribute__((ext_vector_type(4)));
-typedef __fp16 cb_q4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) cb_q4 *cb_lds_q4;
+#include "split_f16.h"
 
 #define CB_COUT 256
 #define CB_TM 128          /* co per workgroup */
@@ -64,7 +59,7 @@ __global__ __launch_bounds__(256) void conv_pack_cl_kernel(const float *__restri
     const float scale = rac_act_scale(*amax);
     const rac_f4 v0 = rac_ld4(src + i * 8), v1 = rac_ld4(src + i * 8 + 4);
     const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    cb_h8 hi, lo;
+    rac_h8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float s = v[j] * scale;
@@ -73,8 +68,8 @@ __global__ __launch_bounds__(256) void conv_pack_cl_kernel(const float *__restri
     }
     const size_t p = ((size_t)n * (H + 2) + h + 1) * (W + 2) + w + 1;
     _Float16 *o = dst + (p * chunks_total + chunk0 + (c8 >> 2)) * 64 + (c8 & 3) * 8;
-    *reinterpret_cast<cb_h8 *>(o) = hi;
-    *reinterpret_cast<cb_h8 *>(o + 32) = lo;
+    *reinterpret_cast<rac_h8 *>(o) = hi;
+    *reinterpret_cast<rac_h8 *>(o + 32) = lo;
 }
 
 // ------------------------------------------------------------------------------------------------ weight gradient
@@ -84,17 +79,6 @@ struct WgradArgs {
     float *ws;          // partial sums [k_splits][9][256][Cin]
     int N, H, W, chunks, k_splits;
 };
-
-__device__ __forceinline__ cb_h8 cb_tr_frag(const char *lds, int off0, int off1)
-{
-    union {
-        struct { cb_q4 a, b; } s;
-        cb_h8 v;
-    } u;
-    u.s.a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((cb_lds_q4)(lds + off0));
-    u.s.b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((cb_lds_q4)(lds + off1));
-    return u.v;
-}
 
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_f16x3_kernel(const WgradArgs a)
 {
@@ -116,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_f16x3_kernel(const Wgrad
         const int idx = tid + 256 * j;
         const int r = idx >> 5, cc = (idx >> 3) & 3, hl = (idx >> 2) & 1, s = idx & 3;
         const int ch = cc * 4 + s;
-        g_lds[j] = hl * CB_G_BYTES + 256 * r + 16 * (ch ^ (((r & 3) << 2) | ((r >> 2) & 3)));
+        g_lds[j] = hl * CB_G_BYTES + 256 * r + 16 * (ch ^ rac_tr_swz(r));
     }
     // (rows 102 .. 127 of the X image are padding: written with a re-read of the last halo pixel, never read)
     const int x_lds = 2 * CB_G_BYTES + ((tid >> 2) & 1) * CB_X_BYTES + 64 * (tid >> 3) + 16 * ((tid & 3) ^ (2 * ((tid >> 6) & 1)));
@@ -148,14 +132,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_f16x3_kernel(const Wgrad
         *reinterpret_cast<uint4 *>(S_ + g_lds[1] + 4096) = rg3; *reinterpret_cast<uint4 *>(S_ + x_lds + 6144) = rx3; \
     } while (0)
 
-    cb_f4 acc[2][2][9];
+    rac_f4v acc[2][2][9];
 #pragma unroll
     for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int t = 0; t < 9; ++t)
-                acc[mm][nt][t] = (cb_f4){0.f, 0.f, 0.f, 0.f};
+                acc[mm][nt][t] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 
     // transposed-read addresses: lane 4 q + p of a 16-lane group supplies row q, elements 4 p .. 4 p + 3 of the block's 16 channels,
     // i.e. 16-byte slot (p >> 1) of the block's two, byte 8 (p & 1) in it.  Block blk of lane group lk holds pixels 8 lk + 4 blk + q.
@@ -166,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_f16x3_kernel(const Wgrad
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
             const int r = 8 * lk + 4 * blk + q, ch = 2 * (2 * wave + mm) + (p >> 1);
-            ga[mm][blk] = 256 * r + 16 * (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))) + 8 * (p & 1);
+            ga[mm][blk] = 256 * r + 16 * (ch ^ rac_tr_swz(r)) + 8 * (p & 1);
         }
     const int xrow0 = 8 * lk + q;   // X halo row of block 0 at tap (0, 0); tap (dy, dx) adds dy * CB_XCOLS + dx, block 1 adds 4
 
@@ -178,24 +162,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_f16x3_kernel(const Wgrad
             const int nxt = step + 1 < nsteps ? step + 1 : step;
             CB_GLOAD(nxt);     // (past the end the last tile is re-fetched: unconditional code)
             const char *S = cb_lds + (step & 1) * CB_STAGE_BYTES;
-            cb_h8 ah[2], al[2];
+            rac_h8 ah[2], al[2];
 #pragma unroll
             for (int mm = 0; mm < 2; ++mm) {
-                ah[mm] = cb_tr_frag(S, ga[mm][0], ga[mm][1]);
-                al[mm] = cb_tr_frag(S + CB_G_BYTES, ga[mm][0], ga[mm][1]);
+                ah[mm] = rac_tr_frag(S, ga[mm][0], ga[mm][1]);
+                al[mm] = rac_tr_frag(S + CB_G_BYTES, ga[mm][0], ga[mm][1]);
             }
             const char *SX = S + 2 * CB_G_BYTES;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int r0 = xrow0 + (t / 3) * CB_XCOLS + (t % 3), r1 = r0 + 4;
-                cb_h8 bh[2], bl[2];
+                rac_h8 bh[2], bl[2];
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const int s = 2 * nt + (p >> 1);
                     const int o0 = 64 * r0 + 16 * (s ^ (2 * ((r0 >> 3) & 1))) + 8 * (p & 1);
                     const int o1 = 64 * r1 + 16 * (s ^ (2 * ((r1 >> 3) & 1))) + 8 * (p & 1);
-                    bh[nt] = cb_tr_frag(SX, o0, o1);
-                    bl[nt] = cb_tr_frag(SX + CB_X_BYTES, o0, o1);
+                    bh[nt] = rac_tr_frag(SX, o0, o1);
+                    bl[nt] = rac_tr_frag(SX + CB_X_BYTES, o0, o1);
                 }
 #pragma unroll
                 for (int mm = 0; mm < 2; ++mm)

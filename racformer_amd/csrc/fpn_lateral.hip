@@ -35,13 +35,7 @@
 //   dX[n][ci][p] = sum_co W[co][ci] * G[n][co][p]
 // is this GEMM with K = 256, the merged gradient G as x (per-pixel scale as above), the line image of W^T (rac_linear_pack_wt) as the
 // weights and Cin output channels in blocks of 256.  The rest of the backward is fpn_lateral_bwd.hip.
-#include "rac_common.h"
-
-typedef _Float16 fl_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 fl_h4 __attribute__((ext_vector_type(4)));
-typedef float fl_f4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fl_q4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) fl_q4 *fl_lds_q4;
+#include "split_f16.h"
 
 #define FL_COUT 256
 
@@ -55,19 +49,6 @@ struct FpnLateralArgs {
     int HW, W, chunks, hc, wc, tiles_per_img;
     int cout, nblk;      // data gradient only: output channels (rows of the weight image that are stored), blocks of 256 of them
 };
-
-__device__ __forceinline__ fl_h8 fl_tr_frag(const char *lds, int off0, int off1)
-{
-    union {
-        struct { fl_q4 a, b; } s;
-        fl_h8 v;
-    } u;
-    u.s.a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((fl_lds_q4)(lds + off0));
-    u.s.b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((fl_lds_q4)(lds + off1));
-    return u.v;
-}
-
-__device__ __forceinline__ int fl_swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
 // NJ: 16-pixel MFMA tiles per workgroup (8: 128 pixels, 4: 64 pixels).  VEC: 16-byte loads (H*W % 4 == 0, x 16-byte aligned).
 // HAS_TOP: the top-down term is gathered in the epilogue.
@@ -104,14 +85,14 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
 #pragma unroll
     for (int e = 0; e < (VEC ? 2 : 8); ++e)
         s_off[e] = VEC ? min(s_p + 4 * e, HW - 4) : min(s_p + e, HW - 1);
-    auto gload = [&](int c, fl_f4 *rx) {
+    auto gload = [&](int c, rac_f4v *rx) {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const float *row = xn + (size_t)(c * 32 + s_rb + RP * j) * HW;
             if (VEC) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
-                    rx[2 * j + h] = *reinterpret_cast<const fl_f4 *>(row + s_off[h]);
+                    rx[2 * j + h] = *reinterpret_cast<const rac_f4v *>(row + s_off[h]);
             } else {
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
     for (int e = 0; e < 8; ++e)
         mx[e] = 0.f;
     for (int c = 0; c < chunks; c += 4) {
-        fl_f4 r4[4][2 * NI];
+        rac_f4v r4[4][2 * NI];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             gload(min(c + u, chunks - 1), r4[u]);
@@ -164,35 +145,35 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
     }
     __syncthreads();     // the scales are in place and the maxima read: the stages may be written
 
-    fl_f4 rx[2 * NI];
+    rac_f4v rx[2 * NI];
     auto lstore = [&](int buf) {
         char *S = fl_lds + buf * STAGE;
-        const fl_f4 sc0 = *reinterpret_cast<const fl_f4 *>(fl_scale + 8 * s_ch), sc1 = *reinterpret_cast<const fl_f4 *>(fl_scale + 8 * s_ch + 4);
+        const rac_f4v sc0 = *reinterpret_cast<const rac_f4v *>(fl_scale + 8 * s_ch), sc1 = *reinterpret_cast<const rac_f4v *>(fl_scale + 8 * s_ch + 4);
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int r = s_rb + RP * j;
-            fl_h8 hi, lo;
+            rac_h8 hi, lo;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float s = rx[2 * j + (e >> 2)][e & 3] * (e < 4 ? sc0[e & 3] : sc1[e & 3]);
                 hi[e] = (_Float16)s;
                 lo[e] = (_Float16)(s - (float)hi[e]);
             }
-            char *d = S + RB * r + 16 * (s_ch ^ (fl_swz(r) & (TPR - 1)));
-            *reinterpret_cast<fl_h8 *>(d) = hi;
-            *reinterpret_cast<fl_h8 *>(d + HALF) = lo;
+            char *d = S + RB * r + 16 * (s_ch ^ (rac_tr_swz(r) & (TPR - 1)));
+            *reinterpret_cast<rac_h8 *>(d) = hi;
+            *reinterpret_cast<rac_h8 *>(d + HALF) = lo;
         }
     };
 
     // weight fragments of this wave's 64 output channels: tile i = rows 64 wave + 16 i + li, chunk lk of the line's hi / lo half
     const char *__restrict__ wrow = a.w + (size_t)(cbase + 64 * wave + li) * chunks * 128 + lk * 16;
     const size_t wstep = (size_t)16 * chunks * 128;
-    fl_h8 wh[4], wl[4], nwh[4], nwl[4];
+    rac_h8 wh[4], wl[4], nwh[4], nwl[4];
     auto wload = [&](int c) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            nwh[i] = *reinterpret_cast<const fl_h8 *>(wrow + i * wstep + (size_t)c * 128);
-            nwl[i] = *reinterpret_cast<const fl_h8 *>(wrow + i * wstep + (size_t)c * 128 + 64);
+            nwh[i] = *reinterpret_cast<const rac_h8 *>(wrow + i * wstep + (size_t)c * 128);
+            nwl[i] = *reinterpret_cast<const rac_h8 *>(wrow + i * wstep + (size_t)c * 128 + 64);
         }
     };
 
@@ -205,17 +186,17 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
         const int q = li >> 2, p = li & 3;
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
-            const int r = 8 * lk + 4 * blk + q, sw = fl_swz(r) & (TPR - 1);
+            const int r = 8 * lk + 4 * blk + q, sw = rac_tr_swz(r) & (TPR - 1);
             xa[blk] = RB * r + 16 * ((p >> 1) ^ sw) + 8 * (p & 1);
         }
     }
 
-    fl_f4 acc[4][NJ];
+    rac_f4v acc[4][NJ];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-            acc[i][j] = (fl_f4){0.f, 0.f, 0.f, 0.f};
+            acc[i][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 
     // ---- second walk: the products.  (Uniform control flow over the workgroup: the transposed reads need every lane active.)
     gload(0, rx);
@@ -239,8 +220,8 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
         asm volatile("" : "+v"(xa0), "+v"(xa1));     // (per step: otherwise the 2 NJ tile addresses are hoisted out of the loop -- and spilled)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            const fl_h8 xh = fl_tr_frag(S, xa0 ^ (32 * j), xa1 ^ (32 * j));
-            const fl_h8 xl = fl_tr_frag(S + HALF, xa0 ^ (32 * j), xa1 ^ (32 * j));
+            const rac_h8 xh = rac_tr_frag(S, xa0 ^ (32 * j), xa1 ^ (32 * j));
+            const rac_h8 xl = rac_tr_frag(S + HALF, xa0 ^ (32 * j), xa1 ^ (32 * j));
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], xh, acc[i][j], 0, 0, 0);
@@ -262,10 +243,10 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
     float *__restrict__ on = a.out + (size_t)n * (DG ? a.cout : FL_COUT) * HW + (size_t)cbase * HW;
     const int tplane = a.hc * a.wc;
     const float *__restrict__ tn = HAS_TOP ? a.top + (size_t)n * FL_COUT * tplane : nullptr;
-    fl_f4 bv[4];
+    rac_f4v bv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        bv[i] = a.bias ? *reinterpret_cast<const fl_f4 *>(a.bias + 64 * wave + 16 * i + 4 * lk) : (fl_f4){0.f, 0.f, 0.f, 0.f};
+        bv[i] = a.bias ? *reinterpret_cast<const rac_f4v *>(a.bias + 64 * wave + 16 * i + 4 * lk) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int pl = 16 * j + li, p = p0 + pl;
@@ -289,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_kernel(const FpnLateralArg
             for (int i = 0; i < 4; ++i) {
                 if (DG && cbase + 64 * wave + 16 * i >= a.cout)      // (wave-uniform: a.cout is a multiple of 32)
                     continue;
-                const fl_f4 v = __builtin_elementwise_fma(acc[i][j], (fl_f4){us, us, us, us}, bv[i]);
+                const rac_f4v v = __builtin_elementwise_fma(acc[i][j], (rac_f4v){us, us, us, us}, bv[i]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     on[(size_t)(64 * wave + 16 * i + 4 * lk + r) * HW + p] = HAS_TOP ? v[r] + tv[i][r] : v[r];

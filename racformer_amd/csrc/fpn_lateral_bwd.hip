@@ -13,26 +13,18 @@
 //
 // Weight gradient.  Both operands are channel-first, so the reduction index (the pixel) is the contiguous one: a lane's MFMA fragment
 // -- 8 consecutive k of one row (A: G's channel co) or one column (B: x's channel ci) -- is 8 consecutive pixels of one channel, and
-// the LDS image needs no transpose.  K is cut into units of 32 pixels of one image; a workgroup owns a contiguous range of units
-// (k_splits ranges, none empty) and a tile of all 256 co x CT ci (CT = 128, or 64 for narrow levels), and writes its partial sums to
-// a workspace [k_splits][256][Cin] that a second launch adds in ascending range order (the scheme of rac_conv3x3_wgrad).
+// the LDS image needs no transpose.  The split-K scheme, its per-channel scale, LDS image, epilogue and reduce launch are
+// wgrad_splitk.h's (shared with resnet_bwd.hip); this file has the loader, the tile and the bias sums.  A workgroup owns a K range
+// and a tile of all 256 co x CT ci (CT = 128, or 64 for narrow levels); workspace [k_splits][256][Cin].
 // Arithmetic as in the forward: v * 2^e = hi + lo (two f16), the three leading products per K step in v_mfma_f32_16x16x32_f16, fp32
-// accumulate.  The reduction runs over pixels, so a per-pixel scale does not factor out of it; a scale per CHANNEL does (it is constant
-// along k for a row of A and for a column of B).  Each workgroup therefore takes one power-of-two scale per channel and K range -- the
-// largest value of that channel within the range lands in [2^13, 2^14) -- from a first walk over its range (maxima; the bias sums
-// ride along), and multiplies the two exact factors back in the epilogue.  No pass over the maps for a global maximum, nothing the
-// host has to read, and a range of small gradients keeps its 22 bits beside a range of large ones.  The second walk finds the range
-// in L2 / the Infinity Cache.
+// accumulate.  No pass over the maps for a global maximum, nothing the host has to read, and a range of small gradients keeps its
+// 22 bits beside a range of large ones.  The second walk finds the range in L2 / the Infinity Cache.
 // Workgroup = 256 threads = 4 waves; wave w owns co 64 w .. 64 w + 63 x the CT ci = 4 x NJ MFMA tiles.  Per unit the (256 + CT) x 32
-// fp32 block goes global -> registers (one unit ahead, under the MFMAs) -> (scale, split) -> LDS rows of 64 B hi and 64 B lo; 16-byte
-// slot s of row r sits at slot s ^ (3 * ((r >> 3) & 1)): the 16-lane groups of ds_read_b128 then touch 16 distinct slots of a 256-byte
-// line.  Pixels past the image are loaded from a clamped address and replaced by zero; ci rows past Cin (a last tile of fewer than
+// fp32 block goes global -> registers (one unit ahead, under the MFMAs) -> (scale, split) -> LDS.  Pixels past the image are loaded
+// from a clamped address and replaced by zero; ci rows past Cin (a last tile of fewer than
 // CT) re-read row Cin - 1 and are not stored.  One LDS stage, two barriers per unit; two workgroups share a CU.
 // db: the threads that stage G add their values in fp32 during the first walk (tile 0's workgroups only), per range, in a fixed order.
-#include "rac_common.h"
-
-typedef _Float16 fb_h8 __attribute__((ext_vector_type(8)));
-typedef float fb_f4 __attribute__((ext_vector_type(4)));
+#include "wgrad_splitk.h"
 
 #define FB_COUT 256
 
@@ -87,8 +79,6 @@ struct FpnWgradArgs {
     int Cin, HW, upi, units, per, ntiles;      // upi: units of 32 pixels per image; per: units per K range
 };
 
-__device__ __forceinline__ int fb_slot(int row, int s) { return s ^ (3 * ((row >> 3) & 1)); }
-
 // NJ: 16-channel MFMA tiles of ci per workgroup (8: CT = 128, 4: CT = 64).  VEC: 16-byte loads (H*W % 4 == 0, g and x 16-byte aligned).
 template <int NJ, bool VEC>
 __global__ __launch_bounds__(256, 2) void fpn_lateral_wgrad_kernel(const FpnWgradArgs a)
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_wgrad_kernel(const FpnWgra
 #pragma unroll
     for (int j = 0; j < NP - 4; ++j)
         xrow[j] = min(CT * ct + 64 * j + s_r, Cin - 1);
-    auto gload = [&](int u, fb_f4 *rx) {
+    auto gload = [&](int u, rac_f4v *rx) {
         const int n = u / a.upi, p0 = (u - n * a.upi) * 32 + 8 * s_q;
         const float *__restrict__ gn = a.g + (size_t)n * FB_COUT * HW;
         const float *__restrict__ xn = a.x + (size_t)n * Cin * HW;
@@ -121,8 +111,8 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_wgrad_kernel(const FpnWgra
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int p = p0 + 4 * h;
-                    const fb_f4 v = *reinterpret_cast<const fb_f4 *>(row + min(p, HW - 4));
-                    rx[2 * j + h] = p < HW ? v : (fb_f4){0.f, 0.f, 0.f, 0.f};
+                    const rac_f4v v = *reinterpret_cast<const rac_f4v *>(row + min(p, HW - 4));
+                    rx[2 * j + h] = p < HW ? v : (rac_f4v){0.f, 0.f, 0.f, 0.f};
                 }
             } else {
 #pragma unroll
@@ -138,15 +128,15 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_wgrad_kernel(const FpnWgra
     // ---- first walk: per-channel maxima over this K range (and the bias sums, by the workgroups of tile 0)
     const bool do_bias = a.wsb != nullptr && ct == 0;
     float mx[NP];
-    fb_f4 bs[4];
+    rac_f4v bs[4];
 #pragma unroll
     for (int j = 0; j < NP; ++j)
         mx[j] = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        bs[j] = (fb_f4){0.f, 0.f, 0.f, 0.f};
+        bs[j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
     for (int u = u0; u < u1; ++u) {
-        fb_f4 r[2 * NP];
+        rac_f4v r[2 * NP];
         gload(u, r);
 #pragma unroll
         for (int j = 0; j < NP; ++j)
@@ -164,117 +154,43 @@ __global__ __launch_bounds__(256, 2) void fpn_lateral_wgrad_kernel(const FpnWgra
     float sc[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        float m = mx[j];
-        m = fmaxf(m, __shfl_xor(m, 1));
-        m = fmaxf(m, __shfl_xor(m, 2));
-        // 2^(13 - e) with e = floor(log2(max)), exponent arithmetic only (max = 0 / denormal / inf: clamped exponents), as the forward
-        int eb = (int)((__float_as_uint(m) >> 23) & 255u);
-        eb = eb < 14 ? 14 : (eb > 254 ? 254 : eb);
-        sc[j] = __uint_as_float((unsigned)(267 - eb) << 23);
+        float us;
+        sc[j] = wg_row_scale(mx[j], us);
         if (s_q == 0)
-            fb_unscale[64 * j + s_r] = __uint_as_float((unsigned)(eb - 13) << 23);
+            fb_unscale[64 * j + s_r] = us;
     }
     if (do_bias) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float t = (bs[j][0] + bs[j][1]) + (bs[j][2] + bs[j][3]);
-            t += __shfl_xor(t, 1);
-            t += __shfl_xor(t, 2);
+            const float t = wg_row_sum((bs[j][0] + bs[j][1]) + (bs[j][2] + bs[j][3]));
             if (s_q == 0)
                 a.wsb[(size_t)split * FB_COUT + 64 * j + s_r] = t;
         }
     }
 
-    // ---- second walk: the products
-    fb_f4 acc[4][NJ];
+    // ---- second walk: the products.  Wave w owns co 64 w .. 64 w + 63 x the CT ci = 4 x NJ MFMA tiles.
+    rac_f4v acc[4][NJ];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-            acc[i][j] = (fb_f4){0.f, 0.f, 0.f, 0.f};
-    const int a_off = (64 * wave + li) * 64 + 16 * fb_slot(li, lk);          // tile i: + 1024 i  (row & 8 == li & 8)
-    const int b_off = (FB_COUT + li) * 64 + 16 * fb_slot(li, lk);            // tile j: + 1024 j
-    fb_f4 rx[2 * NP];
+            acc[i][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
+    const int a_off = wg_frag_off(64 * wave, li, lk), b_off = wg_frag_off(FB_COUT, li, lk);
+    rac_f4v rx[2 * NP];
     gload(u0, rx);
     for (int u = u0; u < u1; ++u) {
 #pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int row = 64 * j + s_r;
-            fb_h8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float s = rx[2 * j + (e >> 2)][e & 3] * sc[j];
-                hi[e] = (_Float16)s;
-                lo[e] = (_Float16)(s - (float)hi[e]);
-            }
-            char *d = fb_lds + row * 64 + 16 * fb_slot(row, s_q);
-            *reinterpret_cast<fb_h8 *>(d) = hi;
-            *reinterpret_cast<fb_h8 *>(d + HALF) = lo;
-        }
+        for (int j = 0; j < NP; ++j)
+            wg_stage(fb_lds, HALF, 64 * j + s_r, s_q, sc[j], [&](int e) { return rx[2 * j + (e >> 2)][e & 3]; });
         __syncthreads();
         gload(u + 1 < u1 ? u + 1 : u, rx);      // (past the end the last unit again: unconditional code)
         __builtin_amdgcn_sched_barrier(0);      // (the conversion of the next unit, and the wait for these loads, stay behind the MFMAs)
-        fb_h8 ah[4], al[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ah[i] = *reinterpret_cast<const fb_h8 *>(fb_lds + a_off + 1024 * i);
-            al[i] = *reinterpret_cast<const fb_h8 *>(fb_lds + HALF + a_off + 1024 * i);
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const fb_h8 bh = *reinterpret_cast<const fb_h8 *>(fb_lds + b_off + 1024 * j);
-            const fb_h8 bl = *reinterpret_cast<const fb_h8 *>(fb_lds + HALF + b_off + 1024 * j);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh, acc[i][j], 0, 0, 0);
-        }
+        wg_products<3>(fb_lds, HALF, a_off, b_off, acc);
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();      // every wave has read the stage: the next unit may overwrite it
     }
 
-    // ---- epilogue.  Accumulator tile (i, j): rows 4 lk + r = co, column li = ci: per co the 16 lanes li store 64 contiguous bytes.
-    // (Two exact power-of-two factors one after the other: their product could leave the float range.)
-    float *__restrict__ wp = a.ws + (size_t)split * FB_COUT * Cin;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int ci = CT * ct + 16 * j + li;
-        if (ci < Cin) {
-            const float ux = fb_unscale[FB_COUT + 16 * j + li];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = 64 * wave + 16 * i + 4 * lk + r;
-                    wp[(size_t)co * Cin + ci] = acc[i][j][r] * fb_unscale[co] * ux;
-                }
-        }
-    }
-}
-
-// dW = the k_splits partial sums added in ascending order; db likewise
-__global__ __launch_bounds__(256) void fpn_lateral_wgrad_reduce_kernel(const float *__restrict__ ws, const float *__restrict__ wsb,
-                                                                       float *__restrict__ dw, float *__restrict__ db, int per,
-                                                                       int k_splits)
-{
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < per) {
-        float s = 0.f;
-        for (int p = 0; p < k_splits; ++p)
-            s += ws[(size_t)p * per + e];
-        dw[e] = s;
-    } else if (db && e < per + FB_COUT) {
-        const int co = e - per;
-        float s = 0.f;
-        for (int p = 0; p < k_splits; ++p)
-            s += wsb[(size_t)p * FB_COUT + co];
-        db[co] = s;
-    }
+    wg_store(a.ws + (size_t)split * FB_COUT * Cin, fb_unscale, FB_COUT, acc, CT * ct, Cin, wave, li, lk);
 }
 
 extern "C" int rac_fpn_lateral_wgrad(const float *g, const float *x, float *workspace, float *dw, float *db, int N, int Cin, int H,
@@ -284,24 +200,17 @@ extern "C" int rac_fpn_lateral_wgrad(const float *g, const float *x, float *work
     RAC_CHECK_ARG(Cout == FB_COUT, "%s: built for %d output channels (got %d)", what, FB_COUT, Cout);
     RAC_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cin <= 2048, "%s: Cin=%d (a multiple of 32 from 32 to 2048)", what, Cin);
     RAC_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && (long)H * W < (1l << 30), "%s: N=%d H=%d W=%d", what, N, H, W);
-    const int HW = H * W, upi = (HW + 31) / 32;
-    RAC_CHECK_ARG((long)N * upi < (1l << 31), "%s: N=%d H=%d W=%d (too many K units)", what, N, H, W);
-    const int units = N * upi;
-    RAC_CHECK_ARG(k_splits >= 1 && k_splits <= units, "%s: k_splits=%d (1 .. %d units of 32 pixels)", what, k_splits, units);
-    const int per = (units + k_splits - 1) / k_splits;
-    RAC_CHECK_ARG((long)(k_splits - 1) * per < units, "%s: k_splits=%d leaves an empty range (%d units, %d per range)", what, k_splits,
-                  units, per);
-    RAC_CHECK_ARG(g && x && workspace && dw, "%s: null pointer", what);
-    RAC_CHECK_ARG(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace) |
-                    reinterpret_cast<uintptr_t>(dw) | reinterpret_cast<uintptr_t>(db)) & 3) == 0,
-                  "%s: pointers must be 4-byte aligned", what);
+    WgSplit ks;
+    if (const int rc = wg_split(what, "H", "W", N, H, W, k_splits, g, x, workspace, dw, db, ks))
+        return rc;
+    const int HW = H * W;
     const bool wide = Cin >= 128;
     const int ctile = wide ? 128 : 64, ntiles = (Cin + ctile - 1) / ctile;
     RAC_CHECK_ARG((long)k_splits * ntiles < (1l << 31), "%s: %ld workgroups", what, (long)k_splits * ntiles);
     FpnWgradArgs a;
     a.g = g; a.x = x; a.ws = workspace;
     a.wsb = db ? workspace + (size_t)k_splits * FB_COUT * Cin : nullptr;
-    a.Cin = Cin; a.HW = HW; a.upi = upi; a.units = units; a.per = per; a.ntiles = ntiles;
+    a.Cin = Cin; a.HW = HW; a.upi = ks.upi; a.units = ks.units; a.per = ks.per; a.ntiles = ntiles;
     const bool vec = HW % 4 == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
     const dim3 grid((unsigned)(k_splits * ntiles));
     hipStream_t st = (hipStream_t)stream;
@@ -309,8 +218,6 @@ extern "C" int rac_fpn_lateral_wgrad(const float *g, const float *x, float *work
     else if (wide) hipLaunchKernelGGL((fpn_lateral_wgrad_kernel<8, false>), grid, dim3(256), 0, st, a);
     else if (vec) hipLaunchKernelGGL((fpn_lateral_wgrad_kernel<4, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((fpn_lateral_wgrad_kernel<4, false>), grid, dim3(256), 0, st, a);
-    const int per_out = FB_COUT * Cin;
-    hipLaunchKernelGGL(fpn_lateral_wgrad_reduce_kernel, dim3((unsigned)((per_out + FB_COUT + 255) / 256)), dim3(256), 0, st, workspace,
-                       a.wsb, dw, db, per_out, k_splits);
+    wg_reduce(workspace, a.wsb, dw, db, FB_COUT, Cin, 1, k_splits, st);
     return rac_launch_status(what);
 }

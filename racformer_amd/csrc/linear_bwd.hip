@@ -44,12 +44,7 @@
 //   Column sums of the wide operand (db_gen = sum_m dP) come from the same pass: the staging threads add the fp32 values they
 //   convert (thread t: rows t / 16 and t / 16 + 16 of every step, ascending), and sixteen such row classes are added in ascending
 //   order at the end -- a fixed order, one writer per column.
-#include "rac_common.h"
-
-typedef _Float16 lb_h8 __attribute__((ext_vector_type(8)));
-typedef float lb_f4 __attribute__((ext_vector_type(4)));
-typedef __fp16 lb_q4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef __attribute__((address_space(3))) lb_q4 *lb_lds_q4;
+#include "split_f16.h"
 
 #define LB_NARROW 256
 #define LB_TW 128                                  /* wide columns per workgroup */
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(256) void linear_pack_act_kernel(const float *__res
     const float *p = src + row * ld_src + k8 * 8;
     const rac_f4 v0 = rac_ld4(p), v1 = rac_ld4(p + 4);
     const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    lb_h8 hi, lo;
+    rac_h8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float s = v[j] * scale;
@@ -81,8 +76,8 @@ __global__ __launch_bounds__(256) void linear_pack_act_kernel(const float *__res
         lo[j] = (_Float16)(s - (float)hi[j]);
     }
     _Float16 *o = img + (row * (K >> 5) + (k8 >> 2)) * 64 + (k8 & 3) * 8;
-    *reinterpret_cast<lb_h8 *>(o) = hi;
-    *reinterpret_cast<lb_h8 *>(o + 32) = lo;
+    *reinterpret_cast<rac_h8 *>(o) = hi;
+    *reinterpret_cast<rac_h8 *>(o + 32) = lo;
 }
 
 // Workgroup = one 32 x 32 tile of W through LDS: read along K (W's rows), written along N (the image's lines).
@@ -150,19 +145,6 @@ struct LinWgradArgs {
     int M, Wd;
 };
 
-__device__ __forceinline__ lb_h8 lb_tr_frag(const char *lds, int off0, int off1)
-{
-    union {
-        struct { lb_q4 a, b; } s;
-        lb_h8 v;
-    } u;
-    u.s.a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lb_lds_q4)(lds + off0));
-    u.s.b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lb_lds_q4)(lds + off1));
-    return u.v;
-}
-
-__device__ __forceinline__ int lb_swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-
 template <bool WIDE_MAJOR>
 __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgradArgs a)
 {
@@ -178,7 +160,7 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
     const int n_u = tid & 63, n_rb = tid >> 6, n_ch = 4 * ((tid >> 3) & 7) + (tid & 3), n_hl = (tid >> 2) & 1;
     const int w_rb = tid >> 4, w_ch = tid & 15;
     uint4 rn[8];
-    lb_f4 rw[4];
+    rac_f4v rw[4];
     float cs[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e)
@@ -197,8 +179,8 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
         for (int j = 0; j < 2; ++j) {
             const int m = m0 + w_rb + 16 * j;
             const float *p = a.wide + (size_t)min(m, M - 1) * a.ld_wide + b0 + 8 * w_ch;
-            const lb_f4 v0 = *reinterpret_cast<const lb_f4 *>(p), v1 = *reinterpret_cast<const lb_f4 *>(p + 4);
-            const lb_f4 z = {0.f, 0.f, 0.f, 0.f};
+            const rac_f4v v0 = *reinterpret_cast<const rac_f4v *>(p), v1 = *reinterpret_cast<const rac_f4v *>(p + 4);
+            const rac_f4v z = {0.f, 0.f, 0.f, 0.f};
             rw[2 * j] = m < M ? v0 : z;          // (a select, not a product: the masked row may hold anything)
             rw[2 * j + 1] = m < M ? v1 : z;
         }
@@ -209,12 +191,12 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int r = n_rb + 4 * j;
-            *reinterpret_cast<uint4 *>(S + n_hl * LB_N_BYTES + 512 * r + 16 * (n_ch ^ lb_swz(r))) = rn[j];
+            *reinterpret_cast<uint4 *>(S + n_hl * LB_N_BYTES + 512 * r + 16 * (n_ch ^ rac_tr_swz(r))) = rn[j];
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int r = w_rb + 16 * j;
-            lb_h8 hi, lo;
+            rac_h8 hi, lo;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float v = e < 4 ? rw[2 * j][e] : rw[2 * j + 1][e - 4];
@@ -224,18 +206,18 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
                 hi[e] = (_Float16)s;
                 lo[e] = (_Float16)(s - (float)hi[e]);
             }
-            char *d = S + 2 * LB_N_BYTES + 256 * r + 16 * (w_ch ^ lb_swz(r));
-            *reinterpret_cast<lb_h8 *>(d) = hi;
-            *reinterpret_cast<lb_h8 *>(d + LB_W_BYTES) = lo;
+            char *d = S + 2 * LB_N_BYTES + 256 * r + 16 * (w_ch ^ rac_tr_swz(r));
+            *reinterpret_cast<rac_h8 *>(d) = hi;
+            *reinterpret_cast<rac_h8 *>(d + LB_W_BYTES) = lo;
         }
     };
 
-    lb_f4 acc[4][8];
+    rac_f4v acc[4][8];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            acc[i][j] = (lb_f4){0.f, 0.f, 0.f, 0.f};
+            acc[i][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 
     // transposed-read addresses: lane 4 q + p of a 16-lane group supplies row q, elements 4 p .. 4 p + 3 of the tile's 16 columns, i.e.
     // 16-byte slot (p >> 1) of the tile's two, byte 8 (p & 1) in it.  Block blk of lane group lk holds rows 8 lk + 4 blk + q.
@@ -243,7 +225,7 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
     int na[4][2], wa[8][2];
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
-        const int r = 8 * lk + 4 * blk + q, sw = lb_swz(r);
+        const int r = 8 * lk + 4 * blk + q, sw = rac_tr_swz(r);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             na[i][blk] = 512 * r + 16 * ((8 * wave + 2 * i + (p >> 1)) ^ sw) + 8 * (p & 1);
@@ -260,16 +242,16 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
         const bool more = step + 1 < nsteps;
         gload(more ? step + 1 : step);      // (past the end the last tile is re-fetched: unconditional code)
         const char *S = lb_lds + (step & 1) * LB_STAGE_BYTES;
-        lb_h8 nh[4], nl[4];
+        rac_h8 nh[4], nl[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            nh[i] = lb_tr_frag(S, na[i][0], na[i][1]);
-            nl[i] = lb_tr_frag(S + LB_N_BYTES, na[i][0], na[i][1]);
+            nh[i] = rac_tr_frag(S, na[i][0], na[i][1]);
+            nl[i] = rac_tr_frag(S + LB_N_BYTES, na[i][0], na[i][1]);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const lb_h8 wh = lb_tr_frag(S, wa[j][0], wa[j][1]);
-            const lb_h8 wl = lb_tr_frag(S + LB_W_BYTES, wa[j][0], wa[j][1]);
+            const rac_h8 wh = rac_tr_frag(S, wa[j][0], wa[j][1]);
+            const rac_h8 wl = rac_tr_frag(S + LB_W_BYTES, wa[j][0], wa[j][1]);
             // smallest terms first (all four products: see the header); product-major, so that four independent accumulators lie between two MFMAs into the same one
             if (WIDE_MAJOR) {
 #pragma unroll
@@ -310,13 +292,13 @@ __global__ __launch_bounds__(256, 1) void linear_wgrad_split_kernel(const LinWgr
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const lb_f4 v = acc[i][j] * inv_n * inv_w;
+            const rac_f4v v = acc[i][j] * inv_n * inv_w;
             if (WIDE_MAJOR) {
                 const int na_ = 64 * wave + 16 * i + 4 * lk, b = b0 + 16 * j + li;
-                *reinterpret_cast<lb_f4 *>(a.out + (size_t)b * LB_NARROW + na_) = v;
+                *reinterpret_cast<rac_f4v *>(a.out + (size_t)b * LB_NARROW + na_) = v;
             } else {
                 const int na_ = 64 * wave + 16 * i + li, b = b0 + 16 * j + 4 * lk;
-                *reinterpret_cast<lb_f4 *>(a.out + (size_t)na_ * a.Wd + b) = v;
+                *reinterpret_cast<rac_f4v *>(a.out + (size_t)na_ * a.Wd + b) = v;
             }
         }
 

@@ -52,6 +52,12 @@ static inline int rac_launch_status(const char *what)
     return 0;
 }
 
+// output size along one axis of a ksize x ksize convolution with padding ksize / 2 (forward, data gradient and weight gradient agree on it)
+static inline int rac_conv_out_size(int in, int ksize, int stride)
+{
+    return (in + 2 * (ksize / 2) - ksize) / stride + 1;
+}
+
 // bf16 <-> f32 (bit-level; bf16 is the top half of an IEEE f32)
 __device__ __forceinline__ float rac_bf16_to_f32(unsigned short v)
 {

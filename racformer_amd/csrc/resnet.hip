@@ -9,7 +9,7 @@
 // weight image [Cout][K/32][hi 32 | lo 32] from rac_gemm_split_pack_fwd with K = (tap, ci), tap-major; the three leading products
 // lo*hi + hi*lo + hi*hi per K step in v_mfma_f32_16x16x32_f16, fp32 accumulate).  The activation scale 2^e is chosen PER IMAGE: a 3x3
 // sum reads a different pixel with every tap, so fpn_lateral.hip's per-pixel scale does not factor out of it; the image's maximum comes
-// from a pass of its own (rn_absmax_kernel: RN_PARTS partial maxima per image, combined by every workgroup of the convolution -- a maximum
+// from a pass of its own (rn_absmax_kernel: RAC_AMAX_PARTS partial maxima per image, combined by every workgroup of the convolution -- a maximum
 // has no order, nothing is atomic).  One scale rule for 1x1 and 3x3 keeps one kernel.
 //
 // Workgroup = 256 threads = 4 waves, tile = 64 consecutive output pixels of ONE image x 64 MI output channels (MI = 4, 2 or 1: the
@@ -22,6 +22,9 @@
 // with one barrier, with or without the weights one step ahead in registers, were measured slower (144 -> 172 registers
 // at MI = 4 takes the third wave from each SIMD).
 // Workgroups of one pixel tile are neighbours in the grid (channel block fastest), so the tile's input is shared through L2.
+// The same kernel source is the convolution's data gradient (template Rule, rac_resnet_conv_dgrad below): the roles of Cin and Cout
+// exchanged, the image of W^T with the taps flipped as the weights, g as the activations with one scale per image; the two rules differ
+// in which source pixel a tap reads and in the epilogue.  The rest of the backward is resnet_bwd.hip.
 //
 // rn_stem_kernel: exact fp32 (an fmaf chain over (ci, ky, kx) in ascending order per output).  K = 147 is no multiple of the MFMA's 32
 // and the layer is bound by its 554 MB of output at the f8 shapes, not by arithmetic.  A workgroup owns 16 x 16 convolution outputs of
@@ -29,12 +32,8 @@
 // (x[perm[c]] - mean[c]) / std[c] (IEEE division) applied while the patch is staged; padding stays zero.  rn_pool_kernel then takes the
 // maximum of the valid pixels of each 3x3 / stride 2 / pad 1 window.
 // No atomics, nothing read back, every sum in one fixed order, launch geometry from the shapes alone; 64-bit index arithmetic.
-#include "rac_common.h"
+#include "split_f16.h"
 
-typedef _Float16 rn_h8 __attribute__((ext_vector_type(8)));
-typedef float rn_f4 __attribute__((ext_vector_type(4)));
-
-#define RN_PARTS 64       // partial maxima per image (rac_resnet_absmax_fwd)
 #define RN_ROW 80         // bytes per LDS pixel row: 32 f16 + 16 bytes of padding (spreads the 16-byte reads over the banks)
 #define RN_STEM_C 64
 #define RN_STEM_TAPS 147
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(256) void rn_absmax_kernel(const float *__restrict_
 {
     __shared__ unsigned red[4];
     const int n = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
-    const long len = (per_image + RN_PARTS - 1) / RN_PARTS;
+    const long len = (per_image + RAC_AMAX_PARTS - 1) / RAC_AMAX_PARTS;
     const long b = (long)part * len, e = b + len < per_image ? b + len : per_image;
     const float *__restrict__ xn = x + (size_t)n * per_image;
     unsigned m = 0u;
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(256) void rn_absmax_kernel(const float *__restrict_
         red[tid >> 6] = m;
     __syncthreads();
     if (tid == 0)
-        parts[(size_t)n * RN_PARTS + part] = __uint_as_float(max(max(red[0], red[1]), max(red[2], red[3])));
+        parts[(size_t)n * RAC_AMAX_PARTS + part] = __uint_as_float(max(max(red[0], red[1]), max(red[2], red[3])));
 }
 
 extern "C" int rac_resnet_absmax_fwd(const float *x, float *parts, int N, int64_t per_image, void *stream)
@@ -66,23 +65,75 @@ extern "C" int rac_resnet_absmax_fwd(const float *x, float *parts, int N, int64_
     const char *what = "rac_resnet_absmax_fwd";
     RAC_CHECK_ARG(N >= 1 && N <= 65535 && per_image >= 1, "%s: N=%d per_image=%ld", what, N, (long)per_image);
     RAC_CHECK_ARG(x && parts, "%s: null pointer", what);
-    hipLaunchKernelGGL(rn_absmax_kernel, dim3(RN_PARTS, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x, parts, (long)per_image);
+    hipLaunchKernelGGL(rn_absmax_kernel, dim3(RAC_AMAX_PARTS, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x, parts, (long)per_image);
     return rac_launch_status(what);
 }
 
 // ------------------------------------------------------------------------------------------------ Bottleneck convolution
+// One kernel for the forward and the data gradient: source map -> destination map through a weight image with the destination's
+// channels as rows.  Forward: source = in (H x W, Cin), destination = out (Ho x Wo, Cout).  Data gradient: source = g (Ho x Wo, Cout),
+// destination = dx (H x W, Cin), the image that of W^T with the taps flipped.
 struct RnConvArgs {
-    const float *in;      // [N][Cin][H*W]
-    const char *w;        // [Cout][steps][hi 32 | lo 32] f16, step = tap * (Cin / 32) + chunk
-    const float *bias;    // [Cout] or null
-    const float *res;     // [N][Cout][Ho*Wo] or null
-    const float *parts;   // [N][RN_PARTS]
-    float *out;           // [N][Cout][Ho*Wo]
+    const float *src;     // [N][Cs][Hs*Ws]
+    const char *w;        // [Cd][steps][hi 32 | lo 32] f16, step = tap * (Cs / 32) + chunk
+    const float *e0;      // forward: bias [Cd];  data gradient: add [N][Cd][Hd*Wd];  or null
+    const float *e1;      // forward: residual [N][Cd][Hd*Wd];  data gradient: mask [N][Cd][Hd*Wd];  or null
+    const float *parts;   // [N][RAC_AMAX_PARTS] partial maxima of src
+    float *dst;           // [N][Cd][Hd*Wd]
     float w_alpha;
-    int relu, H, W, Ho, Wo, Cin, Cout, ksize, stride, pad, cblocks;
+    int relu, Hs, Ws, Hd, Wd, Cs, Cd, ksize, stride, pad, cblocks;
 };
 
-template <int MI>
+// What the two directions differ in.  tap: the source pixel (sh, sw) that tap (ky, kx) of destination pixel (dh, dw) reads, and
+// whether there is one for a thread whose pixel is `live`, i.e. inside the map (the kernel clamps the coordinates and stages a zero where
+// there is none).  The flag is formed before the coordinates are written out: the other way round hipcc merges two of its compares
+// behind a v_or_b32 in the K loop's staging code, 1.2 % on layer4 at 6 images.  store: the value stored for an
+// accumulator of channel c at element o of the destination.
+struct RnForward {
+    static constexpr bool dgrad = false;
+    static __device__ __forceinline__ bool tap(const RnConvArgs &a, bool live, int dh, int dw, int ky, int kx, int &sh, int &sw)
+    {
+        const int ih = dh * a.stride + ky - a.pad, iw = dw * a.stride + kx - a.pad;
+        const bool valid = live && ih >= 0 && ih < a.Hs && iw >= 0 && iw < a.Ws;
+        sh = ih, sw = iw;
+        return valid;
+    }
+    static __device__ __forceinline__ float store(const RnConvArgs &a, float acc, float unscale, int c, size_t o)
+    {
+        float v = __builtin_fmaf(acc, unscale, a.e0 ? a.e0[c] : 0.f);
+        if (a.e1)
+            v += a.e1[o];
+        if (a.relu)
+            v = v < 0.f ? 0.f : v;
+        return v;
+    }
+};
+// At stride 1 the forward itself.  At stride 2 pixel p reads tap t' at n = p + t' - pad only where both coordinates of n are even and
+// n / 2 lies inside g.  The epilogue adds `add` (the identity branch, an outside gradient) and applies the ReLU backward of the layer in
+// front (mask = the convolution's own post-ReLU input): a masked element is +0 exactly.
+struct RnDgrad {
+    static constexpr bool dgrad = true;
+    static __device__ __forceinline__ bool tap(const RnConvArgs &a, bool live, int dh, int dw, int ky, int kx, int &sh, int &sw)
+    {
+        const int sft = a.stride - 1;                    // stride 1 or 2: a shift and a parity mask
+        const int nh = dh + ky - a.pad, nw = dw + kx - a.pad;
+        const int qh = nh >> sft, qw = nw >> sft;
+        const bool valid = live && nh >= 0 && nw >= 0 && ((nh | nw) & sft) == 0 && qh < a.Hs && qw < a.Ws;
+        sh = qh, sw = qw;
+        return valid;
+    }
+    static __device__ __forceinline__ float store(const RnConvArgs &a, float acc, float unscale, int c, size_t o)
+    {
+        float v = acc * unscale;
+        if (a.e0)
+            v += a.e0[o];
+        if (a.e1)
+            v = a.e1[o] <= 0.f ? 0.f : v;
+        return v;
+    }
+};
+
+template <class Rule, int MI>
 __global__ __launch_bounds__(256) void rn_conv_kernel(const RnConvArgs a)
 {
     constexpr int HALF = 64 * RN_ROW;
@@ -90,41 +141,37 @@ __global__ __launch_bounds__(256) void rn_conv_kernel(const RnConvArgs a)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
     const int cb = blockIdx.x % a.cblocks;
     const long pt = blockIdx.x / a.cblocks;              // pixel tile over all images
-    const int HWo = a.Ho * a.Wo, tiles = (HWo + 63) / 64;
+    const int HWd = a.Hd * a.Wd, tiles = (HWd + 63) / 64;
     const int n = (int)(pt / tiles), q0 = (int)(pt - (long)n * tiles) * 64;
-    const int co0 = cb * 64 * MI + wave * 16 * MI;
-    const int chunks = a.Cin >> 5, steps = a.ksize * a.ksize * chunks;
-    const size_t HWi = (size_t)a.H * a.W;
+    const int c0 = cb * 64 * MI + wave * 16 * MI;
+    const int chunks = a.Cs >> 5, steps = a.ksize * a.ksize * chunks;
+    const size_t HWs = (size_t)a.Hs * a.Ws;
 
-    // the image's scale: every wave combines the RN_PARTS partial maxima (bit patterns: a NaN wins and turns the scale into 1)
-    unsigned mb = rac_absbits(a.parts[(size_t)n * RN_PARTS + lane]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        mb = max(mb, (unsigned)__shfl_xor((int)mb, off));
-    const float sc = rac_act_scale(__uint_as_float(mb));
+    // the image's scale, by every wave
+    const float sc = rac_act_scale(rac_wave_amax(a.parts + (size_t)n * RAC_AMAX_PARTS, lane));
     const float unscale = a.w_alpha / sc;                // both powers of two: exact
 
     // staging role: pixel sp of the tile, channels 8 sg .. 8 sg + 7 of the step's 32
     const int sp = tid & 63, sg = tid >> 6;
-    const bool live = q0 + sp < HWo;
-    const int qc = live ? q0 + sp : HWo - 1;
-    const int oh = qc / a.Wo, ow = qc - oh * a.Wo;
-    const float *__restrict__ xin = a.in + ((size_t)n * a.Cin + 8 * sg) * HWi;
+    const bool live = q0 + sp < HWd;
+    const int qc = live ? q0 + sp : HWd - 1;
+    const int dh = qc / a.Wd, dw = qc - dh * a.Wd;
+    const float *__restrict__ xin = a.src + ((size_t)n * a.Cs + 8 * sg) * HWs;
     float rx[8];
     bool rvalid = false;
     auto gload = [&](int s) {
         const int tap = s / chunks, c = s - tap * chunks;
         const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
-        const int ih = oh * a.stride + ky - a.pad, iw = ow * a.stride + kx - a.pad;
-        rvalid = live && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W;
-        const int ihc = min(max(ih, 0), a.H - 1), iwc = min(max(iw, 0), a.W - 1);
-        const float *p = xin + (size_t)c * 32 * HWi + (size_t)ihc * a.W + iwc;
+        int sh, sw;
+        rvalid = Rule::tap(a, live, dh, dw, ky, kx, sh, sw);
+        const int shc = min(max(sh, 0), a.Hs - 1), swc = min(max(sw, 0), a.Ws - 1);
+        const float *p = xin + (size_t)c * 32 * HWs + (size_t)shc * a.Ws + swc;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-            rx[e] = p[(size_t)e * HWi];
+            rx[e] = p[(size_t)e * HWs];
     };
     auto lstore = [&]() {
-        rn_h8 hi, lo;
+        rac_h8 hi, lo;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float v = rvalid ? rx[e] * sc : 0.f;
@@ -132,28 +179,28 @@ __global__ __launch_bounds__(256) void rn_conv_kernel(const RnConvArgs a)
             lo[e] = (_Float16)(v - (float)hi[e]);
         }
         char *d = rn_lds + sp * RN_ROW + 16 * sg;
-        *reinterpret_cast<rn_h8 *>(d) = hi;
-        *reinterpret_cast<rn_h8 *>(d + HALF) = lo;
+        *reinterpret_cast<rac_h8 *>(d) = hi;
+        *reinterpret_cast<rac_h8 *>(d + HALF) = lo;
     };
 
-    // A operand: tile i = output channels co0 + 16 i + li, K values 8 lk .. 8 lk + 7 of the step's line
-    const char *__restrict__ wrow = a.w + ((size_t)(co0 + li) * steps) * 128 + lk * 16;
+    // A operand: tile i = destination channels c0 + 16 i + li, K values 8 lk .. 8 lk + 7 of the step's line
+    const char *__restrict__ wrow = a.w + ((size_t)(c0 + li) * steps) * 128 + lk * 16;
     const size_t wtile = (size_t)16 * steps * 128;
 
-    rn_f4 acc[MI][4];
+    rac_f4v acc[MI][4];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            acc[i][j] = (rn_f4){0.f, 0.f, 0.f, 0.f};
+            acc[i][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 
     gload(0);
     for (int s = 0; s < steps; ++s) {
-        rn_h8 wh[MI], wl[MI];
+        rac_h8 wh[MI], wl[MI];
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
-            wh[i] = *reinterpret_cast<const rn_h8 *>(wrow + i * wtile + (size_t)s * 128);
-            wl[i] = *reinterpret_cast<const rn_h8 *>(wrow + i * wtile + (size_t)s * 128 + 64);
+            wh[i] = *reinterpret_cast<const rac_h8 *>(wrow + i * wtile + (size_t)s * 128);
+            wl[i] = *reinterpret_cast<const rac_h8 *>(wrow + i * wtile + (size_t)s * 128 + 64);
         }
         lstore();
         __syncthreads();
@@ -163,8 +210,8 @@ __global__ __launch_bounds__(256) void rn_conv_kernel(const RnConvArgs a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const char *b = S + (16 * j + li) * RN_ROW + 16 * lk;
-            const rn_h8 xh = *reinterpret_cast<const rn_h8 *>(b);
-            const rn_h8 xl = *reinterpret_cast<const rn_h8 *>(b + HALF);
+            const rac_h8 xh = *reinterpret_cast<const rac_h8 *>(b);
+            const rac_h8 xl = *reinterpret_cast<const rac_h8 *>(b + HALF);
 #pragma unroll
             for (int i = 0; i < MI; ++i)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], xh, acc[i][j], 0, 0, 0);
@@ -178,67 +225,91 @@ __global__ __launch_bounds__(256) void rn_conv_kernel(const RnConvArgs a)
         __syncthreads();
     }
 
-    // epilogue: accumulator tile (i, j) holds output channels co0 + 16 i + 4 lk + r (r = register) of pixel q0 + 16 j + li
+    // epilogue: accumulator tile (i, j) holds destination channels c0 + 16 i + 4 lk + r (r = register) of pixel q0 + 16 j + li
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int q = q0 + 16 * j + li;
-        if (q >= HWo)
+        if (q >= HWd)
             continue;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int co = co0 + 16 * i + 4 * lk + r;
-                const size_t o = ((size_t)n * a.Cout + co) * HWo + q;
-                float v = __builtin_fmaf(acc[i][j][r], unscale, a.bias ? a.bias[co] : 0.f);
-                if (a.res)
-                    v += a.res[o];
-                if (a.relu)
-                    v = v < 0.f ? 0.f : v;
-                a.out[o] = v;
+                const int c = c0 + 16 * i + 4 * lk + r;
+                const size_t o = ((size_t)n * a.Cd + c) * HWd + q;
+                a.dst[o] = Rule::store(a, acc[i][j][r], unscale, c, o);
             }
     }
+}
+
+// The checks, the tile-width rule and the launch of both directions.  The caller has set a's pointers, w_alpha, relu, ksize and stride;
+// H x W is the forward's input map, Ho x Wo its output (the forward derives it, the data gradient's is checked); `maps` names the
+// 4-byte aligned pointers in the message.
+template <class Rule>
+static int rn_conv_launch(const char *what, const char *maps, RnConvArgs a, int N, int Cin, int Cout, int H, int W, int Ho, int Wo,
+                          void *stream)
+{
+    constexpr bool DG = Rule::dgrad;
+    constexpr int cin_unit = DG ? 64 : 32, cout_unit = DG ? 32 : 64;      // the destination's tiles of 64, the source's K steps of 32
+    RAC_CHECK_ARG(a.ksize == 1 || a.ksize == 3, "%s: ksize=%d (1 or 3)", what, a.ksize);
+    RAC_CHECK_ARG(a.stride == 1 || a.stride == 2, "%s: stride=%d (1 or 2)", what, a.stride);
+    RAC_CHECK_ARG(Cin >= cin_unit && Cin % cin_unit == 0 && Cin <= 2048, "%s: Cin=%d (a multiple of %d, at most 2048)", what, Cin,
+                  cin_unit);
+    RAC_CHECK_ARG(Cout >= cout_unit && Cout % cout_unit == 0 && Cout <= 2048, "%s: Cout=%d (a multiple of %d, at most 2048)", what, Cout,
+                  cout_unit);
+    RAC_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && (long)H * W < (1l << 30), "%s: N=%d H=%d W=%d must be positive", what, N, H, W);
+    if (!DG)
+        Ho = rac_conv_out_size(H, a.ksize, a.stride), Wo = rac_conv_out_size(W, a.ksize, a.stride);
+    RAC_CHECK_ARG(Ho >= 1 && Wo >= 1 && Ho == rac_conv_out_size(H, a.ksize, a.stride) && Wo == rac_conv_out_size(W, a.ksize, a.stride),
+                  "%s: H=%d W=%d does not map to Ho=%d Wo=%d (ksize %d, stride %d)", what, H, W, Ho, Wo, a.ksize, a.stride);
+    RAC_CHECK_ARG(a.src && a.w && a.parts && a.dst, "%s: null pointer", what);
+    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(a.w) & 15) == 0, "%s: w_image must be 16-byte aligned", what);
+    RAC_CHECK_ARG(((reinterpret_cast<uintptr_t>(a.src) | reinterpret_cast<uintptr_t>(a.dst) | reinterpret_cast<uintptr_t>(a.e0) |
+                    reinterpret_cast<uintptr_t>(a.e1) | reinterpret_cast<uintptr_t>(a.parts)) & 3) == 0,
+                  "%s: %s must be 4-byte aligned", what, maps);
+    a.pad = a.ksize / 2;
+    a.Hs = DG ? Ho : H; a.Ws = DG ? Wo : W; a.Cs = DG ? Cout : Cin;
+    a.Hd = DG ? H : Ho; a.Wd = DG ? W : Wo; a.Cd = DG ? Cin : Cout;
+    // 256 destination channels per workgroup (the pixel tile is split once per 256 channels) where that still gives every CU a
+    // workgroup, then 128, then 64: a function of the shapes alone
+    const long ptiles = (long)N * ((a.Hd * a.Wd + 63) / 64);
+    int mi = 1;
+    for (int c = 4; c > 1; c >>= 1)
+        if (a.Cd % (64 * c) == 0 && ptiles * (a.Cd / (64 * c)) >= 256) {
+            mi = c;
+            break;
+        }
+    a.cblocks = a.Cd / (64 * mi);
+    const long wgs = ptiles * a.cblocks;
+    RAC_CHECK_ARG(wgs < (1l << 31), "%s: %ld workgroups", what, wgs);
+    const dim3 grid((unsigned)wgs);
+    hipStream_t st = (hipStream_t)stream;
+    if (mi == 4) hipLaunchKernelGGL((rn_conv_kernel<Rule, 4>), grid, dim3(256), 0, st, a);
+    else if (mi == 2) hipLaunchKernelGGL((rn_conv_kernel<Rule, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rn_conv_kernel<Rule, 1>), grid, dim3(256), 0, st, a);
+    return rac_launch_status(what);
 }
 
 extern "C" int rac_resnet_conv_fwd(const rac_resnet_conv *d, void *stream)
 {
     const char *what = "rac_resnet_conv_fwd";
     RAC_CHECK_ARG(d, "%s: null pointer (descriptor)", what);
-    RAC_CHECK_ARG(d->ksize == 1 || d->ksize == 3, "%s: ksize=%d (1 or 3)", what, d->ksize);
-    RAC_CHECK_ARG(d->stride == 1 || d->stride == 2, "%s: stride=%d (1 or 2)", what, d->stride);
-    RAC_CHECK_ARG(d->Cin >= 32 && d->Cin % 32 == 0 && d->Cin <= 2048, "%s: Cin=%d (a multiple of 32, at most 2048)", what, d->Cin);
-    RAC_CHECK_ARG(d->Cout >= 64 && d->Cout % 64 == 0 && d->Cout <= 2048, "%s: Cout=%d (a multiple of 64, at most 2048)", what, d->Cout);
-    RAC_CHECK_ARG(d->N >= 1 && d->H >= 1 && d->W >= 1 && (long)d->H * d->W < (1l << 30), "%s: N=%d H=%d W=%d must be positive", what,
-                  d->N, d->H, d->W);
-    RAC_CHECK_ARG(d->in && d->w_image && d->amax_parts && d->out, "%s: null pointer", what);
-    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(d->w_image) & 15) == 0, "%s: w_image must be 16-byte aligned", what);
-    RAC_CHECK_ARG(((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual) |
-                    reinterpret_cast<uintptr_t>(d->bias) | reinterpret_cast<uintptr_t>(d->amax_parts)) & 3) == 0,
-                  "%s: in / residual / bias / amax_parts / out must be 4-byte aligned", what);
     RnConvArgs a;
-    a.in = d->in; a.w = reinterpret_cast<const char *>(d->w_image); a.bias = d->bias; a.res = d->residual; a.parts = d->amax_parts;
-    a.out = d->out; a.w_alpha = d->w_alpha; a.relu = d->relu;
-    a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.ksize = d->ksize; a.stride = d->stride; a.pad = d->ksize / 2;
-    a.Ho = (d->H + 2 * a.pad - d->ksize) / d->stride + 1;
-    a.Wo = (d->W + 2 * a.pad - d->ksize) / d->stride + 1;
-    // 256 output channels per workgroup (the pixel tile is split once per 256 channels) where that still gives every CU a workgroup,
-    // then 128, then 64: a function of the shapes alone
-    const long ptiles = (long)d->N * ((a.Ho * a.Wo + 63) / 64);
-    int mi = 1;
-    for (int c = 4; c > 1; c >>= 1)
-        if (d->Cout % (64 * c) == 0 && ptiles * (d->Cout / (64 * c)) >= 256) {
-            mi = c;
-            break;
-        }
-    a.cblocks = d->Cout / (64 * mi);
-    const long wgs = ptiles * a.cblocks;
-    RAC_CHECK_ARG(wgs < (1l << 31), "%s: %ld workgroups", what, wgs);
-    const dim3 grid((unsigned)wgs);
-    hipStream_t st = (hipStream_t)stream;
-    if (mi == 4) hipLaunchKernelGGL(rn_conv_kernel<4>, grid, dim3(256), 0, st, a);
-    else if (mi == 2) hipLaunchKernelGGL(rn_conv_kernel<2>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(rn_conv_kernel<1>, grid, dim3(256), 0, st, a);
-    return rac_launch_status(what);
+    a.src = d->in; a.w = reinterpret_cast<const char *>(d->w_image); a.e0 = d->bias; a.e1 = d->residual; a.parts = d->amax_parts;
+    a.dst = d->out; a.w_alpha = d->w_alpha; a.relu = d->relu; a.ksize = d->ksize; a.stride = d->stride;
+    return rn_conv_launch<RnForward>(what, "in / residual / bias / amax_parts / out", a, d->N, d->Cin, d->Cout, d->H, d->W, 0, 0, stream);
+}
+
+// dx = the same kernel on the line image of W^T as [Cin][K], K = (flipped tap, co), with g as the activations.  The output size H x W
+// is an argument (7 and 8 both map to 4) and is checked against the forward's formula.
+extern "C" int rac_resnet_conv_dgrad(const rac_resnet_dgrad *d, void *stream)
+{
+    const char *what = "rac_resnet_conv_dgrad";
+    RAC_CHECK_ARG(d, "%s: null pointer (descriptor)", what);
+    RnConvArgs a;
+    a.src = d->g; a.w = reinterpret_cast<const char *>(d->w_image); a.e0 = d->add; a.e1 = d->mask; a.parts = d->amax_parts;
+    a.dst = d->out; a.w_alpha = d->w_alpha; a.relu = 0; a.ksize = d->ksize; a.stride = d->stride;
+    return rn_conv_launch<RnDgrad>(what, "g / add / mask / amax_parts / out", a, d->N, d->Cin, d->Cout, d->H, d->W, d->Ho, d->Wo, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ stem
@@ -293,7 +364,7 @@ __global__ __launch_bounds__(256) void rn_stem_kernel(const RnStemArgs a)
                 const float x = xr[kx];
 #pragma unroll
                 for (int c4 = 0; c4 < RN_STEM_C / 4; ++c4) {
-                    const rn_f4 w4 = *reinterpret_cast<const rn_f4 *>(wr + kx * RN_STEM_C + 4 * c4);
+                    const rac_f4v w4 = *reinterpret_cast<const rac_f4v *>(wr + kx * RN_STEM_C + 4 * c4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         acc[4 * c4 + r] = __builtin_fmaf(x, w4[r], acc[4 * c4 + r]);

@@ -25,7 +25,7 @@ rule, ``hip_route`` tells):
           statistics, so the forward under autograd is the folded-convolution forward above, bit for bit (``forward_hip_train``): the
           stem and every stage before the first one with a trainable parameter run on scratch as before, from that stage on each
           block's ``x, t1, t2, y`` are new tensors, saved for the backward (no scratch buffer is saved; ``with_cp`` is ignored: no
-          activation checkpointing on this route).  The backward (csrc/resnet_bwd.hip) walks the blocks last to first; per block, from
+          activation checkpointing on this route).  The backward (csrc/resnet_bwd.hip; the data gradient is csrc/resnet.hip's kernel) walks the blocks last to first; per block, from
           the masked gradient ``g3`` of its output: the weight gradient of ``conv3`` from ``(g3, t2)``, ``gt2 = dgrad(conv3; mask =
           t2)``, the weight gradient and the stride-aware data gradient of ``conv2`` (``gt1``, masked by ``t1``), the weight gradient of
           ``conv1``, the identity branch (``dgrad(downsample; add = the outside gradient of the stage map below)`` and the downsample's

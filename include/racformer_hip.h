@@ -77,6 +77,8 @@
  *                        input normalisation of models/racformer.py:202-212
  *   rac_resnet_conv_dgrad / rac_resnet_conv_wgrad / rac_resnet_relu_bwd <- autograd of the same Bottleneck stages (frozen_stages=1,
  *                        norm_eval=True: the stem and layer1 need no backward, the BatchNorms stay folded)
+ *   rac_pillar_train_fwd / rac_pillar_train_bwd / rac_bn_train_* <- extract_pts_feat on frame 0 in training mode under autograd
+ *                        (models/racformer.py:316-331): the PFN layer and radar_bev_conv on batch statistics, forward and backward
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -87,7 +89,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 31
+#define RAC_ABI_VERSION 32
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1044,6 +1046,66 @@ int rac_pillar_encode_fwd(const float *voxels, const int32_t *coors, const int32
                           int n_clouds,
                           int C, int max_num_points, int F, float vs_x, float vs_y, float vs_z, float center_x, float center_y,
                           float center_z, int H, int W, void *stream);
+
+/* ---- Training through the radar pillar branch (models/racformer.py:316-331: frame 0 runs extract_pts_feat in training mode under
+ * autograd; csrc/radar_pillars.hip, csrc/batchnorm_train.hip).  The BatchNorm1d of the PFN layer and the BatchNorm2d of the three
+ * radar_bev_conv layers use BATCH statistics and update their running statistics; the convolutions between them are
+ * rac_resnet_conv_fwd / _dgrad / _wgrad.  No float atomics, every sum float64 in one fixed order, launch geometry from the shapes
+ * alone, nothing read back (the number of pillars stays on the device): capturable, bitwise reproducible.  Every argument is checked
+ * before any launch.  Points get no gradient (the voxelization is no_grad in the reference too).
+ *
+ * rac_pillar_train_fwd: per real point row x = W f (the decoration and the fma chain of rac_pillar_encode_fwd, W the RAW Linear weight);
+ *   per channel mean and biased variance over all n = M * P rows of the call, M = rows with num_points > 0 and coors[0] >= 0, P =
+ *   max_num_points >= 2 -- the padded rows count, they are exactly 0 and add nothing to the sums;
+ *   y = relu((x - mean) * invstd * gamma + beta); feature = max over the P slots, a padded slot taking part with
+ *   relu((0 - mean) * invstd * gamma + beta); canvas[cloud, :, c_y, c_x] = feature, the rest of the canvas cleared first.
+ *     wt          f32 [C + 6][64], the Linear's weight transposed;  gamma, beta f32 [64]
+ *     running_mean, running_var f32 [64], num_batches_tracked int64 [1]: updated as nn.BatchNorm1d does in training mode (momentum;
+ *                 the unbiased n / (n - 1) variance; += 1), all three or none (NULL)
+ *     xbuf        f32 [n_rows][P][64]: x of the real rows (the rest is not written), for the backward
+ *     workspace   f64 [n_rows][2][64]
+ *     stat        f32 [128] = mean | invstd;  n_total int32 [1] = n
+ *     feats       f32 [n_rows][64], slots int32 [n_rows][64]: the winning value and its slot -- the FIRST maximum in slot order, -1 for a
+ *                 padded slot (it comes after the real ones); 0 / -1 in rows without a pillar.  torch may pick another of several tied
+ *                 slots: tied rows are identical inputs (duplicate radar returns), all padded, or both at the ReLU's zero, and in each
+ *                 case every parameter gradient is the same.
+ *     canvas      f32 [n_clouds][64][H][W], 16-byte aligned
+ *   Sums: a pillar's rows in slot order, the pillars of each of 16 contiguous row ranges (ceil(n_rows / 16) rows) ascending, the ranges
+ *   ascending.  No pillar at all: canvas 0, stat 0, n_total 0, the running statistics untouched.
+ * rac_pillar_train_bwd: from dcanvas [n_clouds][64][H][W]: gm = dcanvas at the pillar's cell where the saved feature > 0, routed to the
+ *   saved slot; dbeta = sum gm, dgamma = sum gm * xhat (xhat of a padded winner = (0 - mean) * invstd);
+ *   dx = gamma * invstd * (gm - dbeta / n - xhat * dgamma / n) on every real row; dw [64][C + 6] = sum over the real rows of dx f^T (padded
+ *   rows have f = 0; they still count in n).  dw may be NULL (only dgamma / dbeta).
+ *     workspace   f64 [n_rows][2][64] + [ceil(n_rows / 64)][C + 6][64]
+ *   Sums: dgamma / dbeta as the forward's; dw: 64 pillar rows per workgroup (a wave takes 16 in ascending order, the four waves added in
+ *   ascending order), the workgroups in ascending order.  n_total = 0: all three gradients are 0.
+ *
+ * Training-mode BatchNorm (+ ReLU) on channel-first f32 maps [N][C][HW]: C a multiple of 64 (at most 4096), any N, HW with N * HW >= 2.
+ * A channel's N * HW values in (image, pixel) order are cut into chunks of 4096; a workgroup sums a chunk (a thread's 16 values
+ * ascending, lanes by butterfly, the 4 waves ascending), a second launch adds the chunks in ascending order.  float64 sums of x and x^2
+ * (exact squares): var = sum x^2 / n - mean^2 keeps 10 digits at |mean| = 1e3 std.  workspace: f64 [C][ceil(N * HW / 4096)][2].
+ * rac_bn_train_stats_fwd: mean, invstd = 1 / sqrt(biased var + eps) f32 [C]; the same launch that finishes them updates running_mean
+ *   and running_var (momentum; unbiased n / (n - 1)) and num_batches_tracked (int64 [1], += 1) -- all three or none (NULL).
+ * rac_bn_train_apply_fwd: y = [relu]((x - mean) * invstd * gamma + beta), left to right in f32 (a NaN stays a NaN).
+ * rac_bn_train_bwd: from g = dL/dy and the saved x, y, mean, invstd: gm = g where y > 0 (y NULL: gm = g -- no ReLU, or the decision
+ *   was already applied, e.g. by rac_resnet_conv_dgrad's mask), xhat = (x - mean) * invstd;  dbeta = sum gm, dgamma = sum gm * xhat,
+ *   dx = gamma * invstd * (gm - dbeta / n - xhat * dgamma / n).  dx may be NULL (only dgamma / dbeta); it must not alias an input. */
+int rac_pillar_train_fwd(const float *voxels, const int32_t *coors, const int32_t *num_points, const float *wt, const float *gamma,
+                         const float *beta, float *running_mean, float *running_var, int64_t *num_batches_tracked, float *xbuf,
+                         double *workspace, float *stat, int32_t *n_total, float *feats, int32_t *slots, float *canvas, int n_rows,
+                         int n_clouds, int C, int max_num_points, int F, float eps, float momentum, float vs_x, float vs_y, float vs_z,
+                         float center_x, float center_y, float center_z, int H, int W, void *stream);
+int rac_pillar_train_bwd(const float *dcanvas, const float *voxels, const int32_t *coors, const int32_t *num_points, const float *gamma,
+                         const float *xbuf, const float *stat, const int32_t *n_total, const float *feats, const int32_t *slots,
+                         double *workspace, float *dw, float *dgamma, float *dbeta, int n_rows, int n_clouds, int C, int max_num_points,
+                         int F, float vs_x, float vs_y, float vs_z, float center_x, float center_y, float center_z, int H, int W,
+                         void *stream);
+int rac_bn_train_stats_fwd(const float *x, double *workspace, float *mean, float *invstd, float *running_mean, float *running_var,
+                           int64_t *num_batches_tracked, int N, int C, int HW, float eps, float momentum, void *stream);
+int rac_bn_train_apply_fwd(const float *x, const float *mean, const float *invstd, const float *gamma, const float *beta, float *y,
+                           int N, int C, int HW, int relu, void *stream);
+int rac_bn_train_bwd(const float *g, const float *x, const float *y, const float *mean, const float *invstd, const float *gamma,
+                     double *workspace, float *dgamma, float *dbeta, float *dx, int N, int C, int HW, void *stream);
 
 /* ---- DepthNet (models/necks/view_transformer_racformer.py:329-567, use_dcn=False), eval mode, BatchNorms folded by the caller:
  * a convolution for many small maps and the per-image vectors around it (csrc/depth_net.hip).  Activations between layers are

@@ -209,6 +209,69 @@ struct RpEncode {
     float vs[3], center0[3];
 };
 
+// The pillar decoration, shared by the inference kernel and the training kernels below.  Every operand is wave-uniform.
+// rp_pillar_centres: the mean of the pillar's points (the padded rows add zeros, as in the reference's sum over dim 1) and the cell's
+// centre, x / y / z from coors columns 3 / 2 / 1.
+__device__ __forceinline__ void rp_pillar_centres(const float *__restrict__ vox, int P, int C, int np, const int32_t *__restrict__ co,
+                                                  const float (&vs)[3], const float (&center0)[3], float (&mean)[3], float (&centre)[3])
+{
+#pragma clang fp contract(off)
+    float sum[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < P; ++s)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            sum[j] += vox[s * C + j];
+    const int cc[3] = {co[3], co[2], co[1]};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        mean[j] = __fdiv_rn(sum[j], (float)np);
+        centre[j] = (float)cc[j] * vs[j] + center0[j];
+    }
+}
+
+// one point row -> its decorated features: raw [C] (zero past C), then [xyz - mean | xyz - cell centre]
+__device__ __forceinline__ void rp_row_features(const float *__restrict__ v, int C, const float (&mean)[3], const float (&centre)[3],
+                                                float (&f)[RP_MAX_C], float (&fc)[6])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < RP_MAX_C; ++k)
+        f[k] = k < C ? v[k] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        fc[j] = f[j] - mean[j];
+        fc[3 + j] = f[j] - centre[j];
+    }
+}
+
+// W f of one point row for the lane's channel: an fma chain in ascending feature order
+__device__ __forceinline__ float rp_row_dot(const float *__restrict__ v, int C, const float (&w)[RP_MAX_C], const float (&wc)[6],
+                                            const float (&mean)[3], const float (&centre)[3])
+{
+    float f[RP_MAX_C], fc[6];
+    rp_row_features(v, C, mean, centre, f, fc);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < RP_MAX_C; ++k)
+        if (k < C)
+            acc = __builtin_fmaf(w[k], f[k], acc);
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        acc = __builtin_fmaf(wc[j], fc[j], acc);
+    return acc;
+}
+
+// the lane's column of the transposed Linear weight wt [C + 6][64]
+__device__ __forceinline__ void rp_load_weight(const float *__restrict__ wt, int C, int ch, float (&w)[RP_MAX_C], float (&wc)[6])
+{
+#pragma unroll
+    for (int k = 0; k < RP_MAX_C; ++k)
+        w[k] = k < C ? wt[k * RP_FEAT + ch] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        wc[j] = wt[(C + j) * RP_FEAT + ch];
+}
+
 // One wave per pillar row, a lane per output channel.  PillarFeatureNet (legacy=False, with_cluster_center, with_voxel_center):
 // features = [raw C | xyz - mean | xyz - cell centre]; y = relu(W' f + shift) with the BatchNorm folded into W' and shift; max over
 // the max_num_points rows, the padded rows taking part with relu(shift) (the reference multiplies their features by 0 and still
@@ -228,44 +291,14 @@ __global__ __launch_bounds__(256) void rp_encode_kernel(const RpEncode a)
     const bool on_map = cloud < a.n_clouds && cy >= 0 && cy < a.H && cx >= 0 && cx < a.W;   // (foreign coors never write outside)
     const int C = a.C;
     float w[RP_MAX_C], wc[6];
-#pragma unroll
-    for (int k = 0; k < RP_MAX_C; ++k)
-        w[k] = k < C ? a.wt[k * RP_FEAT + ch] : 0.f;
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-        wc[j] = a.wt[(C + j) * RP_FEAT + ch];
+    rp_load_weight(a.wt, C, ch, w, wc);
     const float shift = a.shift[ch];
     const float *vox = a.voxels + (size_t)r * a.P * C;
-    float sum[3] = {0.f, 0.f, 0.f};
-    for (int s = 0; s < a.P; ++s)             // (padded rows add zeros, as in the reference's sum over dim 1)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            sum[j] += vox[s * C + j];
     float mean[3], centre[3];
-    const int cc[3] = {cx, cy, co[1]};
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        mean[j] = __fdiv_rn(sum[j], (float)np);
-        centre[j] = (float)cc[j] * a.vs[j] + a.center0[j];
-    }
+    rp_pillar_centres(vox, a.P, C, np, co, a.vs, a.center0, mean, centre);
     float best = np < a.P ? fmaxf(shift, 0.f) : 0.f;       // (every candidate is >= 0: 0 is neutral for the max)
     for (int s = 0; s < min(np, a.P); ++s) {
-        const float *v = vox + s * C;
-        float f[RP_MAX_C];
-#pragma unroll
-        for (int k = 0; k < RP_MAX_C; ++k)
-            f[k] = k < C ? v[k] : 0.f;
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < RP_MAX_C; ++k)
-            if (k < C)
-                acc = __builtin_fmaf(w[k], f[k], acc);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            acc = __builtin_fmaf(wc[j], f[j] - mean[j], acc);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            acc = __builtin_fmaf(wc[3 + j], f[j] - centre[j], acc);
+        const float acc = rp_row_dot(vox + s * C, C, w, wc, mean, centre);
         best = fmaxf(best, fmaxf(acc + shift, 0.f));
     }
     if (a.feats)
@@ -365,4 +398,364 @@ extern "C" int rac_pillar_encode_fwd(const float *voxels, const int32_t *coors, 
         hipLaunchKernelGGL(rp_encode_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, st, a);
     }
     return rac_launch_status("rac_pillar_encode_fwd");
+}
+
+// ------------------------------------------------------------------------------------------------ the PFN layer in training mode
+// Linear (no bias) -> BatchNorm1d on BATCH statistics -> ReLU -> max over the P slots -> scatter, and its backward.  The statistics of
+// a channel run over all n = M * P rows of the call (M = the real pillar rows, counted on the device from num_points; never read
+// back); the padded rows are exactly 0 and add nothing to the sums, so only real rows are touched and n alone knows about the rest.
+// x = W f of every real row is kept in xbuf [n_rows][P][64] for the apply pass and the backward.
+// Sums: float64 (sum x, sum x^2 as in batchnorm_train.hip); a pillar's rows in slot order, the pillars of one of 16 contiguous row
+// ranges in ascending order, the 16 ranges in ascending order -- a function of n_rows alone.  No float atomics.
+// The winning slot of a (pillar, channel) is the FIRST maximum (a padded slot comes after the real ones and is saved as -1).  torch
+// may pick another of several tied slots; tied rows are identical inputs (duplicate radar returns), all padded, or both at the ReLU's
+// zero, and in each case every parameter gradient is the same.
+#define RP_SUM_GROUPS 16
+#define RP_DW_ROWS 64            // pillar rows per workgroup of the dW kernel: 4 waves x 16 rows
+
+struct RpTrain {
+    const float *voxels;
+    const int32_t *coors, *num_points;
+    const float *wt, *gamma, *beta;
+    float *running_mean, *running_var;
+    int64_t *tracked;
+    float *xbuf, *stat, *feats, *canvas;
+    double *part;
+    int32_t *n_total, *slots;
+    int n_rows, n_clouds, C, P, H, W;
+    float vs[3], center0[3];
+    float eps, momentum;
+};
+
+__device__ __forceinline__ bool rp_row_valid(const int32_t *__restrict__ coors, const int32_t *__restrict__ num_points, int r)
+{
+    return coors[4 * (size_t)r] >= 0 && num_points[r] > 0;
+}
+
+// x = W f of the real rows; part[r] = (sum x [64], sum x^2 [64]) of pillar r, zeros for a padding row
+__global__ __launch_bounds__(256) void rp_train_x_kernel(const RpTrain a)
+{
+    const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), ch = threadIdx.x & 63;
+    if (r >= a.n_rows)
+        return;
+    double s1 = 0.0, s2 = 0.0;
+    if (rp_row_valid(a.coors, a.num_points, r)) {
+        const int C = a.C, np = min(a.num_points[r], a.P);
+        float w[RP_MAX_C], wc[6], mean[3], centre[3];
+        rp_load_weight(a.wt, C, ch, w, wc);
+        const float *vox = a.voxels + (size_t)r * a.P * C;
+        rp_pillar_centres(vox, a.P, C, a.num_points[r], a.coors + 4 * (size_t)r, a.vs, a.center0, mean, centre);
+        for (int s = 0; s < np; ++s) {
+            const float x = rp_row_dot(vox + s * C, C, w, wc, mean, centre);
+            a.xbuf[((size_t)r * a.P + s) * RP_FEAT + ch] = x;
+            s1 += (double)x;
+            s2 += (double)x * (double)x;
+        }
+    }
+    a.part[((size_t)r * 2 + 0) * RP_FEAT + ch] = s1;
+    a.part[((size_t)r * 2 + 1) * RP_FEAT + ch] = s2;
+}
+
+// One workgroup: out[0 / 1][ch] = the two sums of part over all rows in the fixed order of the section comment, *m_out = the number
+// of real rows.  Every thread returns with the totals of its channel.
+__device__ __forceinline__ void rp_sum_rows(const double *__restrict__ part, const int32_t *__restrict__ coors,
+                                            const int32_t *__restrict__ num_points, int n_rows, double &s1, double &s2, int &m)
+{
+    __shared__ double sh[2][RP_SUM_GROUPS][RP_FEAT];
+    __shared__ int sh_m[RP_SUM_GROUPS];
+    const int grp = threadIdx.x >> 6, ch = threadIdx.x & 63;
+    const int per = (n_rows + RP_SUM_GROUPS - 1) / RP_SUM_GROUPS, r0 = grp * per, r1 = min(n_rows, r0 + per);
+    double a1 = 0.0, a2 = 0.0;
+    int cnt = 0;
+    for (int r = r0; r < r1; ++r) {
+        a1 += part[((size_t)r * 2 + 0) * RP_FEAT + ch];
+        a2 += part[((size_t)r * 2 + 1) * RP_FEAT + ch];
+        cnt += rp_row_valid(coors, num_points, r) ? 1 : 0;
+    }
+    sh[0][grp][ch] = a1;
+    sh[1][grp][ch] = a2;
+    if (ch == 0)
+        sh_m[grp] = cnt;
+    __syncthreads();
+    s1 = 0.0;
+    s2 = 0.0;
+    m = 0;
+#pragma unroll
+    for (int k = 0; k < RP_SUM_GROUPS; ++k) {
+        s1 += sh[0][k][ch];
+        s2 += sh[1][k][ch];
+        m += sh_m[k];
+    }
+}
+
+// stat = [mean 64 | invstd 64], *n_total = M * P; the BatchNorm1d running statistics as nn.BatchNorm1d updates them in training mode.
+// No pillar at all: stat = 0, n_total = 0, the running statistics stay as they are.
+__global__ __launch_bounds__(1024) void rp_train_stats_kernel(const RpTrain a)
+{
+    double s1, s2;
+    int m;
+    rp_sum_rows(a.part, a.coors, a.num_points, a.n_rows, s1, s2, m);
+    if (threadIdx.x >= RP_FEAT)
+        return;
+    const int ch = threadIdx.x;
+    if (ch == 0)
+        *a.n_total = m * a.P;
+    if (m == 0) {
+        a.stat[ch] = 0.f;
+        a.stat[RP_FEAT + ch] = 0.f;
+        return;
+    }
+    const double n = (double)m * (double)a.P, mu = s1 / n;
+    double var = s2 / n - mu * mu;
+    var = var > 0.0 ? var : (var == var ? 0.0 : var);
+    a.stat[ch] = (float)mu;
+    a.stat[RP_FEAT + ch] = (float)(1.0 / sqrt(var + (double)a.eps));
+    if (a.running_mean) {
+        const double mo = (double)a.momentum;
+        a.running_mean[ch] = (float)((1.0 - mo) * (double)a.running_mean[ch] + mo * mu);
+        a.running_var[ch] = (float)((1.0 - mo) * (double)a.running_var[ch] + mo * (var * (n / (n - 1.0))));
+        if (ch == 0)
+            *a.tracked += 1;
+    }
+}
+
+__device__ __forceinline__ float rp_bn_relu(float x, float m, float is, float g, float b)
+{
+#pragma clang fp contract(off)
+    return rac_relu(((x - m) * is) * g + b);
+}
+
+// BatchNorm + ReLU + max over the slots (first maximum), the winner and its slot saved, the canvas cell written
+__global__ __launch_bounds__(256) void rp_train_apply_kernel(const RpTrain a)
+{
+    const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), ch = threadIdx.x & 63;
+    if (r >= a.n_rows)
+        return;
+    float best = 0.f;
+    int slot = -1;
+    if (rp_row_valid(a.coors, a.num_points, r)) {
+        const int np = min(a.num_points[r], a.P);
+        const float m = a.stat[ch], is = a.stat[RP_FEAT + ch], g = a.gamma[ch], b = a.beta[ch];
+        const float *x = a.xbuf + (size_t)r * a.P * RP_FEAT + ch;
+        best = rp_bn_relu(x[0], m, is, g, b);
+        slot = 0;
+        for (int s = 1; s < np; ++s) {
+            const float y = rp_bn_relu(x[s * RP_FEAT], m, is, g, b);
+            if (y > best) {
+                best = y;
+                slot = s;
+            }
+        }
+        if (np < a.P) {
+            const float y = rp_bn_relu(0.f, m, is, g, b);
+            if (y > best) {
+                best = y;
+                slot = -1;
+            }
+        }
+        const int32_t *co = a.coors + 4 * (size_t)r;
+        const int cloud = co[0], cy = co[2], cx = co[3];
+        if (cloud < a.n_clouds && cy >= 0 && cy < a.H && cx >= 0 && cx < a.W)
+            a.canvas[(((size_t)cloud * RP_FEAT + ch) * a.H + cy) * a.W + cx] = best;
+    }
+    a.feats[(size_t)r * RP_FEAT + ch] = best;
+    a.slots[(size_t)r * RP_FEAT + ch] = slot;
+}
+
+struct RpTrainBwd {
+    const float *dcanvas, *voxels;
+    const int32_t *coors, *num_points;
+    const float *gamma, *xbuf, *stat, *feats;
+    const int32_t *n_total, *slots;
+    double *part, *dwpart;
+    float *dw, *dgamma, *dbeta;
+    int n_rows, n_clouds, C, P, H, W, n_blocks;
+    float vs[3], center0[3];
+};
+
+// the canvas gradient of (pillar r, channel ch) behind the ReLU: 0 for a padding row, a cell off the map or a winner at 0
+__device__ __forceinline__ float rp_gm(const RpTrainBwd &a, int r, int ch)
+{
+    if (!rp_row_valid(a.coors, a.num_points, r))
+        return 0.f;
+    const int32_t *co = a.coors + 4 * (size_t)r;
+    const int cloud = co[0], cy = co[2], cx = co[3];
+    if (!(cloud < a.n_clouds && cy >= 0 && cy < a.H && cx >= 0 && cx < a.W) || !(a.feats[(size_t)r * RP_FEAT + ch] > 0.f))
+        return 0.f;
+    return a.dcanvas[(((size_t)cloud * RP_FEAT + ch) * a.H + cy) * a.W + cx];
+}
+
+// part[r] = (gm [64], gm * xhat of the winning slot [64]) of pillar r
+__global__ __launch_bounds__(256) void rp_train_bwd_rows_kernel(const RpTrainBwd a)
+{
+#pragma clang fp contract(off)
+    const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), ch = threadIdx.x & 63;
+    if (r >= a.n_rows)
+        return;
+    const float gm = rp_gm(a, r, ch);
+    double p = 0.0;
+    if (gm != 0.f) {
+        const int slot = a.slots[(size_t)r * RP_FEAT + ch];
+        const float xw = slot >= 0 ? a.xbuf[((size_t)r * a.P + slot) * RP_FEAT + ch] : 0.f;
+        p = (double)gm * (double)((xw - a.stat[ch]) * a.stat[RP_FEAT + ch]);
+    }
+    a.part[((size_t)r * 2 + 0) * RP_FEAT + ch] = (double)gm;
+    a.part[((size_t)r * 2 + 1) * RP_FEAT + ch] = p;
+}
+
+__global__ __launch_bounds__(1024) void rp_train_bwd_finish_kernel(const RpTrainBwd a)
+{
+    double s1, s2;
+    int m;
+    rp_sum_rows(a.part, a.coors, a.num_points, a.n_rows, s1, s2, m);
+    if (threadIdx.x < RP_FEAT) {
+        a.dbeta[threadIdx.x] = (float)s1;
+        a.dgamma[threadIdx.x] = (float)s2;
+    }
+}
+
+// dwpart[block][k][ch] = sum over the block's pillar rows and their real slots of dx[row][ch] * f[row][k],
+// dx = gamma * invstd * (gm [winning slot] - dbeta / n - xhat * dgamma / n).  A wave takes 16 rows in ascending order, the four waves
+// are added in ascending order.
+__global__ __launch_bounds__(256) void rp_train_bwd_dw_kernel(const RpTrainBwd a)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[3][RP_MAX_C + 6][RP_FEAT];
+    const int wave = threadIdx.x >> 6, ch = threadIdx.x & 63, C = a.C;
+    const int n = *a.n_total;
+    const float inv_n = n > 0 ? (float)(1.0 / (double)n) : 0.f;
+    const float m = a.stat[ch], is = a.stat[RP_FEAT + ch], k = a.gamma[ch] * is, cb = a.dbeta[ch] * inv_n, cg = a.dgamma[ch] * inv_n;
+    double acc[RP_MAX_C], accc[6];
+#pragma unroll
+    for (int j = 0; j < RP_MAX_C; ++j)
+        acc[j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        accc[j] = 0.0;
+    for (int i = 0; i < RP_DW_ROWS / 4; ++i) {
+        const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * RP_DW_ROWS + wave * (RP_DW_ROWS / 4) + i);
+        if (r >= a.n_rows || !rp_row_valid(a.coors, a.num_points, r))
+            continue;
+        const int np = min(a.num_points[r], a.P);
+        const float gm = rp_gm(a, r, ch);
+        const int slot = a.slots[(size_t)r * RP_FEAT + ch];
+        const float *vox = a.voxels + (size_t)r * a.P * C;
+        float mean[3], centre[3];
+        rp_pillar_centres(vox, a.P, C, a.num_points[r], a.coors + 4 * (size_t)r, a.vs, a.center0, mean, centre);
+        for (int s = 0; s < np; ++s) {
+            float f[RP_MAX_C], fc[6];
+            rp_row_features(vox + s * C, C, mean, centre, f, fc);
+            const float xh = (a.xbuf[((size_t)r * a.P + s) * RP_FEAT + ch] - m) * is;
+            const float dx = k * (((s == slot ? gm : 0.f) - cb) - xh * cg);
+#pragma unroll
+            for (int j = 0; j < RP_MAX_C; ++j)
+                if (j < C)
+                    acc[j] += (double)dx * (double)f[j];
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                accc[j] += (double)dx * (double)fc[j];
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int j = 0; j < RP_MAX_C; ++j)
+            sh[wave - 1][j][ch] = acc[j];
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            sh[wave - 1][RP_MAX_C + j][ch] = accc[j];
+    }
+    __syncthreads();
+    if (wave > 0)
+        return;
+    double *out = a.dwpart + (size_t)blockIdx.x * (C + 6) * RP_FEAT;
+#pragma unroll
+    for (int j = 0; j < RP_MAX_C; ++j)
+        if (j < C)
+            out[j * RP_FEAT + ch] = ((acc[j] + sh[0][j][ch]) + sh[1][j][ch]) + sh[2][j][ch];
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        out[(C + j) * RP_FEAT + ch] = ((accc[j] + sh[0][RP_MAX_C + j][ch]) + sh[1][RP_MAX_C + j][ch]) + sh[2][RP_MAX_C + j][ch];
+}
+
+// dw [64][C + 6] = the blocks' partial sums in ascending order
+__global__ __launch_bounds__(64) void rp_train_bwd_dw_finish_kernel(const RpTrainBwd a)
+{
+    const int kf = blockIdx.x, ch = threadIdx.x, F = a.C + 6;
+    double s = 0.0;
+    for (int b = 0; b < a.n_blocks; ++b)
+        s += a.dwpart[((size_t)b * F + kf) * RP_FEAT + ch];
+    a.dw[ch * F + kf] = (float)s;
+}
+
+static int rp_train_check(const char *what, int n_rows, int n_clouds, int C, int P, int F, int H, int W)
+{
+    RAC_CHECK_ARG(n_rows >= 0 && n_clouds >= 1 && H > 0 && W > 0, "%s: n_rows=%d n_clouds=%d H=%d W=%d", what, n_rows, n_clouds, H, W);
+    RAC_CHECK_ARG(C >= 4 && C <= RP_MAX_C && P >= 2 && P <= 32, "%s: point width C=%d (4..%d), max_num_points=%d (2..32: one pillar has to "
+                  "give the batch statistics two rows)", what, C, RP_MAX_C, P);
+    RAC_CHECK_ARG(F == RP_FEAT, "%s: built for %d feature channels, got %d", what, RP_FEAT, F);
+    RAC_CHECK_ARG((int64_t)n_clouds * H * W < ((int64_t)1 << 31) / RP_FEAT && (int64_t)n_rows * P < ((int64_t)1 << 31) / RP_FEAT,
+                  "%s: %d maps of %d x %d / %d rows are too large", what, n_clouds, H, W, n_rows);
+    return 0;
+}
+
+extern "C" int rac_pillar_train_fwd(const float *voxels, const int32_t *coors, const int32_t *num_points, const float *wt,
+                                    const float *gamma, const float *beta, float *running_mean, float *running_var,
+                                    int64_t *num_batches_tracked, float *xbuf, double *workspace, float *stat, int32_t *n_total,
+                                    float *feats, int32_t *slots, float *canvas, int n_rows, int n_clouds, int C, int max_num_points,
+                                    int F, float eps, float momentum, float vs_x, float vs_y, float vs_z, float center_x, float center_y,
+                                    float center_z, int H, int W, void *stream)
+{
+    if (int rc = rp_train_check("rac_pillar_train_fwd", n_rows, n_clouds, C, max_num_points, F, H, W))
+        return rc;
+    RAC_CHECK_ARG(wt && gamma && beta && stat && n_total && canvas && workspace, "rac_pillar_train_fwd: null pointer");
+    RAC_CHECK_ARG(n_rows == 0 || (voxels && coors && num_points && xbuf && feats && slots), "rac_pillar_train_fwd: null pointer");
+    RAC_CHECK_ARG((running_mean && running_var && num_batches_tracked) || (!running_mean && !running_var && !num_batches_tracked),
+                  "rac_pillar_train_fwd: running_mean, running_var and num_batches_tracked are given together or not at all");
+    RAC_CHECK_ARG(eps >= 0.f && momentum >= 0.f && momentum <= 1.f, "rac_pillar_train_fwd: eps=%g momentum=%g", eps, momentum);
+    RAC_CHECK_ARG((reinterpret_cast<uintptr_t>(canvas) & 15) == 0, "rac_pillar_train_fwd: canvas must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    RpTrain a;
+    a.voxels = voxels; a.coors = coors; a.num_points = num_points; a.wt = wt; a.gamma = gamma; a.beta = beta;
+    a.running_mean = running_mean; a.running_var = running_var; a.tracked = num_batches_tracked;
+    a.xbuf = xbuf; a.stat = stat; a.feats = feats; a.canvas = canvas; a.part = workspace; a.n_total = n_total; a.slots = slots;
+    a.n_rows = n_rows; a.n_clouds = n_clouds; a.C = C; a.P = max_num_points; a.H = H; a.W = W;
+    a.vs[0] = vs_x; a.vs[1] = vs_y; a.vs[2] = vs_z; a.center0[0] = center_x; a.center0[1] = center_y; a.center0[2] = center_z;
+    a.eps = eps; a.momentum = momentum;
+    const long n4 = (long)n_clouds * RP_FEAT * H * W / 4;
+    hipLaunchKernelGGL(rp_fill_zero_kernel, dim3(rp_blocks(n4, 8192)), dim3(256), 0, st, reinterpret_cast<uint4 *>(canvas), n4);
+    if (n_rows > 0)
+        hipLaunchKernelGGL(rp_train_x_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rp_train_stats_kernel, dim3(1), dim3(1024), 0, st, a);
+    if (n_rows > 0)
+        hipLaunchKernelGGL(rp_train_apply_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, st, a);
+    return rac_launch_status("rac_pillar_train_fwd");
+}
+
+extern "C" int rac_pillar_train_bwd(const float *dcanvas, const float *voxels, const int32_t *coors, const int32_t *num_points,
+                                    const float *gamma, const float *xbuf, const float *stat, const int32_t *n_total, const float *feats,
+                                    const int32_t *slots, double *workspace, float *dw, float *dgamma, float *dbeta, int n_rows,
+                                    int n_clouds, int C, int max_num_points, int F, float vs_x, float vs_y, float vs_z, float center_x,
+                                    float center_y, float center_z, int H, int W, void *stream)
+{
+    if (int rc = rp_train_check("rac_pillar_train_bwd", n_rows, n_clouds, C, max_num_points, F, H, W))
+        return rc;
+    RAC_CHECK_ARG(dcanvas && gamma && stat && n_total && workspace && dgamma && dbeta, "rac_pillar_train_bwd: null pointer");
+    RAC_CHECK_ARG(n_rows == 0 || (voxels && coors && num_points && xbuf && feats && slots), "rac_pillar_train_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    RpTrainBwd a;
+    a.dcanvas = dcanvas; a.voxels = voxels; a.coors = coors; a.num_points = num_points; a.gamma = gamma; a.xbuf = xbuf; a.stat = stat;
+    a.feats = feats; a.n_total = n_total; a.slots = slots; a.part = workspace; a.dwpart = workspace + (size_t)n_rows * 2 * RP_FEAT;
+    a.dw = dw; a.dgamma = dgamma; a.dbeta = dbeta;
+    a.n_rows = n_rows; a.n_clouds = n_clouds; a.C = C; a.P = max_num_points; a.H = H; a.W = W;
+    a.n_blocks = (n_rows + RP_DW_ROWS - 1) / RP_DW_ROWS;
+    a.vs[0] = vs_x; a.vs[1] = vs_y; a.vs[2] = vs_z; a.center0[0] = center_x; a.center0[1] = center_y; a.center0[2] = center_z;
+    if (n_rows > 0)
+        hipLaunchKernelGGL(rp_train_bwd_rows_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rp_train_bwd_finish_kernel, dim3(1), dim3(1024), 0, st, a);
+    if (dw) {
+        if (n_rows > 0)
+            hipLaunchKernelGGL(rp_train_bwd_dw_kernel, dim3(a.n_blocks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(rp_train_bwd_dw_finish_kernel, dim3(C + 6), dim3(64), 0, st, a);
+    }
+    return rac_launch_status("rac_pillar_train_bwd");
 }

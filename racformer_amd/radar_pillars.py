@@ -1,10 +1,25 @@
 """The radar branch in front of the decoder: raw radar clouds ``[n, 7]`` to ``radar_bev_feats [B, T, 256, H, W]`` -- the
 reference's ``RaCFormer.extract_pts_feat`` (models/racformer.py:130-177: mmcv's hard ``Voxelization``, mmdet3d's
 ``PillarFeatureNet`` and ``PointPillarsScatter``, then the three ``ConvModule`` s of ``radar_bev_conv``, :81-99), stacked over the
-frames (:333-342).  Forward only, inference mode, on the HIP kernels of ``csrc/radar_pillars.hip`` (``rac_pillar_*``),
+frames (:333-342).  Inference runs on the HIP kernels of ``csrc/radar_pillars.hip`` (``rac_pillar_*``),
 ``csrc/conv_direct.hip`` (modes ``RAC_CD_IMAGE_RELU`` / ``RAC_CD_F32_CF_RELU``) and ``csrc/conv3x3.hip``
 (``rac_conv3x3_relu_cf_fwd``); nothing is read back and every launch is sized by an upper bound, so the branch can be captured
 into a graph; two runs give the same bits.
+
+Training (opt-in: ``RadarPillarEncoder.fused_grad = True`` and ``.train()``; off, training-mode BatchNorm raises as before): the
+reference runs ``extract_pts_feat`` on frame 0 in training mode under autograd (:316-331), frames 1 .. T-1 in eval mode under
+``no_grad`` on the statistics frame 0 has just updated.  ``extract_pts_feat`` then is one ``torch.autograd.Function``
+(``_RadarTrainCore``): voxelize (cap ``max_voxels[0]``), the PFN layer on BATCH statistics over all M * P rows of the call into an
+fp32 canvas (``rac_pillar_train_fwd``), and three times ``resnet.conv_fwd`` on the raw weight + batch-stat BatchNorm2d + ReLU
+(``rac_bn_train_*``, csrc/batchnorm_train.hip); the kernels update running_mean / running_var / num_batches_tracked on the device
+through raw pointers, so the caches keyed on ``_version`` (``_folded``, ``_packed``) are dropped explicitly.  The backward returns
+gradients for linear.weight, the PFN norm.weight / norm.bias and every layer's conv.weight / bn.weight / bn.bias, skipping launches
+nothing asks for; float64 sums in fixed orders, no float atomics: two runs give the same bits.  With the weight packs cached a
+forward + backward of ``extract_pts_feat`` reads nothing back (re-packing a changed weight reads its absmax, and frames 1 .. T-1 of
+``forward`` re-fold the eval route's weights on the new statistics, which reads their norms, as after any parameter change).
+No pillar at all: zero canvas, PFN statistics untouched, zero PFN gradients.  CPU tensors and ``fused=False`` take the torch
+modules in training mode under autograd (the comparator).  Not here: ``RaCFormer.forward_train`` (detector.py keeps its
+``TRAINING_MESSAGE``; this is what unblocks it), gradients to the points (voxelization is no_grad in the reference too).
 
 mmcv and mmdet3d are not importable here: the semantics below restate their documented behaviour (mmcv 1.6.0, mmdet3d 1.0.0rc6)
 under the f8 configuration.  Three quirks of the reference are KEPT:
@@ -23,7 +38,7 @@ Three cases the reference breaks on are DEFINED here:
 
 Tensors that are not on the GPU, and ``fused=False``, take a vectorised torch route (stable sort by cell for the voxelization,
 ``nn`` layers for the rest): the CPU path and the benchmark's baseline (tools/radar_pillars_bench.py).
-Out of scope: backward and training-mode BatchNorm (raise), dynamic voxelization.
+Out of scope: dynamic voxelization; training-mode BatchNorm without the ``fused_grad`` switch (raises).
 """
 from collections import namedtuple
 
@@ -45,9 +60,10 @@ def voxel_geom(voxel_size, point_cloud_range):
     return VoxelGeom(tuple(float(v) for v in r[:3]), tuple(float(v) for v in vs), tuple(int(v) for v in grid))
 
 
-def pack_clouds(clouds, zero_z=False):
+def pack_clouds(clouds, zero_z=False, pinned=False):
     """list of [n_i, C] float32 clouds -> (points [sum n_i, C] -- a new tensor, the inputs stay as they are --,
-    cloud_offsets int32 [len + 1] on the same device).  The offsets come from the shapes: an upload, not a read-back."""
+    cloud_offsets int32 [len + 1] on the same device).  The offsets come from the shapes: an upload, not a read-back;
+    ``pinned`` uploads them from pinned memory without the host waiting for the copy."""
     if len(clouds) == 0:
         raise ValueError("pack_clouds: no clouds")
     C = clouds[0].shape[1]
@@ -59,7 +75,10 @@ def pack_clouds(clouds, zero_z=False):
         points[:, 2] = 0
     off = np.zeros(len(clouds) + 1, dtype=np.int32)
     off[1:] = np.cumsum([c.shape[0] for c in clouds])
-    return points, torch.from_numpy(off).to(points.device)
+    off = torch.from_numpy(off)
+    if pinned and points.is_cuda:                           # (from pinned memory, in stream order: the host does not wait for it)
+        return points, off.pin_memory().to(points.device, non_blocking=True)
+    return points, off.to(points.device)
 
 
 # ------------------------------------------------------------------------------------------------ voxelization
@@ -186,6 +205,75 @@ def _param_sig(module):
     return tuple((t.data_ptr(), t._version, str(t.device)) for t in list(module.parameters()) + list(module.buffers()))
 
 
+# ------------------------------------------------------------------------------------------------ training-mode BatchNorm
+def _running_args(bn):
+    """(running_mean, running_var, num_batches_tracked pointers or three None, momentum) of a BatchNorm for the training kernels,
+    which update the buffers in place on the device (their ``_version`` does not move)."""
+    if bn.running_mean is None or not bn.track_running_stats:
+        return None, None, None, 0.0
+    if bn.momentum is None:
+        raise NotImplementedError("training-mode BatchNorm in HIP: momentum=None (cumulative average) is not implemented")
+    if bn.num_batches_tracked.dtype != torch.int64:
+        raise TypeError("training-mode BatchNorm in HIP: num_batches_tracked has to be int64")
+    _lib.require_gpu(bn.running_mean, bn.running_var, bn.num_batches_tracked, what="bn_train_stats")
+    return _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), _lib.ptr(bn.num_batches_tracked), float(bn.momentum)
+
+
+def _bn_maps(what, *tensors):
+    _lib.require_gpu(*tensors, what=what)
+    x = tensors[0]
+    if x.dim() < 3 or any(t.dtype != torch.float32 or t.shape != x.shape for t in tensors):
+        raise RuntimeError(f"{what}: contiguous float32 [N, C, ...] maps of one shape expected")
+    n, c = x.shape[:2]
+    return n, c, x.numel() // max(n * c, 1)
+
+
+def bn_chunks(n, hw):
+    """Partial sums per channel of the training-mode BatchNorm kernels for n maps of hw pixels (chunks of 4096 values)."""
+    return -(-n * hw // 4096)
+
+
+def bn_train_stats(x, bn=None, eps=1e-5):
+    """x float32 device [N, C, H, W] -> (mean [C], invstd [C]) over N * H * W (rac_bn_train_stats_fwd); with ``bn`` (an
+    ``nn.BatchNorm2d``: its eps and momentum) the running statistics are updated as its training-mode forward does."""
+    n, c, hw = _bn_maps("bn_train_stats", x)
+    running = _running_args(bn) if bn is not None else (None, None, None, 0.0)
+    mean, invstd = torch.empty(c, dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device)
+    work = torch.empty(c * bn_chunks(n, hw) * 2, dtype=torch.float64, device=x.device)
+    rc = _lib.lib().rac_bn_train_stats_fwd(_lib.ptr(x), _lib.ptr(work), _lib.ptr(mean), _lib.ptr(invstd), *running[:3], n, c, hw,
+                                           float(bn.eps if bn is not None else eps), running[3], _lib.stream_ptr())
+    _lib.check(rc, "rac_bn_train_stats_fwd")
+    return mean, invstd
+
+
+def bn_train_apply(x, mean, invstd, gamma, beta, relu=True):
+    """[relu]((x - mean) * invstd * gamma + beta) per channel (rac_bn_train_apply_fwd)."""
+    n, c, hw = _bn_maps("bn_train_apply", x)
+    gamma, beta = gamma.detach(), beta.detach()
+    _lib.require_gpu(mean, invstd, gamma, beta, what="bn_train_apply")
+    y = torch.empty_like(x)
+    rc = _lib.lib().rac_bn_train_apply_fwd(_lib.ptr(x), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y), n, c,
+                                           hw, int(bool(relu)), _lib.stream_ptr())
+    _lib.check(rc, "rac_bn_train_apply_fwd")
+    return y
+
+
+def bn_train_bwd(g, x, y, mean, invstd, gamma, need_dx=True):
+    """g = dL/dy, the BatchNorm's input x, its post-ReLU output y (None: no ReLU decision to apply -- there was none, or
+    ``conv_dgrad``'s mask already applied it) -> (dgamma [C], dbeta [C], dx or None) (rac_bn_train_bwd)."""
+    n, c, hw = _bn_maps("bn_train_bwd", g, x, *([y] if y is not None else []))
+    gamma = gamma.detach()
+    _lib.require_gpu(mean, invstd, gamma, what="bn_train_bwd")
+    dgamma, dbeta = torch.empty(c, dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if need_dx else None
+    work = torch.empty(c * bn_chunks(n, hw) * 2, dtype=torch.float64, device=x.device)
+    rc = _lib.lib().rac_bn_train_bwd(_lib.ptr(g), _lib.ptr(x), _lib.ptr(y) if y is not None else None, _lib.ptr(mean), _lib.ptr(invstd),
+                                     _lib.ptr(gamma), _lib.ptr(work), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dx) if need_dx else None,
+                                     n, c, hw, _lib.stream_ptr())
+    _lib.check(rc, "rac_bn_train_bwd")
+    return dgamma, dbeta, dx
+
+
 class PFNLayer(nn.Module):
     def __init__(self, in_channels, out_channels, eps=1e-3, momentum=0.01):
         super().__init__()
@@ -259,12 +347,66 @@ class PillarFeatureNet(nn.Module):
                                               _lib.stream_ptr())
         _lib.check(rc, "rac_pillar_encode_fwd")
 
+    def _geometry_args(self):
+        return (self.vx, self.vy, self.vz, float(np.float32(self.x_offset)), float(np.float32(self.y_offset)),
+                float(np.float32(self.z_offset)))
+
+    def train_fwd(self, pv, H, W):
+        """rac_pillar_train_fwd on packed pillar rows (``voxelize_packed``): the PFN layer on batch statistics, its BatchNorm1d's
+        running statistics updated on the device -> (canvas [n_clouds, 64, H, W], what ``train_bwd`` needs)."""
+        layer = self.pfn_layers[0]
+        lin, bn = layer.linear, layer.norm
+        n_rows, P, C = pv.voxels.shape
+        dev = pv.voxels.device
+        if C != self.in_channels or lin.weight.shape[0] != 64:
+            raise ValueError(f"PillarFeatureNet: {C}-wide points for in_channels={self.in_channels}; 64 feature channels expected")
+        wt = lin.weight.detach().t().contiguous()
+        gamma, beta = bn.weight.detach(), bn.bias.detach()
+        running = _running_args(bn)
+        _lib.require_gpu(pv.voxels, pv.coors, pv.num_points, wt, gamma, beta, what="PillarFeatureNet.train_fwd")
+        xbuf = torch.empty(n_rows, P, 64, dtype=torch.float32, device=dev)
+        work = torch.empty(max(n_rows, 1) * 2 * 64, dtype=torch.float64, device=dev)
+        stat = torch.empty(128, dtype=torch.float32, device=dev)
+        n_total = torch.empty(1, dtype=torch.int32, device=dev)
+        feats = torch.empty(n_rows, 64, dtype=torch.float32, device=dev)
+        slots = torch.empty(n_rows, 64, dtype=torch.int32, device=dev)
+        canvas = torch.empty(pv.n_clouds, 64, H, W, dtype=torch.float32, device=dev)
+        rc = _lib.lib().rac_pillar_train_fwd(_lib.ptr(pv.voxels), _lib.ptr(pv.coors), _lib.ptr(pv.num_points), _lib.ptr(wt), _lib.ptr(gamma),
+                                             _lib.ptr(beta), *running[:3], _lib.ptr(xbuf), _lib.ptr(work), _lib.ptr(stat), _lib.ptr(n_total),
+                                             _lib.ptr(feats), _lib.ptr(slots), _lib.ptr(canvas), n_rows, int(pv.n_clouds), C, P, 64,
+                                             float(bn.eps), running[3], *self._geometry_args(), int(H), int(W), _lib.stream_ptr())
+        _lib.check(rc, "rac_pillar_train_fwd")
+        self._folded = None                              # (the running statistics changed behind their version counters)
+        return canvas, (pv.voxels, pv.coors, pv.num_points, xbuf, stat, n_total, feats, slots)
+
+    def train_bwd(self, saved, dcanvas, need_dw=True):
+        """rac_pillar_train_bwd: ``train_fwd``'s saved tensors and dL/dcanvas -> (dW [64, C + 6] or None, dgamma [64], dbeta [64])."""
+        voxels, coors, num, xbuf, stat, n_total, feats, slots = saved
+        n_rows, P, C = voxels.shape
+        dev = voxels.device
+        n_clouds, _, H, W = dcanvas.shape
+        gamma = self.pfn_layers[0].norm.weight.detach()
+        _lib.require_gpu(dcanvas, gamma, what="PillarFeatureNet.train_bwd")
+        work = torch.empty(max(n_rows, 1) * 2 * 64 + (-(-n_rows // 64)) * (C + 6) * 64, dtype=torch.float64, device=dev)
+        dw = torch.empty(64, C + 6, dtype=torch.float32, device=dev) if need_dw else None
+        dgamma, dbeta = torch.empty(64, dtype=torch.float32, device=dev), torch.empty(64, dtype=torch.float32, device=dev)
+        rc = _lib.lib().rac_pillar_train_bwd(_lib.ptr(dcanvas), _lib.ptr(voxels), _lib.ptr(coors), _lib.ptr(num), _lib.ptr(gamma),
+                                             _lib.ptr(xbuf), _lib.ptr(stat), _lib.ptr(n_total), _lib.ptr(feats), _lib.ptr(slots),
+                                             _lib.ptr(work), _lib.ptr(dw) if need_dw else None, _lib.ptr(dgamma), _lib.ptr(dbeta), n_rows,
+                                             int(n_clouds), C, P, 64, *self._geometry_args(), int(H), int(W), _lib.stream_ptr())
+        _lib.check(rc, "rac_pillar_train_bwd")
+        return dw, dgamma, dbeta
+
     def forward(self, features, num_points, coors):
         if self.fused and features.is_cuda:
             feats = torch.zeros(features.shape[0], 64, dtype=torch.float32, device=features.device)
             self.encode(features.contiguous(), coors.int().contiguous(), num_points.int().contiguous(), 1, 1, 1, feats=feats)
             return feats
         _no_training(self, "PillarFeatureNet")
+        return self.forward_torch(features, num_points, coors)
+
+    def forward_torch(self, features, num_points, coors):
+        """The same in torch ops, in the BatchNorm's own mode (running or batch statistics), under autograd if it is on."""
         dtype = features.dtype
         points_mean = features[:, :, :3].sum(dim=1, keepdim=True) / num_points.type_as(features).view(-1, 1, 1)
         f_cluster = features[:, :, :3] - points_mean
@@ -363,8 +505,11 @@ class RadarPillarEncoder(nn.Module):
     ``radar_voxel_encoder.*`` and ``radar_bev_conv.{0,1,2}.{conv.weight, bn.*}`` keys load as they are.  Arguments are the
     reference config's ``radar_voxel_layer`` / ``radar_voxel_encoder`` / ``radar_middle_encoder`` dicts (``type`` keys ignored)."""
 
+    fused_grad = False        # opt-in: in training mode extract_pts_feat runs on batch statistics under autograd (module docstring)
+
     def __init__(self, radar_voxel_layer=None, radar_voxel_encoder=None, radar_middle_encoder=None, embed_dims=256, fused=True):
         super().__init__()
+        self._train_packed = {}
         vl = dict(radar_voxel_layer or F8_VOXEL_LAYER)
         ve = dict(radar_voxel_encoder or dict(in_channels=7, feat_channels=[64], with_distance=False, voxel_size=vl["voxel_size"],
                                               point_cloud_range=vl["point_cloud_range"], legacy=False,
@@ -431,15 +576,21 @@ class RadarPillarEncoder(nn.Module):
         coors = [torch.nn.functional.pad(r[1], (1, 0), value=i) for i, r in enumerate(res)]
         return torch.cat([r[0] for r in res]), torch.cat([r[2] for r in res]), torch.cat(coors)
 
-    def _torch_route(self, clouds):
-        _no_training(self, "RadarPillarEncoder")
+    def _torch_route(self, clouds, train=False):
+        if not train:
+            _no_training(self, "RadarPillarEncoder")
         zeroed = []
         for p in clouds:
             p = p.detach().clone()
             p[:, 2] = 0
             zeroed.append(p)
-        voxels, num, coors = self.radar_voxelize(zeroed)
-        feats = self.radar_voxel_encoder(voxels, num, coors) if voxels.shape[0] else voxels.new_zeros(0, 64)
+        with torch.no_grad():                                  # (as in the reference: radar_voxelize is no_grad)
+            voxels, num, coors = self.radar_voxelize(zeroed)
+        pfn = self.radar_voxel_encoder
+        if voxels.shape[0] == 0:                               # (no pillar: no batch to take statistics of)
+            feats = voxels.new_zeros(0, 64)
+        else:
+            feats = pfn.forward_torch(voxels, num, coors) if train else pfn(voxels, num, coors)
         return self.radar_bev_conv(self.radar_middle_encoder(feats, coors, len(clouds)))
 
     def _clouds(self, clouds):
@@ -449,15 +600,133 @@ class RadarPillarEncoder(nn.Module):
                 return self.encode_packed(*pack_clouds(list(clouds), zero_z=True))
             return self._torch_route(clouds)
 
+    # -------------------------------------------------------------------------------------------- the training route
+    def train_route(self):
+        """True where ``extract_pts_feat`` trains: the switch is on and the module is in training mode."""
+        return bool(self.fused_grad) and self.training
+
+    def train_packs(self, i, transposed=False):
+        """``resnet.pack_conv_weight`` (``_t``) of radar_bev_conv[i]'s RAW weight, cached per weight version (an optimizer step
+        moves it); packing reads the weight's absmax on the host."""
+        from . import resnet
+        w = self.radar_bev_conv[i].conv.weight
+        key = (i, bool(transposed))
+        sig = (w.data_ptr(), w._version, str(w.device))
+        hit = self._train_packed.get(key)
+        if hit is None or hit[0] != sig:
+            hit = self._train_packed[key] = (sig, (resnet.pack_conv_weight_t if transposed else resnet.pack_conv_weight)(w))
+        return hit[1]
+
+    def train_params(self):
+        """The parameters ``_RadarTrainCore`` returns gradients for, in its order."""
+        layer = self.radar_voxel_encoder.pfn_layers[0]
+        out = [layer.linear.weight, layer.norm.weight, layer.norm.bias]
+        for m in self.radar_bev_conv:
+            out += [m.conv.weight, m.bn.weight, m.bn.bias]
+        return out
+
+    def train_forward_hip(self, points, cloud_offsets):
+        """Packed clouds -> ([n_clouds, 256, H, W], the PFN layer's saved tensors, per layer (input, conv output, output, mean,
+        invstd)): voxelize, the PFN layer and the three ConvModules on batch statistics; every BatchNorm's running statistics are
+        updated on the device.  No read-back, no data-dependent allocation."""
+        from . import resnet
+        vl, pfn = self.radar_voxel_layer, self.radar_voxel_encoder
+        gx, gy, _ = vl.geom.grid
+        pv = voxelize_packed(points, cloud_offsets, vl.geom, vl.max_num_points, vl.cap())
+        x, pfn_saved = pfn.train_fwd(pv, gy, gx)
+        layers = []
+        for i, m in enumerate(self.radar_bev_conv):
+            z = resnet.conv_fwd(x, self.train_packs(i), None, 3, 1, relu=False)
+            mean, invstd = bn_train_stats(z, m.bn)
+            y = bn_train_apply(z, mean, invstd, m.bn.weight, m.bn.bias)
+            layers.append((x, z, y, mean, invstd))
+            x = y
+        self._packed = None                                    # (the running statistics changed behind their version counters)
+        return x, pfn_saved, layers
+
+    def _clouds_train(self, clouds):
+        """``_clouds`` in training mode under autograd: the HIP route on device clouds, else the torch modules."""
+        if self.fused and all(p.is_cuda for p in clouds):
+            points, off = pack_clouds(list(clouds), zero_z=True, pinned=True)
+            return _RadarTrainCore.apply(self, points, off, *self.train_params())
+        return self._torch_route(clouds, train=True)
+
     def extract_pts_feat(self, radar_points):
-        """list over B of [n, 7] -> [B, 256, H, W]: the reference's method for one frame."""
+        """list over B of [n, 7] -> [B, 256, H, W]: the reference's method for one frame.  With ``fused_grad`` on and the module
+        in training mode it runs on batch statistics under autograd (``_RadarTrainCore`` on device clouds)."""
+        if self.train_route():
+            return self._clouds_train(radar_points)
         return self._clouds(radar_points)
+
+    def _eval_frames(self, clouds):
+        """``_clouds`` with every submodule switched to eval mode for the call (the reference's frames 1 .. T-1)."""
+        was = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            return self._clouds(clouds)
+        finally:
+            for m, t in was:
+                m.training = t
 
     def forward(self, radar_points):
         """list over T of list over B of [n, 7] -> radar_bev_feats [B, T, 256, H, W], contiguous fp32 (the decoder's input); all
-        B * T clouds go through one set of launches."""
+        B * T clouds go through one set of launches.  On the training route (``train_route``) frame 0 trains and frames 1 .. T-1
+        run in eval mode under no_grad on the running statistics frame 0 has just updated, as in models/racformer.py:316-342."""
         T, B = len(radar_points), len(radar_points[0])
         if any(len(frame) != B for frame in radar_points):
             raise ValueError("RadarPillarEncoder: every frame needs one cloud per sample")
+        if self.train_route():
+            first = self._clouds_train(list(radar_points[0])).unsqueeze(1)
+            if T == 1:
+                return first
+            rest = self._eval_frames([radar_points[t][b] for b in range(B) for t in range(1, T)])
+            return torch.cat([first, rest.view(B, T - 1, *rest.shape[1:])], dim=1)
         out = self._clouds([radar_points[t][b] for b in range(B) for t in range(T)])
         return out.view(B, T, *out.shape[1:])
+
+
+class _RadarTrainCore(torch.autograd.Function):
+    """The branch's HIP training forward under autograd: apply(encoder, points, cloud_offsets, *encoder.train_params()) ->
+    [n_clouds, 256, H, W].  The parameters are passed for autograd's bookkeeping and read from the modules.  The backward walks the
+    stages last to first -- per ConvModule rac_bn_train_bwd, ``resnet.conv_wgrad``, ``resnet.conv_dgrad`` (its mask applies the ReLU
+    of the layer in front, whose BatchNorm backward then takes the gradient as it is), then rac_pillar_train_bwd -- and runs a launch
+    only where ``ctx.needs_input_grad`` asks for its result or for something in front of it.  Nothing is read back but the weight
+    maxima of a pack whose weight changed.  The points get no gradient."""
+
+    @staticmethod
+    def forward(ctx, enc, points, cloud_offsets, *params):
+        out, pfn_saved, layers = enc.train_forward_hip(points, cloud_offsets)
+        ctx.enc = enc
+        ctx.save_for_backward(*pfn_saved, *[t for layer in layers for t in layer])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        from . import resnet
+        enc = ctx.enc
+        pfn_saved, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        layers = [rest[5 * i:5 * i + 5] for i in range(3)]
+        flags = ctx.needs_input_grad[3:]
+        grads = [None] * len(flags)
+        wanted = [k for k in range(4) if any(flags[3 * k:3 * k + 3])]          # stage 0: the PFN layer; stage i + 1: ConvModule i
+        if not wanted:
+            return (None, None, None, *grads)
+        first = wanted[0]
+        g = gout.contiguous()
+        for i in (2, 1, 0):
+            x, z, y, mean, invstd = layers[i]
+            nw, ng, nb = flags[3 * i + 3:3 * i + 6]
+            front = first < i + 1
+            bn = enc.radar_bev_conv[i].bn
+            dgamma, dbeta, gz = bn_train_bwd(g, z, y if i == 2 else None, mean, invstd, bn.weight, need_dx=bool(nw or front))
+            if nw:
+                grads[3 * i + 3] = resnet.conv_wgrad(gz, x, 3, 1, bias=False)[0]
+            grads[3 * i + 4], grads[3 * i + 5] = dgamma if ng else None, dbeta if nb else None
+            if not front:
+                return (None, None, None, *grads)
+            # (the canvas needs no mask: the PFN backward takes its own ReLU decision from the saved features)
+            g = resnet.conv_dgrad(gz, enc.train_packs(i, transposed=True), 3, 1, x.shape[2:], mask=x if i > 0 else None)
+        dw, dgamma, dbeta = enc.radar_voxel_encoder.train_bwd(pfn_saved, g, need_dw=bool(flags[0]))
+        grads[0], grads[1], grads[2] = dw, dgamma if flags[1] else None, dbeta if flags[2] else None
+        return (None, None, None, *grads)

@@ -733,10 +733,15 @@ int rac_bev_pool_v2_bwd(const float *out_grad, float *depth_grad, float *feat_gr
  *
  * rac_conv_direct_fwd: a 3x3 convolution (stride 1 or 2, pad 1) for the SMALL maps of that branch (64 x 64 x 64 channels, one
  * frame at a time through the recurrence), with the split-precision arithmetic of rac_conv3x3_fwd (three f16 MFMA products of
- * hi / lo operands, fp32 accumulate: fp32-convolution accuracy).  Unlike rac_conv3x3_fwd nothing is staged through LDS and no
- * workgroup barrier is executed: a wave owns 16 output pixels x (16 * tiles) output channels and loads its MFMA fragments
- * straight from the activation image / weight image (both L2-resident at these sizes) through a register ring several K steps
- * ahead -- these launches are latency-bound chains, not throughput kernels.
+ * hi / lo operands, fp32 accumulate: fp32-convolution accuracy).  The WEIGHTS of a workgroup's output-channel block pass through
+ * an LDS double buffer, one 32-channel chunk (9 taps) per buffer (108 KB for 48-channel blocks, 144 KB for 64-channel ones), with
+ * one workgroup barrier per chunk; the PIXELS never do: every lane loads its MFMA fragments straight from the activation image
+ * (L2-resident at these sizes) through a register ring three K steps ahead -- these launches are latency-bound chains, not
+ * throughput kernels.  The chunk count is a template parameter (the K loop is straight-line code); instantiated are
+ *   stride 2, RAC_CD_IMAGE: chunks 2 | 3 | 8;   stride 1, RAC_CD_IMAGE and RAC_CD_IMAGE_RELU: chunks 2;
+ *   RAC_CD_F32: chunks 1 | 2 | 4;   RAC_CD_F32_CF_RELU: chunks 2;   RAC_CD_GRU: chunks 0 | 2
+ * and any other count is an argument error.  bias, pixel_map, out_f32, xpart, h_prev and h_out must be 16-byte aligned.
+ * A frame map carries no frame count: that every frame(n), n < N, lies inside its buffer is the caller's responsibility.
  *
  *   in_img   f16 [frames][H+2][W+2][in_chunks_total][hi 32 | lo 32]  zero border; K runs over chunks in_chunk0 .. +chunks-1
  *            (chunks == 0: no convolution, the accumulators stay zero -- the recurrence's first step, h_0 = 0)

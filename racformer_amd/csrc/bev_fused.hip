@@ -60,19 +60,15 @@ __device__ __forceinline__ void bev_keypoint(const BevArgs &a, const BevStream &
                             a.d_region, a.D, loc2);
 }
 
-#ifndef BEV_U
 #define BEV_U 4    /* keypoints per gather batch (4 taps each in flight) */
-#endif
-#ifndef BEV_OCC
 #define BEV_OCC 4  /* workgroups per CU the register budget is cut for */
-#endif
 #define BEV_GI 4   /* items (b,q,head) per workgroup */
 #define BEV_TS 4   /* point subsets per item: 16-lane group (k, ts) handles points ts, ts+4, ... of every frame */
 #define BEV_TAP_OUTSIDE 0x80000000u   /* tap offset past the end of the value buffer: the buffer load returns zeros */
 
 // Diagnostic build only (tools/bev_phase_split.py; -DBEV_STAMPS): s_memtime at the phase boundaries of every workgroup (wave 0),
 // kept in a device array of the code object and read back through rac_dbg_bev_stamps.  Not part of the product library or its ABI.
-#ifdef BEV_STAMPS
+#if defined(RAC_DIAGNOSTIC_BUILD) && defined(BEV_STAMPS)
 #define BEV_STAMP_WGS 4096
 __device__ unsigned long long bev_stamp_buf[BEV_STAMP_WGS * 8];
 #define BEV_STAMP(i)                                                                                    \
@@ -391,7 +387,7 @@ __global__ __launch_bounds__(256, BEV_OCC) void bev_sampling_d64_kernel(const Be
         }
     }
     BEV_STAMP(4);
-#ifdef BEV_STAMPS
+#if defined(RAC_DIAGNOSTIC_BUILD) && defined(BEV_STAMPS)
     if (threadIdx.x == 0 && blockIdx.y * gridDim.x + blockIdx.x < BEV_STAMP_WGS) {
         // where the workgroup ran: HW_ID (gfx9: wave 3:0, simd 5:4, cu 11:8, sh 12, se 15:13) and the XCC id register
         unsigned hw, xcc;
@@ -402,7 +398,7 @@ __global__ __launch_bounds__(256, BEV_OCC) void bev_sampling_d64_kernel(const Be
 #endif
 }
 
-#ifdef BEV_STAMPS
+#if defined(RAC_DIAGNOSTIC_BUILD) && defined(BEV_STAMPS)
 extern "C" int rac_dbg_bev_stamps(unsigned long long *host_out, int n_wgs)
 {
     if (n_wgs > BEV_STAMP_WGS)

@@ -22,21 +22,9 @@
 #include "rac_common.h"
 #include <string.h>
 
-typedef _Float16 cv_h8 __attribute__((ext_vector_type(8)));
-typedef float cv_f4 __attribute__((ext_vector_type(4)));
-
-#ifndef CV_TAP_MAJOR
-#define CV_TAP_MAJOR 0
-#endif
-#ifndef CV_SPREAD_STAGING
-#define CV_SPREAD_STAGING 1   /* 0: all staging traffic at the top of the step (rounds 2-3; A/B builds) */
-#endif
 #define CV_TM 256
 #define CV_COUT 256
 #define CV_STAGE_U4 4096 /* uint4 per LDS stage: A 2048 + B 2048 */
-
-// power of two that brings amax into [2^13, 2^14): rac_act_scale (rac_common.h; shared with conv_direct.hip)
-#define cv_act_scale rac_act_scale
 
 // ------------------------------------------------------------------------------------------------ absmax
 // (a one-thread launch rather than a memset: inside a captured HIP graph the step then consists of kernel nodes only, whose
@@ -101,7 +89,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float *__restrict_
     const int h = (blockIdx.x / (wpieces * cchunks)) % H;
     const int n = blockIdx.x / (wpieces * cchunks * H);
     const int tid = threadIdx.x;
-    const float scale = cv_act_scale(*amax);
+    const float scale = rac_act_scale(*amax);
     const int w0 = wp << 7, wlen = min(128, W - w0);
     const int grp = n / T, t = n - grp * T;
     const bool live = t < Tv;
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float *__restrict_
     __syncthreads();
     for (int i = tid; i < wlen * 8; i += 256) {
         const int w = i >> 3, s = i & 7, c0 = (s & 3) * 8;
-        cv_h8 o;
+        rac_h8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float v = tile[c0 + j][w] * scale;
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float *__restrict_
             o[j] = s < 4 ? hi : (_Float16)(v - (float)hi);
         }
         const size_t pix = ((size_t)n * (H + 2) + h + 1) * (W + 2) + w0 + w + 1;
-        *reinterpret_cast<cv_h8 *>(dst + (pix * chunks_total + chunk0 + c32) * 64 + s * 8) = o;
+        *reinterpret_cast<rac_h8 *>(dst + (pix * chunks_total + chunk0 + c32) * 64 + s * 8) = o;
     }
 }
 
@@ -169,9 +157,9 @@ struct ConvArgs {
     float scale_mul, scale_add;   // CV_OUT_NCHW_RELU only: the image's bound is scale_mul * (*amax) + scale_add (amax may be NULL)
 };
 enum { CV_OUT_NHWC = 0, CV_OUT_GROUPED = 1, CV_OUT_Q16 = 2, CV_OUT_NCHW_RELU = 3, CV_OUT_NCHW = 4 };
-__device__ __forceinline__ cv_f4 cv_fma4(cv_f4 a, float s, cv_f4 b)
+__device__ __forceinline__ rac_f4v cv_fma4(rac_f4v a, float s, rac_f4v b)
 {
-    return __builtin_elementwise_fma(a, (cv_f4){s, s, s, s}, b);
+    return __builtin_elementwise_fma(a, (rac_f4v){s, s, s, s}, b);
 }
 
 // MODE = CV_OUT_NHWC: out [N][H][W][256] channel-last.  CV_OUT_GROUPED: the decoder's sampling layout of a feature-pyramid
@@ -216,11 +204,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
     // K order: chunk-major, the 9 taps of a 32-channel chunk back to back -- they re-read the same 4 image rows of that chunk
     // (66 KB per workgroup, 2 MB per XCD: L2 hits), where tap-major had 10 chunks = 320 KB per workgroup between two reads of a
     // line (10 MB per XCD > the 4 MB L2: every tap came from the Infinity Cache -- PMC 1.62 GB fetched per launch for a 173 MB
-    // image).  CV_TAP_MAJOR = 1: the old order (A/B builds).
+    // image).
 #define CV_GLOAD(ks_)                                                                          \
     do {                                                                                       \
-        const int chunk_ = CV_TAP_MAJOR ? (ks_) % chunks : (ks_) / 9;                          \
-        const int tap_ = CV_TAP_MAJOR ? (ks_) / chunks : (ks_) - chunk_ * 9;                   \
+        const int chunk_ = (ks_) / 9;                                                          \
+        const int tap_ = (ks_) - chunk_ * 9;                                                   \
         const int dy_ = tap_ / 3, dx_ = tap_ - dy_ * 3;                                        \
         const size_t off_ = ((size_t)dy_ * Wp + dx_) * pix_stride + (size_t)chunk_ * 8;        \
         const uint4 *wsrc_ = a.ws + (size_t)(tap_ * chunks + chunk_) * 2048 + tid;             \
@@ -235,12 +223,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
         B_[st0] = rb0; B_[st1] = rb1; B_[st2] = rb2; B_[st3] = rb3;                    \
     } while (0)
 
-    cv_f4 acc[8][4];
+    rac_f4v acc[8][4];
 #pragma unroll
     for (int m = 0; m < 8; ++m)
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn)
-            acc[m][nn] = (cv_f4){0.f, 0.f, 0.f, 0.f};
+            acc[m][nn] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 
     // fragment slots: row = base + li, hi slot lk, lo slot 4 + lk, both XOR-swizzled with (row >> 1) & 7
     int bidx_h[4], bidx_l[4];
@@ -261,7 +249,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
     CV_GLOAD(KS > 1 ? 1 : 0);
     __syncthreads();
     RAC_CLOCK_BEGIN();
-#if CV_SPREAD_STAGING
     // Round 4: the step's staging traffic -- eight LDS writes of tile ks+1 and the eight global loads of tile ks+2 that re-use
     // their registers -- is dealt out over the eight MFMA groups of the step, one (write, load) pair per group, and the A
     // fragments of group m+1 are read under the MFMAs of group m.  Before, all 64 ds_write_b128 of the workgroup hit the LDS
@@ -269,14 +256,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
     // idle for about a quarter of every step (PMC: 54 % MFMA-busy, 43 % of the wave cycles parked).
     for (int ks = 0; ks < KS; ++ks) {
         const int kn = ks + 2 < KS ? ks + 2 : KS - 1;   // (past the end the last tile is re-fetched / re-written: unconditional code)
-        const int chunk_ = CV_TAP_MAJOR ? kn % chunks : kn / 9;
-        const int tap_ = CV_TAP_MAJOR ? kn / chunks : kn - chunk_ * 9;
+        const int chunk_ = kn / 9;
+        const int tap_ = kn - chunk_ * 9;
         const int dy_ = tap_ / 3, dx_ = tap_ - dy_ * 3;
         const size_t off_ = ((size_t)dy_ * Wp + dx_) * pix_stride + (size_t)chunk_ * 8;
         const uint4 *wsrc_ = a.ws + (size_t)(tap_ * chunks + chunk_) * 2048 + tid;
         uint4 *DA = lds4 + ((ks + 1) & 1) * CV_STAGE_U4, *DB = DA + 2048;
-        const cv_h8 *S = reinterpret_cast<const cv_h8 *>(lds4 + (ks & 1) * CV_STAGE_U4);
-        cv_h8 bh[4], bl[4], ah[2], al[2];
+        const rac_h8 *S = reinterpret_cast<const rac_h8 *>(lds4 + (ks & 1) * CV_STAGE_U4);
+        rac_h8 bh[4], bl[4], ah[2], al[2];
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn) {
             bh[nn] = S[bidx_h[nn]];
@@ -294,23 +281,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
                 ah[(m + 1) & 1] = S[row * 8 + (lk ^ f)];
                 al[(m + 1) & 1] = S[row * 8 + ((4 + lk) ^ f)];
             }
-#if defined(RAC_DIAGNOSTIC_BUILD) && defined(CV_ABLATE)
-            // diagnostic builds only (wrong results, timing ablations: DESIGN 3.6): 1 = no LDS writes, 2 = no global loads, 4 = no step barrier
-#define CV_ST(dst_, src_) do { if (!(CV_ABLATE & 1)) dst_ = src_; } while (0)
-#define CV_LD(dst_, expr_) do { if (!(CV_ABLATE & 2)) dst_ = expr_; } while (0)
-#else
-#define CV_ST(dst_, src_) dst_ = src_
-#define CV_LD(dst_, expr_) dst_ = expr_
-#endif
             switch (m) {     // staging piece m: tile ks+1 out of its register into the other LDS stage, tile ks+2 into the register
-            case 0: CV_ST(DA[st0], ra0); CV_LD(ra0, a.xs[a_base0 + off_]); break;
-            case 1: CV_ST(DA[st1], ra1); CV_LD(ra1, a.xs[a_base1 + off_]); break;
-            case 2: CV_ST(DA[st2], ra2); CV_LD(ra2, a.xs[a_base2 + off_]); break;
-            case 3: CV_ST(DA[st3], ra3); CV_LD(ra3, a.xs[a_base3 + off_]); break;
-            case 4: CV_ST(DB[st0], rb0); CV_LD(rb0, wsrc_[0]); break;
-            case 5: CV_ST(DB[st1], rb1); CV_LD(rb1, wsrc_[512]); break;
-            case 6: CV_ST(DB[st2], rb2); CV_LD(rb2, wsrc_[1024]); break;
-            default: CV_ST(DB[st3], rb3); CV_LD(rb3, wsrc_[1536]); break;
+            case 0: DA[st0] = ra0; ra0 = a.xs[a_base0 + off_]; break;
+            case 1: DA[st1] = ra1; ra1 = a.xs[a_base1 + off_]; break;
+            case 2: DA[st2] = ra2; ra2 = a.xs[a_base2 + off_]; break;
+            case 3: DA[st3] = ra3; ra3 = a.xs[a_base3 + off_]; break;
+            case 4: DB[st0] = rb0; rb0 = wsrc_[0]; break;
+            case 5: DB[st1] = rb1; rb1 = wsrc_[512]; break;
+            case 6: DB[st2] = rb2; rb2 = wsrc_[1024]; break;
+            default: DB[st3] = rb3; rb3 = wsrc_[1536]; break;
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -324,54 +303,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
                 acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[nn], ah[m & 1], acc[m][nn], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#if defined(RAC_DIAGNOSTIC_BUILD) && defined(CV_ABLATE) && (CV_ABLATE & 4)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-        __syncthreads();
-#endif
-    }
-#else
-    for (int ks = 0; ks < KS; ++ks) {
-        // (past the end the last tile is re-fetched / re-written into the unused stage: unconditional code keeps the
-        //  staging registers out of scratch)
-        CV_LSTORE((ks + 1) & 1);
-        const int kn = ks + 2 < KS ? ks + 2 : KS - 1;
-        CV_GLOAD(kn);
-        // (nothing may move across this line: without it hipcc re-uses the eight staging registers for A fragments during the MFMA
-        //  phase and sinks the loads of tile ks+2 to the END of the step)
-        __builtin_amdgcn_sched_barrier(0);
-        const cv_h8 *S = reinterpret_cast<const cv_h8 *>(lds4 + (ks & 1) * CV_STAGE_U4);
-        cv_h8 bh[4], bl[4];
-#pragma unroll
-        for (int nn = 0; nn < 4; ++nn) {
-            bh[nn] = S[bidx_h[nn]];
-            bl[nn] = S[bidx_l[nn]];
-        }
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int row = arow0 + 16 * m, f = (row >> 1) & 7;
-            const cv_h8 ah = S[row * 8 + (lk ^ f)];
-            const cv_h8 al = S[row * 8 + ((4 + lk) ^ f)];
-#pragma unroll
-            for (int nn = 0; nn < 4; ++nn)
-                acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[nn], al, acc[m][nn], 0, 0, 0);
-#pragma unroll
-            for (int nn = 0; nn < 4; ++nn)
-                acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[nn], ah, acc[m][nn], 0, 0, 0);
-#pragma unroll
-            for (int nn = 0; nn < 4; ++nn)
-                acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[nn], ah, acc[m][nn], 0, 0, 0);
-        }
         __syncthreads();
     }
-#endif
 
     RAC_CLOCK_END(conv3x3, blockIdx.x);
     // epilogue: undo the two power-of-two scalings, add the bias (per channel, or per pixel and channel), channel-last store.
     // The weights are the MFMA's A operand, so a 16x16 accumulator tile has its PIXEL on the lane (column li) and four
     // consecutive output CHANNELS (rows 4 lk + r) in the lane's registers: one 16-byte store (and one 16-byte bias load) per
     // tile instead of four 4-byte ones (round 4; the predicated 4-byte form also serialised 128 bias loads per lane).
-    const float unscale = a.w_alpha / cv_act_scale(MODE == CV_OUT_NCHW_RELU ? (a.amax ? a.scale_mul * *a.amax : 0.f) + a.scale_add : *a.amax);
+    const float unscale = a.w_alpha / rac_act_scale(MODE == CV_OUT_NCHW_RELU ? (a.amax ? a.scale_mul * *a.amax : 0.f) + a.scale_add : *a.amax);
     const int prows = min(CV_TM, HW - tile * CV_TM);       // valid pixels of this tile
     if (MODE == CV_OUT_NCHW_RELU || MODE == CV_OUT_NCHW) {
         // a channel's 16 pixels of tile m are the 16 lanes li: 64-byte runs, the 8 tiles m of a wave row 512 contiguous bytes
@@ -379,14 +319,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn) {
             const int col = 64 * wn + 16 * nn + 4 * lk;
-            const cv_f4 bv = a.bias ? *reinterpret_cast<const cv_f4 *>(a.bias + col) : (cv_f4){0.f, 0.f, 0.f, 0.f};
+            const rac_f4v bv = a.bias ? *reinterpret_cast<const rac_f4v *>(a.bias + col) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const int p = 128 * wm + 16 * m + li;
                 if (p < prows) {
-                    cv_f4 v = cv_fma4(acc[m][nn], unscale, bv);
+                    rac_f4v v = cv_fma4(acc[m][nn], unscale, bv);
                     if (MODE == CV_OUT_NCHW_RELU)      // (rac_relu: a NaN stays a NaN, as torch.relu keeps it; the vector maximum returns 0)
-                        v = (cv_f4){rac_relu(v[0]), rac_relu(v[1]), rac_relu(v[2]), rac_relu(v[3])};
+                        v = (rac_f4v){rac_relu(v[0]), rac_relu(v[1]), rac_relu(v[2]), rac_relu(v[3])};
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         obase[(size_t)(col + r) * HW + p] = v[r];
@@ -402,12 +342,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn) {
             const int c = 16 * nn + 4 * lk;
-            const cv_f4 bv = a.bias ? *reinterpret_cast<const cv_f4 *>(a.bias + 64 * wn + c) : (cv_f4){0.f, 0.f, 0.f, 0.f};
+            const rac_f4v bv = a.bias ? *reinterpret_cast<const rac_f4v *>(a.bias + 64 * wn + c) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const int p = 128 * wm + 16 * m + li;
                 if (p < prows)
-                    *reinterpret_cast<cv_f4 *>(obase + (size_t)p * 64 + c) = cv_fma4(acc[m][nn], unscale, bv);
+                    *reinterpret_cast<rac_f4v *>(obase + (size_t)p * 64 + c) = cv_fma4(acc[m][nn], unscale, bv);
             }
         }
         return;
@@ -422,21 +362,21 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
         float *sbase = a.qscale + ((size_t)n * HW + (size_t)tile * CV_TM) * 4 + wn;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            cv_f4 pb[4][4];
+            rac_f4v pb[4][4];
 #pragma unroll
             for (int mm = 0; mm < 4; ++mm) {
                 const int p = min(128 * wm + 16 * (4 * half + mm) + li, prows - 1);
 #pragma unroll
                 for (int nn = 0; nn < 4; ++nn) {
                     const int col = 64 * wn + 16 * nn + 4 * lk;
-                    pb[mm][nn] = pbase ? *reinterpret_cast<const cv_f4 *>(pbase + (size_t)p * CV_COUT + col)
-                                       : (a.bias ? *reinterpret_cast<const cv_f4 *>(a.bias + col) : (cv_f4){0.f, 0.f, 0.f, 0.f});
+                    pb[mm][nn] = pbase ? *reinterpret_cast<const rac_f4v *>(pbase + (size_t)p * CV_COUT + col)
+                                       : (a.bias ? *reinterpret_cast<const rac_f4v *>(a.bias + col) : (rac_f4v){0.f, 0.f, 0.f, 0.f});
                 }
             }
 #pragma unroll
             for (int mm = 0; mm < 4; ++mm) {
                 const int m = 4 * half + mm, p = 128 * wm + 16 * m + li;
-                cv_f4 v[4];
+                rac_f4v v[4];
                 unsigned bm = 0u;
 #pragma unroll
                 for (int nn = 0; nn < 4; ++nn) {
@@ -462,18 +402,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_f16x3_kernel(const ConvArgs a)
 #pragma unroll
     for (int nn = 0; nn < 4; ++nn) {
         const int col = 64 * wn + 16 * nn + 4 * lk;
-        const cv_f4 bv = (!pbase && a.bias) ? *reinterpret_cast<const cv_f4 *>(a.bias + col) : (cv_f4){0.f, 0.f, 0.f, 0.f};
-        cv_f4 pb[8];
+        const rac_f4v bv = (!pbase && a.bias) ? *reinterpret_cast<const rac_f4v *>(a.bias + col) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
+        rac_f4v pb[8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int p = min(128 * wm + 16 * m + li, prows - 1);      // (rows past a ragged tile re-read its last row; not stored)
-            pb[m] = pbase ? *reinterpret_cast<const cv_f4 *>(pbase + (size_t)p * CV_COUT + col) : bv;
+            pb[m] = pbase ? *reinterpret_cast<const rac_f4v *>(pbase + (size_t)p * CV_COUT + col) : bv;
         }
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int p = 128 * wm + 16 * m + li;
             if (p < prows)
-                *reinterpret_cast<cv_f4 *>(obase + (size_t)p * CV_COUT + col) = cv_fma4(acc[m][nn], unscale, pb[m]);
+                *reinterpret_cast<rac_f4v *>(obase + (size_t)p * CV_COUT + col) = cv_fma4(acc[m][nn], unscale, pb[m]);
         }
     }
 }
@@ -493,9 +433,7 @@ struct ConvS2Args {
     float w_alpha;
 };
 
-#ifndef S2_TM
 #define S2_TM 128 /* output pixels per workgroup: 256 workgroups of 4 waves for the 8 x 64 x 64 maps (64: 79 us, 128: 77 us, 256: 86 us) */
-#endif
 #define S2_THREADS (2 * S2_TM)
 #define S2_RSTEP (S2_THREADS / 8) /* tile rows staged per pass */
 #define S2_NB (64 / S2_RSTEP)     /* passes for the 64 weight rows */
@@ -523,8 +461,8 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3s2_c64_f16x3_kernel(cons
     uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
 #define S2_GLOAD(ks_)                                                                          \
     do {                                                                                       \
-        const int chunk_ = CV_TAP_MAJOR ? (ks_) % chunks : (ks_) / 9;                          \
-        const int tap_ = CV_TAP_MAJOR ? (ks_) / chunks : (ks_) - chunk_ * 9;  /* chunk-major, as above */ \
+        const int chunk_ = (ks_) / 9;                                                          \
+        const int tap_ = (ks_) - chunk_ * 9;  /* chunk-major, as above */                      \
         const int dy_ = tap_ / 3, dx_ = tap_ - dy_ * 3;                                        \
         const size_t off_ = ((size_t)dy_ * Wp + dx_) * pix_stride + (size_t)chunk_ * 8;        \
         const size_t wk_ = (size_t)(tap_ * chunks + chunk_) * 512;                             \
@@ -546,12 +484,12 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3s2_c64_f16x3_kernel(cons
         }                                                                                      \
     } while (0)
 
-    cv_f4 acc[2][4];
+    rac_f4v acc[2][4];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn)
-            acc[m][nn] = (cv_f4){0.f, 0.f, 0.f, 0.f};
+            acc[m][nn] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
     int bidx_h[4], bidx_l[4];
 #pragma unroll
     for (int nn = 0; nn < 4; ++nn) {
@@ -570,8 +508,8 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3s2_c64_f16x3_kernel(cons
         const int kn = ks + 2 < KS ? ks + 2 : KS - 1;
         S2_GLOAD(kn);
         __builtin_amdgcn_sched_barrier(0);   // (as in conv3x3_f16x3_kernel: the loads stay at the top of the step)
-        const cv_h8 *S = reinterpret_cast<const cv_h8 *>(lds4 + (ks & 1) * STAGE);
-        cv_h8 bh[4], bl[4];
+        const rac_h8 *S = reinterpret_cast<const rac_h8 *>(lds4 + (ks & 1) * STAGE);
+        rac_h8 bh[4], bl[4];
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn) {
             bh[nn] = S[bidx_h[nn]];
@@ -580,8 +518,8 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3s2_c64_f16x3_kernel(cons
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int row = arow0 + 16 * m, f = (row >> 1) & 7;
-            const cv_h8 ah = S[row * 8 + (lk ^ f)];
-            const cv_h8 al = S[row * 8 + ((4 + lk) ^ f)];
+            const rac_h8 ah = S[row * 8 + (lk ^ f)];
+            const rac_h8 al = S[row * 8 + ((4 + lk) ^ f)];
 #pragma unroll
             for (int nn = 0; nn < 4; ++nn)
                 acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[nn], acc[m][nn], 0, 0, 0);
@@ -595,7 +533,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void conv3x3s2_c64_f16x3_kernel(cons
         __syncthreads();
     }
     // epilogue: NCHW store -- for a channel (column li) the lane's 4 accumulator rows are 4 consecutive output pixels
-    const float unscale = a.w_alpha / cv_act_scale(*a.amax);
+    const float unscale = a.w_alpha / rac_act_scale(*a.amax);
     float *obase = a.out + (size_t)n * a.out_ctotal * OH * OW + (size_t)tile * S2_TM;
 #pragma unroll
     for (int nn = 0; nn < 4; ++nn) {

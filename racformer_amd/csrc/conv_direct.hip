@@ -32,10 +32,6 @@
 // z, r and candidate pre-activations of one (pixel, channel) in the same lane (tiles 0 / 1 / 2 = the three gate blocks).
 #include "rac_common.h"
 
-typedef _Float16 cd_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cd_h4 __attribute__((ext_vector_type(4)));
-typedef float cd_f4 __attribute__((ext_vector_type(4)));
-
 struct CdArgs {
     const uint4 *xs;
     const uint4 *ws;
@@ -63,9 +59,9 @@ __device__ __forceinline__ float cd_scale(const rac_cd_scale &s)
     return rac_act_scale((s.amax ? s.mul * *s.amax : 0.f) + s.add);
 }
 // the ReLU epilogues: rac_relu per component -- a NaN stays a NaN, as torch.relu keeps it (the vector maximum returns 0 for one)
-__device__ __forceinline__ cd_f4 cd_relu4(cd_f4 v)
+__device__ __forceinline__ rac_f4v cd_relu4(rac_f4v v)
 {
-    return (cd_f4){rac_relu(v[0]), rac_relu(v[1]), rac_relu(v[2]), rac_relu(v[3])};
+    return (rac_f4v){rac_relu(v[0]), rac_relu(v[1]), rac_relu(v[2]), rac_relu(v[3])};
 }
 
 // Workgroup = 4 waves = 64 PT consecutive output pixels of one frame x one block of 16 NT output channels.
@@ -119,12 +115,12 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
     // fragment order <- line order: lane (li, lk) takes what loader lane 4 li + lk fetched
     const int perm_addr = ((lane & 15) * 4 + (lane >> 4)) * 4;
 
-    cd_f4 acc[NT][PT];
+    rac_f4v acc[NT][PT];
 #pragma unroll
     for (int nn = 0; nn < NT; ++nn)
 #pragma unroll
         for (int j = 0; j < PT; ++j)
-            acc[nn][j] = (cd_f4){0.f, 0.f, 0.f, 0.f};
+            acc[nn][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 
     if constexpr (KCH > 0) {
         // weight chunk c -> buffer c & 1: piece q = (tap, tile, row half); lane = (row lane >> 3 of the half, LDS slot lane & 7)
@@ -153,7 +149,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
         // A fragments of K step (chunk c, tap): row li of tile nn, hi slot lk, lo slot 4 + lk
         const int fsw = (li >> 1) & 7, ahi = li * 8 + (lk ^ fsw), alo = li * 8 + ((4 + lk) ^ fsw);
         uint4 xr[D][PT][2];
-        cd_h8 wh[2][NT], wl[2][NT];
+        rac_h8 wh[2][NT], wl[2][NT];
 #define CD_XLOAD(slot_, ks_)                                                                       \
     do {                                                                                           \
         constexpr int ksc_ = (ks_) < KS ? (ks_) : KS - 1;     /* past the end: re-fetch the last step */ \
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
 #define CD_ALOAD(set_, ks_)                                                                        \
     do {                                                                                           \
         constexpr int kk_ = (ks_) < KS ? (ks_) : KS - 1;                                           \
-        const cd_h8 *S_ = reinterpret_cast<const cd_h8 *>(cd_lds + ((kk_ / 9) & 1) * SLICE + (kk_ % 9) * NT * 128); \
+        const rac_h8 *S_ = reinterpret_cast<const rac_h8 *>(cd_lds + ((kk_ / 9) & 1) * SLICE + (kk_ % 9) * NT * 128); \
         _Pragma("unroll") for (int nn = 0; nn < NT; ++nn)                                          \
         {                                                                                          \
             wh[set_][nn] = S_[nn * 128 + ahi];                                                     \
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
             }
 #pragma unroll
             for (int j = 0; j < PT; ++j) {
-                const cd_h8 bh = __builtin_bit_cast(cd_h8, xq[set][j][0]), bl = __builtin_bit_cast(cd_h8, xq[set][j][1]);
+                const rac_h8 bh = __builtin_bit_cast(rac_h8, xq[set][j][0]), bl = __builtin_bit_cast(rac_h8, xq[set][j][1]);
 #pragma unroll
                 for (int nn = 0; nn < NT; ++nn)
                     acc[nn][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[set][nn], bl, acc[nn][j], 0, 0, 0);
@@ -238,7 +234,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
     }
 
     const float unscale = KCH > 0 ? a.w_alpha / cd_scale(a.in_scale) : 0.f;
-    const cd_f4 us4 = {unscale, unscale, unscale, unscale};
+    const rac_f4v us4 = {unscale, unscale, unscale, unscale};
     const float so = MODE == RAC_CD_F32 ? 1.f : cd_scale(a.out_scale);
     const size_t fout = MODE == RAC_CD_F32 ? 0 : (size_t)cd_frame(a.out_frames, n) * (a.OH + 2);
 #pragma unroll
@@ -251,10 +247,10 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) {
                 const int c = co0[nn] + 4 * lk;
-                cd_f4 add = a.bias ? *reinterpret_cast<const cd_f4 *>(a.bias + c) : (cd_f4){0.f, 0.f, 0.f, 0.f};
+                rac_f4v add = a.bias ? *reinterpret_cast<const rac_f4v *>(a.bias + c) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
                 if (a.pixel_map)
-                    add += *reinterpret_cast<const cd_f4 *>(a.pixel_map + (size_t)p * a.Cout + c);
-                cd_f4 v = __builtin_elementwise_fma(acc[nn][j], us4, add);
+                    add += *reinterpret_cast<const rac_f4v *>(a.pixel_map + (size_t)p * a.Cout + c);
+                rac_f4v v = __builtin_elementwise_fma(acc[nn][j], us4, add);
                 if constexpr (EPI != 0)
                     v = cd_relu4(v);
                 if constexpr (EPI == 2) {
@@ -263,7 +259,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
                     for (int r = 0; r < 4; ++r)
                         ocf[(size_t)r * npix] = v[r];
                 } else {
-                    *reinterpret_cast<cd_f4 *>(o + c) = v;
+                    *reinterpret_cast<rac_f4v *>(o + c) = v;
                 }
             }
             continue;
@@ -271,8 +267,8 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
         // the activation-image destination: pixel (oh + 1, ow + 1) of the output frame, per 32-channel chunk [hi 32 | lo 32]
         const int oh = p / a.OW, ow = p - oh * a.OW;
         _Float16 *opix = a.out_img + (((fout + oh + 1) * (a.OW + 2) + ow + 1) * a.out_chunks_total + a.out_chunk0) * 64;
-        auto store_img = [&](int co, cd_f4 v) {      // channels co .. co + 3 of this launch's output
-            cd_h4 hi, lo;
+        auto store_img = [&](int co, rac_f4v v) {      // channels co .. co + 3 of this launch's output
+            rac_h4v hi, lo;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float y = v[r] * so;
@@ -280,15 +276,15 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
                 lo[r] = (_Float16)(y - (float)hi[r]);
             }
             _Float16 *d = opix + (co >> 5) * 64 + (co & 31);
-            *reinterpret_cast<cd_h4 *>(d) = hi;
-            *reinterpret_cast<cd_h4 *>(d + 32) = lo;
+            *reinterpret_cast<rac_h4v *>(d) = hi;
+            *reinterpret_cast<rac_h4v *>(d + 32) = lo;
         };
         if (MODE == RAC_CD_IMAGE) {
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) {
                 const int c = co0[nn] + 4 * lk;
-                const cd_f4 bv = a.bias ? *reinterpret_cast<const cd_f4 *>(a.bias + c) : (cd_f4){0.f, 0.f, 0.f, 0.f};
-                cd_f4 v = __builtin_elementwise_fma(acc[nn][j], us4, bv);
+                const rac_f4v bv = a.bias ? *reinterpret_cast<const rac_f4v *>(a.bias + c) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
+                rac_f4v v = __builtin_elementwise_fma(acc[nn][j], us4, bv);
                 if constexpr (EPI != 0)
                     v = cd_relu4(v);
                 store_img(c, v);
@@ -298,11 +294,11 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
         // GRU update (models/racformer_transformer.py:714-720): channel c = 16 cb + 4 lk + r of the 64
         const int c4 = 16 * cb + 4 * lk;
         const float *xp = a.xpart + ((size_t)cd_frame(a.xpart_frames, n) * npix + p) * 192 + c4;
-        const cd_f4 xz = *reinterpret_cast<const cd_f4 *>(xp), xg = *reinterpret_cast<const cd_f4 *>(xp + 64),
-                    xc = *reinterpret_cast<const cd_f4 *>(xp + 128);
-        const cd_f4 hp = a.h_prev ? *reinterpret_cast<const cd_f4 *>(a.h_prev + ((size_t)cd_frame(a.h_prev_frames, n) * npix + p) * 64 + c4)
-                                  : (cd_f4){0.f, 0.f, 0.f, 0.f};
-        cd_f4 h;
+        const rac_f4v xz = *reinterpret_cast<const rac_f4v *>(xp), xg = *reinterpret_cast<const rac_f4v *>(xp + 64),
+                    xc = *reinterpret_cast<const rac_f4v *>(xp + 128);
+        const rac_f4v hp = a.h_prev ? *reinterpret_cast<const rac_f4v *>(a.h_prev + ((size_t)cd_frame(a.h_prev_frames, n) * npix + p) * 64 + c4)
+                                  : (rac_f4v){0.f, 0.f, 0.f, 0.f};
+        rac_f4v h;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float zg = __builtin_fmaf(acc[0][j][r], unscale, xz[r]);
@@ -313,7 +309,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const CdArgs a)
             const float cand = tanhf(cg + rr * hp[r]);
             h[r] = (1.f - z) * hp[r] + z * cand;
         }
-        *reinterpret_cast<cd_f4 *>(a.h_out + ((size_t)cd_frame(a.h_out_frames, n) * npix + p) * 64 + c4) = h;
+        *reinterpret_cast<rac_f4v *>(a.h_out + ((size_t)cd_frame(a.h_out_frames, n) * npix + p) * 64 + c4) = h;
         store_img(c4, h);
     }
 }
@@ -341,7 +337,7 @@ __global__ __launch_bounds__(256) void upsample2x_image_kernel(const float *__re
         const float *b = src + (size_t)f * h * w * C + c8 * 8;
         const float *p00 = b + ((size_t)y0 * w + x0) * C, *p01 = b + ((size_t)y0 * w + x1) * C;
         const float *p10 = b + ((size_t)y1 * w + x0) * C, *p11 = b + ((size_t)y1 * w + x1) * C;
-        cd_h8 hi, lo;
+        rac_h8 hi, lo;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const rac_f4 a00 = rac_ld4(p00 + 4 * q), a01 = rac_ld4(p01 + 4 * q), a10 = rac_ld4(p10 + 4 * q), a11 = rac_ld4(p11 + 4 * q);
@@ -357,8 +353,8 @@ __global__ __launch_bounds__(256) void upsample2x_image_kernel(const float *__re
             }
         }
         _Float16 *d = img + ((((size_t)f * (oh + 2) + y + 1) * (ow + 2) + x + 1) * chunks + (c8 >> 2)) * 64 + (c8 & 3) * 8;
-        *reinterpret_cast<cd_h8 *>(d) = hi;
-        *reinterpret_cast<cd_h8 *>(d + 32) = lo;
+        *reinterpret_cast<rac_h8 *>(d) = hi;
+        *reinterpret_cast<rac_h8 *>(d + 32) = lo;
     }
 }
 

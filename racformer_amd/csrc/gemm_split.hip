@@ -34,9 +34,6 @@
 // (round-robin dispatch) and take consecutive tile ranges, so tiles that share W rows pull them through one L2.
 #include "rac_common.h"
 
-typedef _Float16 gs_h8 __attribute__((ext_vector_type(8)));
-typedef float gs_f4 __attribute__((ext_vector_type(4)));
-
 #define GS_TW 256                          /* W rows (output features) per tile */
 #define GS_TX 128                          /* X rows per tile (at most) */
 #define GS_LINE 128                        /* bytes per row and K step of 32: [hi 32 | lo 32] f16 */
@@ -157,7 +154,7 @@ __global__ __launch_bounds__(768, 1) void gemm_split_kernel(const GemmSplitArgs 
         w_off[i] = (64 * ww + 16 * i + li) * GS_LINE;
         x_off[i] = GS_TW * GS_LINE + (64 * wx + 16 * i + li) * GS_LINE;
     }
-    gs_f4 acc[4][4];                                // [W tile][X tile]: rows = features, cols = X rows
+    rac_f4v acc[4][4];                                // [W tile][X tile]: rows = features, cols = X rows
     __builtin_amdgcn_s_barrier();                   // step 0 has landed
     RAC_CLOCK_BEGIN();
     int gs = 0;
@@ -173,20 +170,20 @@ __global__ __launch_bounds__(768, 1) void gemm_split_kernel(const GemmSplitArgs 
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[i][j] = (gs_f4){0.f, 0.f, 0.f, 0.f};
+                acc[i][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
         for (int ks = 0; ks < ksteps; ++ks, ++gs) {
             const char *S = lds + (gs % GS_STAGES) * GS_STAGE;
-            gs_h8 wh[4], wl[4];
+            rac_h8 wh[4], wl[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                wh[i] = *reinterpret_cast<const gs_h8 *>(S + w_off[i] + ch);
-                wl[i] = *reinterpret_cast<const gs_h8 *>(S + w_off[i] + cl);
+                wh[i] = *reinterpret_cast<const rac_h8 *>(S + w_off[i] + ch);
+                wl[i] = *reinterpret_cast<const rac_h8 *>(S + w_off[i] + cl);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j < nx) {
-                    const gs_h8 xh = *reinterpret_cast<const gs_h8 *>(S + x_off[j] + ch);
-                    const gs_h8 xl = *reinterpret_cast<const gs_h8 *>(S + x_off[j] + cl);
+                    const rac_h8 xh = *reinterpret_cast<const rac_h8 *>(S + x_off[j] + ch);
+                    const rac_h8 xl = *reinterpret_cast<const rac_h8 *>(S + x_off[j] + cl);
                     // smallest terms first
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -215,12 +212,12 @@ __global__ __launch_bounds__(768, 1) void gemm_split_kernel(const GemmSplitArgs 
                 for (int i = 0; i < 4; ++i) {
                     const int n = wt * GS_TW + 64 * ww + 16 * i + 4 * lk;
                     if (n + 3 < g.N) {
-                        gs_f4 v = acc[i][j];
+                        rac_f4v v = acc[i][j];
                         if (g.affine) {
-                            const gs_f4 b = g.bias ? *reinterpret_cast<const gs_f4 *>(g.bias + n) : (gs_f4){0.f, 0.f, 0.f, 0.f};
+                            const rac_f4v b = g.bias ? *reinterpret_cast<const rac_f4v *>(g.bias + n) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
                             v = v * g.alpha + b;
                         }
-                        *reinterpret_cast<gs_f4 *>(obase + (size_t)row * ld + n) = v;
+                        *reinterpret_cast<rac_f4v *>(obase + (size_t)row * ld + n) = v;
                     } else {
                         for (int r = 0; r < 4; ++r)
                             if (n + r < g.N)
@@ -245,15 +242,7 @@ __global__ __launch_bounds__(768, 1) void gemm_split_kernel(const GemmSplitArgs 
 // All eight waves multiply AND load (four pieces each per stage; the two waves of a SIMD alternate between the LDS-DMA
 // issue and their MFMA block); stores, LDS-DMA and loads share vmcnt, so the counted wait covers the stores in between.
 #define GW_STAGES 4
-#ifndef GW4_LDS_PAD
-#define GW4_LDS_PAD 0                       /* A/B builds: extra LDS bytes requested by the four-wave shape (96 KB in all: one workgroup per CU) */
-#endif
-#ifndef GW_UNROLL
 #define GW_UNROLL 4                         /* stages per trip of the stage loop (a multiple of GW_STAGES) */
-#endif
-#ifndef GW_WIDE_WAVES
-#define GW_WIDE_WAVES 8                     /* waves per workgroup of the wide generator launch: 8 (one workgroup per CU) or 4 (two; A/B builds) */
-#endif
 
 struct GenArgs {
     const char *x;      // X image [M][8 lines]
@@ -336,7 +325,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_k
     if (nstages > 2) issue(2, 2);
 
     // ---- this wave's weights: fragment (tile t, K step ks) = W rows n0 + 16t + li, 16-byte chunk lk of the hi / lo half
-    gs_h8 wh[2][8], wl[2][8];
+    rac_h8 wh[2][8], wl[2][8];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         int n = n0 + 16 * t + li;
@@ -344,15 +333,15 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_k
         const char *wp = g.w + (size_t)n * 1024 + lk * 16;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            wh[t][ks] = *reinterpret_cast<const gs_h8 *>(wp + ks * 128);
-            wl[t][ks] = *reinterpret_cast<const gs_h8 *>(wp + ks * 128 + 64);
+            wh[t][ks] = *reinterpret_cast<const rac_h8 *>(wp + ks * 128);
+            wl[t][ks] = *reinterpret_cast<const rac_h8 *>(wp + ks * 128 + 64);
         }
     }
-    gs_f4 bias4[2];
+    rac_f4v bias4[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = n0 + 16 * t + 4 * lk;
-        bias4[t] = (g.bias && n + 3 < g.N) ? *reinterpret_cast<const gs_f4 *>(g.bias + n) : (gs_f4){0.f, 0.f, 0.f, 0.f};
+        bias4[t] = (g.bias && n + 3 < g.N) ? *reinterpret_cast<const rac_f4v *>(g.bias + n) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
     }
     float inv_scale = 1.f;      // (two exact power-of-two factors one after the other: their product could leave the float range)
     if constexpr (DEVSCALE)
@@ -381,21 +370,21 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_k
         if (u != 0 && st + 3 < nstages)
             issue(st + 3, (u + 3) & (GW_STAGES - 1));
         const char *S = lds + (u & (GW_STAGES - 1)) * STAGE;
-        gs_f4 acc[2][J];
+        rac_f4v acc[2][J];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int j = 0; j < J; ++j)
-                acc[t][j] = (gs_f4){0.f, 0.f, 0.f, 0.f};
+                acc[t][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
         // X fragments one K step ahead of their MFMAs (two register sets): the LDS latency of step ks + 1 runs under the
         // MFMAs of step ks instead of in front of them
-        gs_h8 xh[2][J], xl[2][J];
+        rac_h8 xh[2][J], xl[2][J];
         auto frag = [&](int ks, int b) {
 #pragma unroll
             for (int j = 0; j < J; ++j) {
                 const char *rowp = S + (16 * j + li) * 1024;
-                xh[b][j] = *reinterpret_cast<const gs_h8 *>(rowp + (((8 * ks + lk) ^ li) * 16));
-                xl[b][j] = *reinterpret_cast<const gs_h8 *>(rowp + (((8 * ks + 4 + lk) ^ li) * 16));
+                xh[b][j] = *reinterpret_cast<const rac_h8 *>(rowp + (((8 * ks + lk) ^ li) * 16));
+                xl[b][j] = *reinterpret_cast<const rac_h8 *>(rowp + (((8 * ks + 4 + lk) ^ li) * 16));
             }
         };
         frag(0, 0);
@@ -439,14 +428,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2) void generator_ws_k
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int n = n0 + 16 * t + 4 * lk;
-                gs_f4 v;
+                rac_f4v v;
                 if constexpr (DEVSCALE)
                     v = acc[t][j] * g.alpha * inv_scale + bias4[t];
                 else
                     v = acc[t][j] * g.alpha + bias4[t];
                 if (row < m0 + mrows) {
                     if (n + 3 < g.N) {
-                        *reinterpret_cast<gs_f4 *>(g.out + (size_t)row * g.ld_out + n) = v;
+                        *reinterpret_cast<rac_f4v *>(g.out + (size_t)row * g.ld_out + n) = v;
                     } else {
                         for (int r = 0; r < 4; ++r)
                             if (n + r < g.N)
@@ -560,39 +549,28 @@ template <bool DS>
 static int gen_ws_launch(GenArgs &a, hipStream_t st, const char *what)
 {
     const int M = a.M, N = a.N;
-    if (GW_WIDE_WAVES == 4 && N >= 128 * 128) {
-        // the wide generator (65536 features): 512 workgroups of four waves, two per CU, every one walks all rows
-        a.rows_per_wg = (M + 15) / 16 * 16;
-        if (const int rc_attr = rac_set_dynamic_lds_once(DS ? RAC_ATTR_GENERATOR4_DS : RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16, DS>), GW_STAGES * 16 * 1024 + GW4_LDS_PAD))
-            return rc_attr;
-        hipLaunchKernelGGL((generator_ws_kernel<4, 16, DS>), dim3((N + 127) / 128, 1), dim3(256), GW_STAGES * 16 * 1024 + GW4_LDS_PAD, st, a);
-        return rac_launch_status(what);
-    }
     // narrow outputs (the 2189 features of the sampling Linears, not the generator's 65536): the rows are cut into chunks so that
     // feature blocks x chunks covers the CUs; every chunk re-reads its weight rows (L2) for a few row stages of work, so the
     // weight prologue is most of a workgroup's life.  Round 5: the FOUR-wave shape here (128 features = 128 KB of weights per
-    // workgroup instead of 256 KB, 16-row stages; about 256 workgroups): 15.6 -> 12.3 us at N = 2189, M = 900
-    // (the same shape LOSES on the wide generator, 104-106 us against 88-90: there the stage loop is everything).
-#if !defined(GW_NARROW_WAVES) || GW_NARROW_WAVES == 4
+    // workgroup instead of 256 KB, 16-row stages; about 256 workgroups): 15.6 -> 12.3 us at N = 2189, M = 900.
     if (N < 128 * 128) {
         const int fb = (N + 127) / 128;
         int ch = fb >= 256 ? 1 : 256 / fb;      // about one workgroup per CU (rows per workgroup 32 / 48 / 64 / 80 / 112: 15.7 / 13.9 / 12.9 / 12.3 / 12.7 us)
         const int maxc = (M + 15) / 16;
         ch = ch > maxc ? maxc : ch;
         a.rows_per_wg = ((M + ch - 1) / ch + 15) / 16 * 16;
-#ifdef GW_NARROW_ROWS
-        a.rows_per_wg = GW_NARROW_ROWS;      /* A/B builds */
-#endif
         ch = (M + a.rows_per_wg - 1) / a.rows_per_wg;
-        if (const int rc_attr = rac_set_dynamic_lds_once(DS ? RAC_ATTR_GENERATOR4_DS : RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16, DS>), GW_STAGES * 16 * 1024 + GW4_LDS_PAD))
+        if (const int rc_attr = rac_set_dynamic_lds_once(DS ? RAC_ATTR_GENERATOR4_DS : RAC_ATTR_GENERATOR4, reinterpret_cast<const void *>(generator_ws_kernel<4, 16, DS>), GW_STAGES * 16 * 1024))
             return rc_attr;
-        hipLaunchKernelGGL((generator_ws_kernel<4, 16, DS>), dim3(fb, ch), dim3(256), GW_STAGES * 16 * 1024 + GW4_LDS_PAD, st, a);
+        hipLaunchKernelGGL((generator_ws_kernel<4, 16, DS>), dim3(fb, ch), dim3(256), GW_STAGES * 16 * 1024, st, a);
         return rac_launch_status(what);
     }
-#endif
-    // the eight-wave shape for narrow outputs (rounds 2-4; A/B builds with -DGW_NARROW_WAVES=8): one workgroup per CU (128 KB of
-    // LDS), so at most 256 workgroups: a 257th would wait for a whole round.  (Measured at N = 2189, M = 900: 135 workgroups
-    // 14.8 us, 261 workgroups 20.5 us; an XCD-major item order that keeps a feature block's chunks on one L2 changed nothing.)
+    // everything wider (the generator's 65536 features) takes the eight-wave shape, one workgroup per CU (128 KB of LDS); the
+    // rows are still cut into chunks while the feature blocks alone would leave CUs idle (N = 16384: 64 blocks x 4 chunks).
+    // Measured: the four-wave shape loses on the wide generator, 104-106 us against 88-90: there the stage loop
+    // is everything.  Measured for narrow outputs at N = 2189, M = 900 (rounds 2-4, before the four-wave shape took them
+    // over): at most 256 workgroups, a 257th waits for a whole round -- 135 workgroups 14.8 us, 261 workgroups 20.5 us; an
+    // XCD-major item order that keeps a feature block's chunks on one L2 changed nothing.
     constexpr int ROWS = 32;
     const int fblocks = (N + 255) / 256;
     int chunks = fblocks >= 128 ? 1 : 256 / fblocks;

@@ -18,8 +18,6 @@
 #include "rac_common.h"
 #include <string.h>
 
-typedef float mix_f4 __attribute__((ext_vector_type(4)));
-
 #define MIX_C 64        /* channels per group (in and out) */
 #define MIX_OUT 128     /* out_points */
 #define MIX_PMAX 96     /* max in_points (f8: 4 points x 8 frames x 3 depths) */
@@ -92,7 +90,7 @@ __device__ __forceinline__ void mix_write_out(const MixArgs &a, const float *sO,
 // 16w + li in register r of tile m), and the two (mean, 1/std) pairs.  Y is then in LDS (region A, row stride MIX_MS) and
 // S half 1 in sS.
 struct MixF32State {
-    mix_f4 acc1[6], acc2[8];
+    rac_f4v acc1[6], acc2[8];
     float mean1, rstd1, mean2, rstd2;
 };
 
@@ -100,8 +98,8 @@ struct MixF32State {
 // recompute (mixing_c64_bwd_kernel), so both run the same MFMA k-order and the same block sums.
 __device__ __forceinline__ void mix_f32_core(const MixArgs &a, float *smem, int q, int g, MixF32State &st)
 {
-    mix_f4 (&acc1)[6] = st.acc1;
-    mix_f4 (&acc2)[8] = st.acc2;
+    rac_f4v (&acc1)[6] = st.acc1;
+    rac_f4v (&acc2)[8] = st.acc2;
     float *sX = smem;                          // [P_pad][68]
     float *sM = smem + MIX_PMAX * MIX_XS;      // [64][80]
     float *sY = smem;                          // [P_pad][80]   (aliases sX|sM after step 1)
@@ -189,7 +187,7 @@ __device__ __forceinline__ void mix_f32_core(const MixArgs &a, float *smem, int 
     // ---- step 1: Y = x @ M, wave w -> columns 16w.. ---------------------------------------------
 #pragma unroll
     for (int m = 0; m < 6; ++m)
-        acc1[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+        acc1[m] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int s = 0; s < MIX_C / 4; ++s) {
         const float bv = sM[(4 * s + lk) * MIX_MS + 16 * wave + li];
@@ -235,7 +233,7 @@ __device__ __forceinline__ void mix_f32_core(const MixArgs &a, float *smem, int 
     // ---- step 2: Z = S @ Y in two 64-row halves --------------------------------------------------
 #pragma unroll
     for (int m = 0; m < 8; ++m)
-        acc2[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+        acc2[m] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
     rac_f4 vs1[6];  // S half 1, fetched while half 0 is being multiplied
 #pragma unroll
     for (int k = 0; k < 6; ++k)
@@ -350,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
     mix_f32_core(a, smem, q, g, st);
 
     // ---- LN2 + ReLU backward: dB (wave w: columns 16w.., all 128 rows, in the layout of B) ---------------------------
-    mix_f4 dB[8];
+    rac_f4v dB[8];
     float s_g = 0.f, s_gb = 0.f;
 #pragma unroll
     for (int m = 0; m < 8; ++m)
@@ -378,10 +376,10 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
 
     // ---- dS = dB Y^T and dY = S^T dB, a 32-row quarter of dB at a time ------------------------------------------------
     // dS: wave w -> rows 16(w&1).. of the quarter, out-point columns 48(w>>1).. (3 tiles);  dY: wave w -> columns 16w..
-    mix_f4 dY[6];
+    rac_f4v dY[6];
 #pragma unroll
     for (int m = 0; m < 6; ++m)
-        dY[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+        dY[m] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
     const int ncol4 = MIX_PMAX >> 2;
     const bool s_vec = (P & 3) == 0;
 #pragma unroll
@@ -416,10 +414,10 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
         // dS tiles of the quarter
         {
             const int mo = wave & 1, n0 = 3 * (wave >> 1);
-            mix_f4 acc[3];
+            rac_f4v acc[3];
 #pragma unroll
             for (int n = 0; n < 3; ++n)
-                acc[n] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+                acc[n] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
             for (int s = 0; s < MIX_C / 4; ++s) {
                 const float av = sDB[(16 * mo + li) * MIXB_DBS + 4 * s + lk];
@@ -482,7 +480,7 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
     float *sX = smem;                          // [96][68]
     float *sMb = smem + MIX_PMAX * MIX_XS;     // [64][68]
     float *sDA = sS;                           // [96][66]
-    mix_f4 dA[6];
+    rac_f4v dA[6];
 #pragma unroll
     for (int m = 0; m < 6; ++m)
 #pragma unroll
@@ -507,10 +505,10 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
 
     // ---- dM = x^T dA: wave w -> columns 16w.. (its own dA columns, straight from the accumulators) ---------------------
     {
-        mix_f4 acc[4];
+        rac_f4v acc[4];
 #pragma unroll
         for (int mc = 0; mc < 4; ++mc)
-            acc[mc] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+            acc[mc] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int m = 0; m < 6; ++m)
 #pragma unroll
@@ -528,10 +526,10 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
     }
     // ---- dx = dA M^T: wave w -> columns 16w.. ---------------------------------------------------------------------------
     {
-        mix_f4 acc[6];
+        rac_f4v acc[6];
 #pragma unroll
         for (int m = 0; m < 6; ++m)
-            acc[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+            acc[m] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
         for (int s = 0; s < MIX_C / 4; ++s) {
             const float bv = sMb[(16 * wave + li) * MIXB_MS + 4 * s + lk];
@@ -576,7 +574,6 @@ __global__ __launch_bounds__(256, 2) void mixing_c64_bwd_kernel(const MixBwdArgs
 //     its 4 registers, so tiles (2t, 2t+1) ARE the B fragment of k-step t of the second product once converted,
 //     with k = 32t + 16h + 4lk + i  <->  fragment element 4h + i.  S is staged with that same k permutation
 //     (an 8-byte-granular shuffle inside each 32-wide block), so its A fragments stay single 16-byte reads.
-typedef _Float16 mix_h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 mix_b8 __attribute__((ext_vector_type(8)));
 struct alignas(8) mix_b4 {
     __bf16 x, y, z, w;
@@ -590,10 +587,6 @@ __device__ __forceinline__ void mix_split_bf16(float v, __bf16 &t1, __bf16 &t2, 
     t3 = (__bf16)(r1 - (float)t2);
 }
 
-#ifndef RAC_MIX_REVERSE
-#define RAC_MIX_REVERSE 1   /* 1: walk the (query, group) items from the LAST one: the generator wrote those rows last, so part of them is still in the
-                                Infinity Cache (A/B, profiles/r04_mixing_reverse_ab.json: 96.4-97.7 -> 91.2-92.2 us per launch); 0: in write order */
-#endif
 #define MIXH_XS 80    /* f16 row stride of the x images  (160 B) */
 #define MIXH_SS 104   /* f16 row stride of the S images  (208 B) */
 #define MIXH_X_BYTES (3 * MIX_PMAX * MIXH_XS * 2)   /* three bf16 terms: 46080 */
@@ -636,7 +629,9 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int li = lane & 15, lk = lane >> 4;
     const int P = a.P;
-    const int item = RAC_MIX_REVERSE ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+    // the (query, group) items are walked from the LAST one: the generator wrote those rows last, so part of them is still in the
+    // Infinity Cache (measured against write order, profiles/r04_mixing_reverse_ab.json: 96.4-97.7 -> 91.2-92.2 us per launch)
+    const int item = (int)(gridDim.x - 1 - blockIdx.x);
     const int q = item / a.G, g = item % a.G;
     const float *gx = a.x + ((size_t)q * a.G + g) * P * MIX_C;
     const float *gM = a.params + (size_t)(q % a.period) * a.ld_params + (size_t)g * (MIX_C * MIX_C + MIX_OUT * P);
@@ -686,7 +681,7 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            mv[ks][j] = RAC_STREAM_NT ? __builtin_nontemporal_load(gM + (32 * ks + 8 * lk + j) * MIX_C + 16 * wave + li) : gM[(32 * ks + 8 * lk + j) * MIX_C + 16 * wave + li];
+            mv[ks][j] = __builtin_nontemporal_load(gM + (32 * ks + 8 * lk + j) * MIX_C + 16 * wave + li);
 #pragma unroll
     for (int k = 0; k < 6; ++k)
         vs0[k] = load_S(0, k);
@@ -720,10 +715,10 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     __syncthreads();
 
     // ---- step 1: Y = x @ M, wave w -> columns 16w.. ------------------------------------------------------------
-    mix_f4 acc1[6];
+    rac_f4v acc1[6];
 #pragma unroll
     for (int m = 0; m < 6; ++m) {
-        acc1[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+        acc1[m] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int off = (16 * m + li) * MIXH_XS + 32 * ks + 8 * lk;
@@ -764,7 +759,7 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
         store_S(sSh + 64 * MIXH_SS, sSl + 64 * MIXH_SS, k, vs1[k]);
     }
     // Y = relu(LN(.)) -> B fragments of the second product, in registers
-    mix_h8 bYh[3], bYl[3];
+    rac_h8 bYh[3], bYl[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -781,15 +776,15 @@ __global__ __launch_bounds__(256, 3) void mixing_c64_f16x3_kernel(const MixArgs 
     __syncthreads();   // S visible
 
     // ---- step 2: Z = S @ Y ---------------------------------------------------------------------------------------
-    mix_f4 acc2[8];
+    rac_f4v acc2[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-        acc2[m] = (mix_f4){0.f, 0.f, 0.f, 0.f};
+        acc2[m] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int off = (16 * m + li) * MIXH_SS + 32 * t + 8 * lk;
-            const mix_h8 ah = *reinterpret_cast<const mix_h8 *>(sSh + off);
-            const mix_h8 al = *reinterpret_cast<const mix_h8 *>(sSl + off);
+            const rac_h8 ah = *reinterpret_cast<const rac_h8 *>(sSh + off);
+            const rac_h8 al = *reinterpret_cast<const rac_h8 *>(sSl + off);
             acc2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bYh[t], acc2[m], 0, 0, 0);
             acc2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bYl[t], acc2[m], 0, 0, 0);
             acc2[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bYh[t], acc2[m], 0, 0, 0);

@@ -25,9 +25,6 @@
 #include "gather_device.h"
 
 #define MSMV_ROWS 8 /* (slot,query) rows per 256-thread workgroup: two per wave */
-#ifndef MSMV_NT_LEVEL0
-#define MSMV_NT_LEVEL0 1   /* measured on SURVEY 8d's uniform-stress set: 122 -> 112 us per launch (60 -> 65 % of the roofline) */
-#endif
 
 template <typename FT, int L, bool OUT_CL>
 __global__ __launch_bounds__(256, (L <= 4 ? 4 : 3)) void msmv_fwd_c64_kernel(const MsmvArgs a)
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(256, (L <= 4 ? 4 : 3)) void msmv_fwd_c64_kernel(con
             for (int l = 0; l < L; ++l) {
                 const rac_u4 o = *reinterpret_cast<const rac_u4 *>(e + l * lstride);
                 tw[l] = *reinterpret_cast<const rac_f4 *>(e + l * lstride + 4);
-                if (l == 0 && MSMV_NT_LEVEL0) {
+                if (l == 0) {   // level 0 through the non-temporal tap; measured on SURVEY 8d's uniform-stress set: 122 -> 112 us per launch (60 -> 65 % of the roofline)
                     v[l][0] = rac_tap<FT, 2>(rsrc[l], o.x + lane_off);
                     v[l][1] = rac_tap<FT, 2>(rsrc[l], o.y + lane_off);
                     v[l][2] = rac_tap<FT, 2>(rsrc[l], o.z + lane_off);

@@ -25,15 +25,9 @@
 // (sparsebev_sampling.py:113-120, quirk Q1).
 #include "rac_common.h"
 
-#ifndef S4D_ROWS
 #define S4D_ROWS 8 /* queries per workgroup: one prologue pass (96 keypoints at P = 12) serves 2 gather rounds per wave; measured 4 / 8 / 12 / 16 / 32: 92.7 / 88.9 / 90.3 / 94 / 107 us */
-#endif
-#ifndef S4D_LB
 #define S4D_LB 4 /* levels per load batch (see the gather loop) */
-#endif
-#ifndef S4D_WPS
 #define S4D_WPS 4 /* waves per SIMD the register allocator must allow */
-#endif
 #include "s4d_device.h"
 
 // COMPACT: a row's points with no tap inside any map (no camera sees them: about half of the points of a 3-camera rig) are
@@ -228,9 +222,7 @@ extern "C" int rac_sampling4d_fwd(const void *const *feats, const int32_t *hw, i
     // (3-cam rig: 76.8 -> 67.9 us) and costs 2.5 us where every point is live.  The caller decides from the rig's measured
     // coverage (RaCFormerTransformerDecoder.stage_metas: share of a ring of probe points some camera sees); -1 = no measurement
     // at hand: by the number of cameras.
-#ifndef S4D_COMPACT_MAX_CAMS
 #define S4D_COMPACT_MAX_CAMS 3
-#endif
     const bool use_compact = (compact < 0 ? N <= S4D_COMPACT_MAX_CAMS : compact == 1) && P <= 64;
 #define S4D_LAUNCH(FT, LL)                                                                                           \
     do {                                                                                                             \

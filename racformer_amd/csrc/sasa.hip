@@ -220,13 +220,7 @@ __device__ __forceinline__ void sasa_centres(float *scen, const float *box, cons
 // of one mask row for one tile is a 16-bit field: bit k set = key tile*16 + k is blocked for that row.  The keys past Q are
 // returned as blocked too (the padding bits of the operand are ignored), so a field of 0xffff means "no allowed key in this
 // tile" and a tile whose 16 rows all say so is skipped by the whole wave: the decision comes from the mask words alone.
-// SASA_NO_TILE_SKIP (an A/B build switch): every tile is computed; the results are the same bit for bit, a blocked pair
-// contributes an exact zero either way.
-#ifdef SASA_NO_TILE_SKIP
-#define SASA_TILE_SKIP 0
-#else
-#define SASA_TILE_SKIP 1
-#endif
+// Computing every tile instead gives the same results bit for bit: a blocked pair contributes an exact zero either way.
 
 __device__ __forceinline__ unsigned sasa_mask_field(const unsigned *mask, int ld_mask, int row, int tile, int Q)
 {
@@ -239,7 +233,7 @@ __device__ __forceinline__ unsigned sasa_mask_field(const unsigned *mask, int ld
 // wave-uniform: no lane of the wave has an allowed pair in its field(s)
 __device__ __forceinline__ bool sasa_all_blocked(unsigned field)
 {
-    return SASA_TILE_SKIP && __builtin_amdgcn_ballot_w64(field != 0xffffu) == 0;
+    return __builtin_amdgcn_ballot_w64(field != 0xffffu) == 0;
 }
 
 template <bool MASKED>

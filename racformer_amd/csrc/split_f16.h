@@ -1,10 +1,9 @@
-// split_f16.h -- what the split-precision matrix-core kernels outside the decoder step share (gfx950): the operand types of
-// v_mfma_f32_16x16x32_f16, the hi + lo split of eight scaled values, the transposed LDS fragment read with its row swizzle, and the
+// split_f16.h -- what the split-precision matrix-core kernels share beyond rac_common.h's vector types (gfx950): the quarter
+// fragment of a transposed LDS read, the hi + lo split of eight scaled values, the transposed LDS fragment read with its row swizzle, and the
 // combination of the per-image partial maxima.
 #pragma once
 #include "rac_common.h"
 
-typedef _Float16 rac_h8 __attribute__((ext_vector_type(8)));
 typedef __fp16 rac_q4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) rac_q4 *rac_lds_q4;
 

@@ -30,14 +30,8 @@
 // 102 us, every side took as long beside the other as alone).
 #include "rac_common.h"
 
-typedef _Float16 vp_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 vp_h4 __attribute__((ext_vector_type(4)));
-typedef float vp_f4 __attribute__((ext_vector_type(4)));
-
 #define VP_ROWS 32
-#ifndef VP_RING
 #define VP_RING 3                                /* raw stages in the LDS-DMA ring = stages in flight */
-#endif
 #define VP_BUF (VP_ROWS * 1024 + VP_ROWS * 4)   /* X image of a stage + its per-row output scales */
 #define VP_RAW (VP_ROWS * 256 * 4)              /* one raw stage: [256 channels][32 pixels] fp32 */
 #define VP_RAW0 (VP_BUF + 8 * VP_ROWS * 4)      /* X image (one buffer: barrier (A) of a stage comes after every wave's MFMAs of the one before), partial maxima, then the ring */
@@ -140,15 +134,12 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
     int pf_blk = b0, pf_f = 0, pf_n = 0;
     auto dma = [&](int slot) {
         const int p = pf_blk * VP_ROWS + 4 * dslot;
-        const unsigned voff = (unsigned)(((pf_f * 256 + 32 * wave + drow) * g.HW + p) * 4);
+        const unsigned voff = ((unsigned)(pf_f * 256 + 32 * wave + drow) * (unsigned)g.HW + (unsigned)p) * 4u;   // (unsigned: maps of 2 GiB and more)
         char *dst = ring + slot * VP_RAW + wave * 4096;
-#if defined(RAC_DIAGNOSTIC_BUILD) && defined(VP_EXP_NODMA)
-        if (g.HW < 0)
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(dst + i * 1024), 16,
-                                                     voff + (unsigned)(8 * i * g.HW * 4), 0, 0, 0);
+                                                     voff + (unsigned)(8 * i) * (unsigned)g.HW * 4u, 0, 0, 0);
         if (pf_n + 1 < nstages) {
             ++pf_n;
             if (++pf_f == F) {
@@ -170,21 +161,21 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
         dma(s0);
 
     // ---- this wave's weights: fragment (tile t, K step ks) = W rows 32 wave + 16t + li, chunk lk of the hi / lo half
-    vp_h8 wh[2][8], wl[2][8];
+    rac_h8 wh[2][8], wl[2][8];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const char *wp = g.w + (size_t)(32 * wave + 16 * t + li) * 1024 + lk * 16;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            wh[t][ks] = *reinterpret_cast<const vp_h8 *>(wp + ks * 128);
-            wl[t][ks] = *reinterpret_cast<const vp_h8 *>(wp + ks * 128 + 64);
+            wh[t][ks] = *reinterpret_cast<const rac_h8 *>(wp + ks * 128);
+            wl[t][ks] = *reinterpret_cast<const rac_h8 *>(wp + ks * 128 + 64);
         }
     }
     // the additive term of the block in hand (HAS_ADD: reloaded by the first stage of every block; else the bias, once)
-    vp_f4 addv[2][2];
+    rac_f4v addv[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const vp_f4 b4 = (g.bias && !HAS_ADD) ? *reinterpret_cast<const vp_f4 *>(g.bias + 32 * wave + 16 * t + 4 * lk) : (vp_f4){0.f, 0.f, 0.f, 0.f};
+        const rac_f4v b4 = (g.bias && !HAS_ADD) ? *reinterpret_cast<const rac_f4v *>(g.bias + 32 * wave + 16 * t + 4 * lk) : (rac_f4v){0.f, 0.f, 0.f, 0.f};
         addv[0][t] = b4;
         addv[1][t] = b4;
     }
@@ -212,7 +203,7 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
         // The four reads of the raw stage are inline assembly: as ordinary LDS loads hipcc cannot tell them from the OTHER slots' pending
         // LDS-DMA (run-time offsets into one LDS array: SIInsertWaitcnts then waits for every LDS-DMA in flight, i.e. for the stages
         // that have just been prefetched).  The counted wait above is what orders them behind their own stage's pieces.
-        vp_f4 xv[4];
+        rac_f4v xv[4];
         {
             const unsigned sb = (unsigned)(slot * VP_RAW);
             asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
@@ -222,7 +213,7 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
             //  is there to avoid; volatile keeps it behind the counted wait above and in front of the barrier below)
         }
         // ---- per-pixel maximum over the 256 channels: this lane's 4, the wave's 32 (lanes that differ in cs), the 8 waves (LDS)
-        vp_f4 mx;
+        rac_f4v mx;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             mx[j] = fmaxf(fmaxf(fabsf(xv[0][j]), fabsf(xv[1][j])), fmaxf(fabsf(xv[2][j]), fabsf(xv[3][j])));
@@ -232,13 +223,13 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
             for (int j = 0; j < 4; ++j)
                 mx[j] = fmaxf(mx[j], __shfl_xor(mx[j], m, 64));
         if (cs == 0)
-            *reinterpret_cast<vp_f4 *>(smax + wave * VP_ROWS + 4 * pq) = mx;
+            *reinterpret_cast<rac_f4v *>(smax + wave * VP_ROWS + 4 * pq) = mx;
         VP_STAMP(2);
         vp_barrier();                                     // (A) partial maxima visible; everyone is past the MFMAs of the stage before
         VP_STAMP(3);
 #pragma unroll
         for (int ww = 0; ww < 8; ++ww) {
-            const vp_f4 o = *reinterpret_cast<const vp_f4 *>(smax + ww * VP_ROWS + 4 * pq);
+            const rac_f4v o = *reinterpret_cast<const rac_f4v *>(smax + ww * VP_ROWS + 4 * pq);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 mx[j] = fmaxf(mx[j], o[j]);
@@ -257,7 +248,7 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int r = 4 * pq + j;
-            vp_h4 hi, lo;
+            rac_h4v hi, lo;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 _Float16 h, l;
@@ -266,8 +257,8 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
                 lo[i] = l;
             }
             char *rowp = B + r * 1024 + (cs & 1) * 8;
-            *reinterpret_cast<vp_h4 *>(rowp + (((8 * wave + (cs >> 1)) ^ (r & 15)) * 16)) = hi;
-            *reinterpret_cast<vp_h4 *>(rowp + (((8 * wave + 4 + (cs >> 1)) ^ (r & 15)) * 16)) = lo;
+            *reinterpret_cast<rac_h4v *>(rowp + (((8 * wave + (cs >> 1)) ^ (r & 15)) * 16)) = hi;
+            *reinterpret_cast<rac_h4v *>(rowp + (((8 * wave + 4 + (cs >> 1)) ^ (r & 15)) * 16)) = lo;
         }
         VP_STAMP(4);
         vp_barrier();                                     // (B) the stage's X image is complete
@@ -282,28 +273,25 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
-                    addv[j][t] = *reinterpret_cast<const vp_f4 *>(g.add + (size_t)(p0 + 16 * j + li) * 256 + 32 * wave + 16 * t + 4 * lk);
+                    addv[j][t] = *reinterpret_cast<const rac_f4v *>(g.add + (size_t)(p0 + 16 * j + li) * 256 + 32 * wave + 16 * t + 4 * lk);
         }
         dma(slot);
         __builtin_amdgcn_sched_barrier(0);
         VP_STAMP(6);
 
-        vp_f4 acc[2][2];
+        rac_f4v acc[2][2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                acc[t][j] = (vp_f4){0.f, 0.f, 0.f, 0.f};
-#if defined(RAC_DIAGNOSTIC_BUILD) && defined(VP_EXP_NOMFMA)
-        if (g.HW < 0)
-#endif
+                acc[t][j] = (rac_f4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const char *rowp = B + (16 * j + li) * 1024;
-                const vp_h8 xh = *reinterpret_cast<const vp_h8 *>(rowp + (((8 * ks + lk) ^ li) * 16));
-                const vp_h8 xl = *reinterpret_cast<const vp_h8 *>(rowp + (((8 * ks + 4 + lk) ^ li) * 16));
+                const rac_h8 xh = *reinterpret_cast<const rac_h8 *>(rowp + (((8 * ks + lk) ^ li) * 16));
+                const rac_h8 xl = *reinterpret_cast<const rac_h8 *>(rowp + (((8 * ks + 4 + lk) ^ li) * 16));
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t][ks], xh, acc[t][j], 0, 0, 0);
@@ -317,14 +305,14 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
         // ---- epilogue: C/D layout col = li (pixel), rows 4 lk + r = four consecutive features: one 16-byte store
         if constexpr (QOUT) {
             // pmax [8 waves][32 pixels]
-            vp_f4 v[2][2];
+            rac_f4v v[2][2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const float a = salpha[16 * j + li];
                 unsigned bm = 0u;
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    v[j][t] = __builtin_elementwise_fma(acc[t][j], (vp_f4){a, a, a, a}, addv[j][t]);
+                    v[j][t] = __builtin_elementwise_fma(acc[t][j], (rac_f4v){a, a, a, a}, addv[j][t]);
                     bm = max(bm, rac_absbits4(v[j][t][0], v[j][t][1], v[j][t][2], v[j][t][3]));
                 }
                 bm = max(bm, (unsigned)__shfl_xor((int)bm, 16, 64));
@@ -357,10 +345,7 @@ __device__ __forceinline__ void value_proj_body(const ValueProjArgs &g, char *__
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const int n = 32 * wave + 16 * t + 4 * lk;
-#if defined(RAC_DIAGNOSTIC_BUILD) && defined(VP_EXP_NOSTORE)
-                    if (acc[t][j][0] == 123.456f)
-#endif
-                    *reinterpret_cast<vp_f4 *>(g.out + (size_t)(gp + r) * 256 + n) = __builtin_elementwise_fma(acc[t][j], (vp_f4){a, a, a, a}, addv[j][t]);
+                    *reinterpret_cast<rac_f4v *>(g.out + (size_t)(gp + r) * 256 + n) = __builtin_elementwise_fma(acc[t][j], (rac_f4v){a, a, a, a}, addv[j][t]);
                 }
             }
         }

@@ -1,8 +1,11 @@
 """rac_conv_direct_fwd / rac_upsample2x_image_fwd / rac_conv3x3_temporal_fwd (round 5: the ConvGRU branch of
 RadarBEVTemporalEncoder, models/racformer_transformer.py:645-656, 674-720, on own kernels) against float64 convolutions and the
-torch modules they replace.  The image, f32 and GRU modes of the direct convolution, both strides, several of the instantiated chunk
-counts (the chunk count is a template parameter: every K loop is straight-line code, csrc/conv_direct.hip, rac_conv_direct_fwd), ragged
-pixel tiles, frame maps; the GRU update against ConvGRUCell; the fold of the constant hidden half against the explicit image.
+torch modules they replace.  The kernel (csrc/conv_direct.hip) stages the weights of a workgroup's output-channel block through an LDS
+double buffer, one 32-channel chunk per buffer with a workgroup barrier per chunk, and loads the pixels per lane through a register
+ring; the chunk count is a template parameter, instantiated for 2 / 3 / 8 chunks (stride 2), 2 (stride-1 image modes), 1 / 2 / 4 (f32
+mode) and 0 / 2 (GRU mode).  A frame map has no frame count: keeping every mapped frame inside its buffer is the caller's
+responsibility, and the maps used here do.  Covered: the image, f32 and GRU modes, both strides, several of the instantiated chunk counts,
+ragged pixel tiles, frame maps; the GRU update against ConvGRUCell; the fold of the constant hidden half against the explicit image.
 Every instantiation, element by element against float64: tests/test_conv_fwd_f64_gpu.py."""
 import math
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Experiment: the launches of the ConvGRU branch (rac_conv_direct_fwd) in isolation at f8 shapes, HIP-event timed, each alone and the
-whole chain back to back.  RAC_CD_DEPTH selects the ring depth of an experiment build."""
+whole chain back to back."""
 import os
 import statistics
 import sys
@@ -82,7 +82,6 @@ def timed(fn, reps=10, inner=20):
 
 chain()
 torch.cuda.synchronize()
-print("depth", os.environ.get("RAC_CD_DEPTH", "3"))
 for name, fn in (("s2", k_s2), ("xpart", k_xpart), ("step0", lambda: k_step(0)), ("step1", lambda: k_step(1)), ("upsample", k_ups),
                  ("upconv", k_upconv), ("chain", chain)):
     print(f"{name:10s} {timed(fn):8.1f} us")

@@ -6,15 +6,13 @@ Q = 1300 (40 boxes) and Q = 1700 (80 boxes)):
   rac_sasa_bwd_mask     dq, dk, dv, dtau under the mask
   torch fwd + bwd       forward_unfused's core (cdist mask, indexed -inf fill, QK^T, softmax, AV on [1,8,Q,Q]) and its autograd
                         backward: the route a masked call took before the masked kernels existed
-  no tile skip          the two masked kernels from a library built with -DSASA_NO_TILE_SKIP (``--noskip-lib``), if given
 After a warm-up the two sides of a pair run in alternating batches of launches, each batch between two events, until each has
 at least --window-ms of timed launches; reported per launch: median, mean and minimum over the batches.  Peak memory
 (torch.cuda.max_memory_allocated over one forward + backward, above what was allocated before it) is recorded for both routes.
 
-    python tools/sasa_mask_timing.py [--out profiles/sasa_mask_f8.json] [--noskip-lib path/to/libracformer_hip_noskip.so]
+    python tools/sasa_mask_timing.py [--out profiles/sasa_mask_f8.json]
 """
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -27,7 +25,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from msmv_v2_timing import summary, time_pair  # noqa: E402
-from racformer_amd import _lib  # noqa: E402
 from racformer_amd import synthetic as syn  # noqa: E402
 from racformer_amd.bbox_utils import decode_bbox, theta_d2xy_coods  # noqa: E402
 from racformer_amd.fused import box_prep, pack_attn_mask, sasa_backward, sasa_fused  # noqa: E402
@@ -49,7 +46,7 @@ def peak_mb(fn):
     return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 2)
 
 
-def one_shape(single, args, noskip):
+def one_shape(single, args):
     dev = "cuda:0"
     B, H, d, groups, matching = 1, 8, 32, 10, 900
     Q, E = groups * single + matching, H * d
@@ -108,27 +105,6 @@ def one_shape(single, args, noskip):
     rec["fused_forward_plus_backward"], rec["torch_unfused_forward_plus_backward"] = summary(res["a"], total["a"]), summary(res["b"], total["b"])
     res, total = time_pair(bwd, fwd, args.batch, args.window_ms, args.warmup)
     rec["rac_sasa_bwd_mask"] = summary(res["a"], total["a"])
-    if noskip is not None:
-        pc = (ctypes.c_float * 6)(*syn.PC_RANGE)
-        P_, ld, w = _lib.ptr, lin.stride(1), pk.bits.shape[1]
-        o2, l2, g2 = torch.empty_like(out), torch.empty_like(lse), torch.empty_like(lin)
-
-        def fwd_noskip():
-            rc = noskip.rac_sasa_fwd_mask(P_(qkv), P_(tau), P_(qb), P_(table), P_(o2), P_(l2), ld, ld, B, Q, H, d, pc, _lib.stream_ptr(),
-                                          P_(pk.bits), w)
-            assert rc == 0
-
-        def bwd_noskip():
-            rc = noskip.rac_sasa_bwd_mask(P_(qkv), P_(tau), P_(qb), P_(table), P_(out), P_(lse), P_(gout), P_(g2[..., :3 * E]),
-                                          P_(g2[..., 3 * E:]), ld, ld, ld, ld, B, Q, H, d, pc, _lib.stream_ptr(), P_(pk.bits), w)
-            assert rc == 0
-
-        res, total = time_pair(fwd, fwd_noskip, args.batch, args.window_ms, args.warmup)
-        rec["rac_sasa_fwd_mask_beside_noskip"], rec["rac_sasa_fwd_mask_no_tile_skip"] = summary(res["a"], total["a"]), summary(res["b"], total["b"])
-        res, total = time_pair(bwd, bwd_noskip, args.batch, args.window_ms, args.warmup)
-        rec["rac_sasa_bwd_mask_beside_noskip"], rec["rac_sasa_bwd_mask_no_tile_skip"] = summary(res["a"], total["a"]), summary(res["b"], total["b"])
-        torch.cuda.synchronize()
-        rec["no_tile_skip_bit_identical"] = bool(torch.equal(o2, out) and torch.equal(l2, lse) and torch.equal(g2, grad_lin))
     rec["peak_mb_fused_forward_plus_backward"] = peak_mb(fused_step)
     rec["peak_mb_torch_forward_plus_backward"] = peak_mb(torch_step)
     rec["torch_over_fused_step_median"] = round(rec["torch_unfused_forward_plus_backward"]["median_us"] / rec["fused_forward_plus_backward"]["median_us"], 2)
@@ -138,25 +114,18 @@ def one_shape(single, args, noskip):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
-    ap.add_argument("--noskip-lib", default="")
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--window-ms", type=float, default=400.0)
     ap.add_argument("--warmup", type=int, default=10)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
-    noskip = None
-    if args.noskip_lib:
-        noskip = ctypes.CDLL(args.noskip_lib)
-        for name in ("rac_sasa_fwd_mask", "rac_sasa_bwd_mask"):
-            fn = getattr(noskip, name)
-            fn.restype, fn.argtypes = _lib.SIGNATURES[name]
     rec = {"what": "masked SASA core at the query-denoising shapes: rac_sasa_fwd_mask (lse written), rac_sasa_bwd_mask, their sum, and "
                    "forward_unfused's core with torch autograd; alternating batches of launches between device events "
                    "(tools/sasa_mask_timing.py)",
            "batch": args.batch, "warmup_launches_each": args.warmup, "window_ms": args.window_ms,
-           "device": torch.cuda.get_device_name(0), "no_tile_skip_library": bool(noskip)}
+           "device": torch.cuda.get_device_name(0)}
     for single in (40, 80):
-        rec[f"Q{10 * single + 900}"] = one_shape(single, args, noskip)
+        rec[f"Q{10 * single + 900}"] = one_shape(single, args)
     text = json.dumps(rec, indent=1)
     print(text)
     if args.out:

@@ -79,6 +79,8 @@
  *                        norm_eval=True: the stem and layer1 need no backward, the BatchNorms stay folded)
  *   rac_pillar_train_fwd / rac_pillar_train_bwd / rac_bn_train_* <- extract_pts_feat on frame 0 in training mode under autograd
  *                        (models/racformer.py:316-331): the PFN layer and radar_bev_conv on batch statistics, forward and backward
+ *   rac_image_aug_fwd <- the image preparation of extract_feat in a training step: GpuPhotoMetricDistortion, img_norm_cfg, pad_multiple
+ *                        and GridMask (models/utils.py:8-45, :104-120, :219-305; models/racformer.py:108-109, :198-224)
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -89,7 +91,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 32
+#define RAC_ABI_VERSION 33
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1011,6 +1013,25 @@ int rac_lss_depth_loss_fwd(const float *logits, const int32_t *labels, float *pa
                            float *loss, float *scale, int BN, int D, int hw, float alpha, float gamma, float weight, void *stream);
 int rac_lss_depth_loss_bwd(const float *grad_unit, const float *scale, const float *grad_loss, float *grad_logits, int64_t n,
                            void *stream);
+
+/* ---- Image preparation of a training step (models/racformer.py:198-224, :108-109; models/utils.py:8-45, :219-305) ----------------
+ * rac_image_aug_fwd: img [n, 3, H, W] f32 (device, the loader's BGR image) -> out [n, 3, Hp, Wp] f32 (device), Hp >= H, Wp >= W, in
+ *   one launch; img is only read.  Per pixel, float32 with the reference's operations one by one (IEEE division, no contraction):
+ *     working R, G, B = input channels 2, 1, 0
+ *     where the image's table row has colour != 0 (GpuPhotoMetricDistortion): + delta; * alpha0; rgb_to_hsv (/255, eps 1e-8, deltac == 0
+ *       -> 1, hue from the first maximal channel, (h / 6) floor-mod 1, * 360); s * sat; h + hue, then h - 360 where h > 360, then
+ *       h + 360 where h < 0; hsv_to_rgb (floor(6h) floor-mod 6, the 18-entry table, * 255); * alpha1.  No clipping.
+ *     output channel k = working[map[k]]: the random channel permutation, the flip back to BGR and to_rgb folded into one map
+ *     (x - mean[k]) / std[k] unless mean and std are NULL
+ *     0 at pixels outside the grid mask's bands (GridMask keeps the bands and zeroes the rest) and in the pad rows and columns
+ *   table: device f32 [n][9] = colour, delta, alpha0, sat, hue, alpha1, map[0], map[1], map[2] (the map as 0.0 / 1.0 / 2.0).
+ *   mean, std: HOST pointers to 3 floats each, or both NULL.
+ *   grid mask: grid_d == 0 for none; else the four integers GridMask draws and derives (d >= 2, 1 <= l < d, 0 <= st_h, st_w < d) on
+ *   the canvas int(1.5 Hp) x int(1.5 Wp) with the centre crop; no mask tensor is built.
+ *   A lane owns four pixels of a row: 16-byte loads and stores where W % 4 == 0, Wp % 4 == 0 and both pointers are 16-byte aligned,
+ *   scalar accesses otherwise.  No atomics, nothing read back: capturable, two runs give the same bits. */
+int rac_image_aug_fwd(const float *img, const float *table, float *out, int n, int H, int W, int Hp, int Wp, const float *mean,
+                      const float *stdv, int grid_d, int grid_l, int grid_st_h, int grid_st_w, void *stream);
 
 /* ---- Radar pillar encoder: point clouds to the BEV canvas (models/racformer.py:130-177 extract_pts_feat / radar_voxelize; mmcv 1.6.0
  * Voxelization (hard), mmdet3d 1.0.0rc6 PillarFeatureNet and PointPillarsScatter; configs/racformer_r50_nuimg_704x256_f8.py:122-139) ----

@@ -106,6 +106,7 @@ SIGNATURES = {
     "rac_lss_prior_bwd": (_i, [_vp] * 5 + [_i] * 5 + [_vp]),
     "rac_lss_depth_loss_fwd": (_i, [_vp] * 7 + [_i] * 3 + [_f] * 3 + [_vp]),
     "rac_lss_depth_loss_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
+    "rac_image_aug_fwd": (_i, [_vp] * 3 + [_i] * 5 + [_vp, _vp] + [_i] * 4 + [_vp]),
     "rac_pillar_voxelize_fwd": (_i, [_vp] * 8 + [_i] * 3 + [_f] * 6 + [_i] * 5 + [_vp]),
     "rac_pillar_encode_fwd": (_i, [_vp] * 6 + [_f, _f, _vp, _vp, _vp] + [_i] * 5 + [_f] * 6 + [_i, _i, _vp]),
     "rac_pillar_train_fwd": (_i, [_vp] * 16 + [_i] * 5 + [_f] * 8 + [_i, _i, _vp]),

@@ -1,4 +1,4 @@
-"""The detector that joins the parts: ``RaCFormer`` of the reference's models/racformer.py for inference -- images, radar clouds and the
+"""The detector that joins the parts: ``RaCFormer`` of the reference's models/racformer.py -- images, radar clouds and the
 radar depth / RCS maps to boxes, offline (``simple_test_offline``: all T frames of a sample through the front end) and streaming
 (``simple_test_online``: only the frames the memory does not hold yet).
 
@@ -28,9 +28,26 @@ stay put; from the second call on these buffers are the ``inputs`` of a ``graph.
 step is: the front end on one frame, one slot copy per kind, one gather launch, ``CapturedStep.replay(img_metas)``.  On CPU tensors the
 same bookkeeping runs with ``torch.index_select``.
 
-Training is out of scope: ``forward(return_loss=True)`` and ``forward_train`` raise ``NotImplementedError`` (the radar branch refuses
-training-mode BatchNorm), and the training branches of ``extract_feat`` (``stop_prev_grad``, ``self.training``, the colour augmentation,
-GridMask -- which returns its input outside training) are not built."""
+Training (opt-in: ``det.fused_grad = True`` and ``det.train()``; off, ``forward(return_loss=True)``, ``forward_train`` and
+``extract_feat`` in training mode raise ``TRAINING_MESSAGE`` as before).  Setting the switch sets ``fused_grad`` on ``img_backbone``,
+``img_neck``, ``img_lss_neck`` and the radar encoder; ``AdaptiveMixing.fused_linear_grad`` stays the user's choice.
+``extract_feat`` in training mode is :179-348 with ``stop_prev_grad == 0``: the images of all B*T*N views go through ONE launch
+(``image_aug.prepare_images`` -> ``rac_image_aug_fwd``: ``color_aug`` where ``data_aug['img_color_aug']``, the img_norm_cfg step, the zero
+padding, ``grid_mask`` while ``use_grid_mask``; numpy's global generator is drawn from exactly as the reference draws), the stem runs
+with ``input_norm`` bypassed, backbone and necks run under autograd on the plain pyramid layout (``pregrouped`` is off for the call: the
+decoder's regroup has a backward, ``forward_pregrouped`` has none); frame 0's radar branch and view transformer run in training mode
+under autograd (batch statistics, running statistics updated once, ASPP's dropout live; the library's convolutions of DepthNet's torch
+route on their deterministic algorithms, ``library_deterministic``, so that a seeded forward repeats bit for bit), frames 1 .. T-1 in
+eval mode under ``no_grad`` on the statistics frame 0 has just updated.  Departure: only these two branches are toggled, where the reference calls ``self.eval()`` /
+``self.train()`` on the whole detector and so un-freezes whatever the user had put into ``eval()``.  ``self.training and
+stop_prev_grad > 0`` raises ``NotImplementedError``: the reference's branch calls the view transformer with three arguments and hands
+all frames' clouds to ``extract_pts_feat`` -- it cannot run.  ``forward_train`` (:400-441, ``forward_pts_train`` :351-382) writes the
+ground truth into the metas, runs the head in training mode and returns ``loss_depth`` plus the head's losses.  On CPU tensors every
+part takes its torch route up to the decoder, which has none: the loss half is device-only, as inference is.  A training step empties
+the streaming memory (its frames were computed on other weights); after ``train()`` or ``load_state_dict`` the next streaming call
+compares the head's weights with those its captured plan was made on, once, and drops the plan if they differ (a steady streaming
+step does not look at the weights; after editing weights in place in eval mode, call ``reset_memory()``).  ``with_cp`` is accepted and without effect; data-parallel training and an optimiser loop are not here."""
+import contextlib
 from collections import OrderedDict
 
 import torch
@@ -38,14 +55,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .head import RaCFormer_head
+from .image_aug import GpuPhotoMetricDistortion, GridMask, prepare_images
 from .lss_depth import LSSViewTransformerBEVDepth_racformer
 from .necks import FPN, CustomFPN
 from .radar_pillars import RadarPillarEncoder
 from .resnet import ResNet, apply_input_norm
 
 MEMORY_KEYS = 16        # the reference evicts while its queue holds this many keys (:551)
-TRAINING_MESSAGE = ("racformer_amd.RaCFormer is built for inference: the radar branch (RadarPillarEncoder) refuses training-mode "
-                    "BatchNorm, so forward(return_loss=True) / forward_train are not implemented")
+TRAINING_MESSAGE = ("racformer_amd.RaCFormer is built for inference unless its fused_grad switch is set: without it the radar branch "
+                    "(RadarPillarEncoder) refuses training-mode BatchNorm, so forward(return_loss=True) / forward_train / extract_feat in "
+                    "training mode are not implemented; set det.fused_grad = True (and det.train()) to opt in")
 
 
 def _cfg(cfg, expected, what):
@@ -74,6 +93,24 @@ def pad_multiple(inputs, img_metas, size_divisor=32):
 def bbox3d2result(bboxes, scores, labels):
     """mmdet3d.core.bbox3d2result: the three results on the host.  ``boxes_3d`` is the plain [k, 9] tensor of ``get_bboxes``."""
     return dict(boxes_3d=bboxes.to('cpu'), scores_3d=scores.cpu(), labels_3d=labels.cpu())
+
+
+@contextlib.contextmanager
+def library_deterministic(on=True):
+    """The library's convolutions on their deterministic algorithms for the block (``torch.backends.cudnn.deterministic``, restored
+    afterwards).  ``DepthNet`` in training mode takes its torch route, i.e. the library's convolutions, and by default those do not
+    give the same bits twice on this device (measured: the first 3x3 convolution of ``reduce_conv`` already differs run to run; with
+    the flag set every module's output repeats).  The training step wraps frame 0's forward in this, so that a seeded forward is
+    reproducible; the backward runs outside it."""
+    if not on:
+        yield
+        return
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = was
 
 
 class FrameMemory:
@@ -106,7 +143,7 @@ class FrameMemory:
 
 
 class RaCFormer(nn.Module):
-    """models/racformer.py:18-557 for inference (module docstring)."""
+    """models/racformer.py:18-557: inference, and the training step behind the ``fused_grad`` switch (module docstring)."""
 
     def __init__(self, data_aug=None, stop_prev_grad=False, pts_voxel_layer=None, pts_voxel_encoder=None, pts_middle_encoder=None,
                  pts_fusion_layer=None, img_backbone=None, pts_backbone=None, img_neck=None, num_lss_fpn=2, dep_downsample=16,
@@ -128,6 +165,13 @@ class RaCFormer(nn.Module):
         self.pre_process = False
         self.pregrouped = True      # return the pyramid in the sampling layout where the neck's HIP route holds (module docstring)
         self.capture = True         # streaming on the device: replay a captured decoder step from the second call on
+        # training: frame 0's forward with the library's convolutions on their deterministic algorithms (``library_deterministic``).  The
+        # flag is process-wide while it is set: switch this off where other threads run library convolutions of their own, or where
+        # the library's default algorithm matters more than a forward that repeats bit for bit
+        self.deterministic_forward = True
+        self.color_aug = GpuPhotoMetricDistortion()
+        self.grid_mask = GridMask(ratio=0.5, prob=0.7)
+        self.use_grid_mask = True
 
         self.img_backbone = img_backbone if isinstance(img_backbone, nn.Module) else ResNet(**_cfg(img_backbone, "ResNet", "img_backbone"))
         if data_aug is not None and 'img_norm_cfg' in data_aug:
@@ -176,8 +220,23 @@ class RaCFormer(nn.Module):
         self.radar_middle_encoder = enc.radar_middle_encoder
         self.radar_bev_conv = enc.radar_bev_conv
 
+        self._fused_grad = False
+        self._weights_touched = False
         self.reset_memory()
         self.eval()
+
+    # ------------------------------------------------------------------------------------------------ the training switch
+    @property
+    def fused_grad(self):
+        """Opt-in to training (module docstring).  Setting it sets ``fused_grad`` on the backbone, both necks and the radar encoder."""
+        return self._fused_grad
+
+    @fused_grad.setter
+    def fused_grad(self, on):
+        self._fused_grad = bool(on)
+        for part in (self.img_backbone, self.img_neck, self.img_lss_neck, self.radar_encoder):
+            if part is not None and hasattr(part, "fused_grad"):
+                part.fused_grad = bool(on)
 
     # ------------------------------------------------------------------------------------------------ properties of the reference
     @property
@@ -192,7 +251,13 @@ class RaCFormer(nn.Module):
     def with_pts_bbox(self):
         return self.pts_bbox_head is not None
 
+    def load_state_dict(self, *args, **kwargs):
+        self._weights_touched = True
+        return super().load_state_dict(*args, **kwargs)
+
     def train(self, mode=True):
+        if mode:
+            self._weights_touched = True        # (weights may move from here on: the streaming route re-checks its captured plan)
         super().train(mode)
         self.radar_encoder.training = mode
         return self
@@ -237,9 +302,105 @@ class RaCFormer(nn.Module):
         radar_rcs [B, T*N, (1,) H, W] -> (img_feats: per level [B, T*N, C, H_i, W_i] -- or [B*T*G, N, H_i, W_i, 64], pregrouped --,
         all_bev_feats [B, T, C, Y, X], radar_bev_feats [B, T, 256, Y, X], depth of frame 0 [B*N, D, h, w])."""
         if self.training:
-            raise NotImplementedError(TRAINING_MESSAGE)
+            if not self.fused_grad:
+                raise NotImplementedError(TRAINING_MESSAGE)
+            if self.stop_prev_grad > 0:
+                raise NotImplementedError("RaCFormer: stop_prev_grad > 0 in training mode is not implemented (the reference's branch cannot "
+                                          "run: it calls the view transformer with three arguments and hands all frames' clouds to "
+                                          "extract_pts_feat)")
+            return self._extract_feat_train(img, radar_points, radar_depth, radar_rcs, img_metas)
         with torch.no_grad():
             return self._extract_feat(img, radar_points, radar_depth, radar_rcs, img_metas)
+
+    @contextlib.contextmanager
+    def _branches_eval(self):
+        """The radar branch and the view transformer in eval mode for the block, their modes restored afterwards (frames 1 .. T-1 of a
+        training step; nothing else of the detector is touched)."""
+        enc = self.radar_encoder
+        roots = [self.img_lss_view_transformer, self.radar_voxel_layer, self.radar_voxel_encoder, self.radar_middle_encoder, self.radar_bev_conv]
+        was = [(m, m.training) for root in roots if isinstance(root, nn.Module) for m in root.modules()] + [(enc, enc.training)]
+        for m, _ in was:
+            m.training = False
+        try:
+            yield
+        finally:
+            for m, t in was:
+                m.training = t
+
+    def _extract_feat_train(self, img, radar_points, radar_depth, radar_rcs, img_metas):
+        """The training branch of :179-348 (``stop_prev_grad == 0``; module docstring).  Returns the reference's four results with
+        their graph: the pyramid [B, T*N, C, H_i, W_i] per level, all_bev_feats [B, T, C, Y, X], radar_bev_feats, frame 0's depth logits."""
+        if isinstance(img, list):
+            img = torch.stack(img, dim=0)
+        assert img.dim() == 5
+        B, NT, C, H, W = img.size()
+        N = self.num_cams
+        T = NT // N
+        img = img.reshape(B * NT, C, H, W).float()
+        radar_depth = radar_depth.reshape(B * NT, 1, H, W).float()
+        radar_rcs = radar_rcs.reshape(B * NT, 1, H, W)
+
+        # the numpy draws in the reference's order: the colour distortion (:199-200), then GridMask on the padded image (:108-109)
+        aug = self.data_aug if self.data_aug is not None else {}
+        photo = self.color_aug.draw(B * NT) if aug.get('img_color_aug') else None
+        div = None
+        if self.data_aug is not None:
+            for b in range(B):
+                img_shape = (H, W, C)
+                img_metas[b]['img_shape'] = [img_shape for _ in range(NT)]
+                img_metas[b]['ori_shape'] = [img_shape for _ in range(NT)]
+            if 'img_pad_cfg' in self.data_aug:
+                div = self.data_aug['img_pad_cfg']['size_divisor']
+                radar_depth = pad_multiple(radar_depth, img_metas, size_divisor=div)       # (rewrites img_shape / pad_shape of the metas)
+                radar_rcs = pad_multiple(radar_rcs, img_metas, size_divisor=div)
+        Hp, Wp = radar_depth.shape[-2:]
+        grid = self.grid_mask.draw(Hp) if self.use_grid_mask else None
+        keep_norm = self.img_backbone.input_norm
+        img = prepare_images(img, photo, keep_norm, div, grid)          # one launch on the device: normalised, padded, masked
+        H, W = img.shape[-2:]
+        radar_depth = radar_depth.reshape(B, N, T, H, W)
+        radar_rcs = radar_rcs.reshape(B, N, T, H, W)
+        input_shape = img.shape[-2:]
+        for img_meta in img_metas:
+            img_meta.update(input_shape=input_shape)
+
+        keep_pre = self.pregrouped
+        try:
+            self.img_backbone.input_norm, self.pregrouped = None, False
+            img_feats, img_lss_feats = self.extract_img_feat(img.contiguous())
+        finally:
+            self.img_backbone.input_norm, self.pregrouped = keep_norm, keep_pre
+        self.pts_bbox_head.transformer.decoder.pregrouped = False
+        _, C_lss, h, w = img_lss_feats.shape
+        img_lss_feats = img_lss_feats.view(B, NT, C_lss, h, w)
+        mlp_input = self.img_lss_view_transformer.get_mlp_input(img_metas)
+
+        def frame(i):
+            img_meta_b = [dict(lidar2img=img_metas[b]['lidar2img'][i * N:(i + 1) * N],
+                               img_shape=img_metas[b]['img_shape'][i * N:(i + 1) * N]) for b in range(B)]
+            pts_feats = self.extract_pts_feat(radar_points=radar_points[i])
+            bev_feat, depth = self.img_lss_view_transformer(img_lss_feats[:, i * N:(i + 1) * N], radar_depth[:, :, i], radar_rcs[:, :, i],
+                                                            img_meta_b, mlp_input[:, i * N:(i + 1) * N])
+            return pts_feats, bev_feat, depth
+
+        radar_bev_feats, all_bev_feats, all_depths = [], [], []
+        for i in range(T):
+            if i == 0:
+                with library_deterministic(self.deterministic_forward):     # (DepthNet's torch route: a seeded forward repeats)
+                    pts_feats, bev_feat, depth = frame(i)
+            else:
+                with torch.no_grad(), self._branches_eval():
+                    pts_feats, bev_feat, depth = frame(i)
+            all_bev_feats.append(bev_feat)
+            all_depths.append(depth)
+            radar_bev_feats.append(pts_feats)
+        all_bev_feats = torch.stack(all_bev_feats, dim=1)
+        radar_bev_feats = torch.stack(radar_bev_feats, dim=1)
+        img_feats_reshaped = []
+        for img_feat in img_feats:
+            BN, C, H, W = img_feat.size()
+            img_feats_reshaped.append(img_feat.view(B, int(BN / B), C, H, W))
+        return img_feats_reshaped, all_bev_feats, radar_bev_feats, all_depths[0]
 
     def _extract_feat(self, img, radar_points, radar_depth, radar_rcs, img_metas):
         if isinstance(img, list):
@@ -314,8 +475,37 @@ class RaCFormer(nn.Module):
             return self.forward_train(**kwargs)
         return self.forward_test(**kwargs)
 
-    def forward_train(self, *args, **kwargs):
-        raise NotImplementedError(TRAINING_MESSAGE)
+    def forward_pts_train(self, pts_feats, bev_feats, radar_bev_feats, depth, gt_bboxes_3d, gt_labels_3d, gt_depth, img_metas,
+                          gt_bboxes_ignore=None):
+        """:351-382 -> ``loss_depth`` and the head's losses"""
+        vt = self.img_lss_view_transformer
+        ds = vt.downsample
+        if gt_depth.dim() != 4 or gt_depth.shape[0] * gt_depth.shape[1] != depth.shape[0] or gt_depth.shape[2] % ds or gt_depth.shape[3] % ds \
+                or (gt_depth.shape[2] // ds, gt_depth.shape[3] // ds) != tuple(depth.shape[2:]):
+            raise ValueError(f"RaCFormer.forward_train: gt_depth {tuple(gt_depth.shape)} pooled by {ds} does not give the depth logits' "
+                             f"shape {tuple(depth.shape)} (the radar maps are padded inside extract_feat, gt_depth is not: hand it "
+                             "over at the padded size)")
+        outs = self.pts_bbox_head(pts_feats, bev_feats, radar_bev_feats, img_metas)
+        loss_depth = vt.get_depth_loss(gt_depth, depth)
+        losses = dict(loss_depth=loss_depth)
+        losses.update(self.pts_bbox_head.loss(gt_bboxes_3d, gt_labels_3d, outs))
+        return losses
+
+    def forward_train(self, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_depth=None, img=None, radar_points=None,
+                      radar_depth=None, radar_rcs=None, gt_bboxes_ignore=None):
+        """:400-441: one training forward -> the dict of losses (``loss_depth``, ``loss_cls``, ``loss_bbox``, ``d{i}.*`` and, with
+        denoising queries, the ``*_dn`` keys), each a 0-dim tensor with its graph.  Needs ``fused_grad`` and ``train()``."""
+        if not self.fused_grad:
+            raise NotImplementedError(TRAINING_MESSAGE)
+        if not self.training:
+            raise RuntimeError("RaCFormer.forward_train: the detector is in eval mode; call train() first")
+        self.reset_memory()         # (frames held by the streaming memory, and a captured plan, belong to the weights before this step)
+        img_feats, bev_feats, radar_bev_feats, depth = self.extract_feat(img, radar_points, radar_depth, radar_rcs, img_metas)
+        for i in range(len(img_metas)):
+            img_metas[i]['gt_bboxes_3d'] = gt_bboxes_3d[i]
+            img_metas[i]['gt_labels_3d'] = gt_labels_3d[i]
+        return self.forward_pts_train(img_feats, bev_feats, radar_bev_feats, depth, gt_bboxes_3d, gt_labels_3d, gt_depth, img_metas,
+                                      gt_bboxes_ignore)
 
     def forward_test(self, img_metas, img=None, **kwargs):
         for var, name in [(img_metas, 'img_metas')]:
@@ -347,8 +537,11 @@ class RaCFormer(nn.Module):
         """Empties the frame memory and drops the window buffers and the captured step."""
         if getattr(self, "_plan", None) is not None:
             self._plan.close()
-        self.memory, self._window, self._plan, self._online_calls = None, None, None, 0
+        self.memory, self._window, self._plan, self._plan_sig, self._online_calls = None, None, None, None, 0
         self.stats = dict(calls=0, computed=0, served=0, total_computed=0, total_served=0)
+
+    def _head_weights_sig(self):
+        return tuple((p.data_ptr(), p._version) for p in self.pts_bbox_head.parameters())
 
     def memory_keys(self):
         return list(self.memory.slots) if self.memory is not None else []
@@ -439,9 +632,14 @@ class RaCFormer(nn.Module):
         self._online_calls += 1
         self.pts_bbox_head.transformer.decoder.pregrouped = self.memory.pregrouped
         if img.is_cuda and self.capture and self._online_calls > 1:
+            if self._plan is not None and self._weights_touched and self._plan_sig != self._head_weights_sig():
+                self._plan.close()          # (captured on other weights: its weight-derived operands are stale)
+                self._plan = None
+            self._weights_touched = False
             if self._plan is None:
                 from .graph import CapturedStep
                 self._plan = CapturedStep(self.pts_bbox_head, img_feats, lss_bev_feats, radar_bev_feat, metas, decode=False)
+                self._plan_sig = self._head_weights_sig()
             with torch.no_grad():
                 outs, _ = self._plan.replay(img_metas=metas)
                 bbox_list = self.pts_bbox_head.get_bboxes(outs, metas[0], rescale=rescale)

@@ -18,8 +18,8 @@ nothing asks for; float64 sums in fixed orders, no float atomics: two runs give 
 forward + backward of ``extract_pts_feat`` reads nothing back (re-packing a changed weight reads its absmax, and frames 1 .. T-1 of
 ``forward`` re-fold the eval route's weights on the new statistics, which reads their norms, as after any parameter change).
 No pillar at all: zero canvas, PFN statistics untouched, zero PFN gradients.  CPU tensors and ``fused=False`` take the torch
-modules in training mode under autograd (the comparator).  Not here: ``RaCFormer.forward_train`` (detector.py keeps its
-``TRAINING_MESSAGE``; this is what unblocks it), gradients to the points (voxelization is no_grad in the reference too).
+modules in training mode under autograd (the comparator).  ``RaCFormer.forward_train`` (detector.py) drives this route: setting the
+detector's ``fused_grad`` sets this one.  Not here: gradients to the points (voxelization is no_grad in the reference too).
 
 mmcv and mmdet3d are not importable here: the semantics below restate their documented behaviour (mmcv 1.6.0, mmdet3d 1.0.0rc6)
 under the f8 configuration.  Three quirks of the reference are KEPT:

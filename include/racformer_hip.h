@@ -81,6 +81,8 @@
  *                        (models/racformer.py:316-331): the PFN layer and radar_bev_conv on batch statistics, forward and backward
  *   rac_image_aug_fwd <- the image preparation of extract_feat in a training step: GpuPhotoMetricDistortion, img_norm_cfg, pad_multiple
  *                        and GridMask (models/utils.py:8-45, :104-120, :219-305; models/racformer.py:108-109, :198-224)
+ *   rac_adamw_step    <- the optimizer and grad_clip of the training recipe (AdamW through mmcv's optimizer hook,
+ *                        configs/racformer_r50_nuimg_704x256_f8.py:282-296): clip_grad_norm_ + torch.optim.AdamW.step
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -91,7 +93,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 33
+#define RAC_ABI_VERSION 34
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1296,6 +1298,64 @@ int rac_resnet_relu_bwd(const float *y, const float *a, const float *b, float *o
  * multiple of 16, a misaligned pointer, a slot outside [0, n_slots), n_tensors or T out of range. */
 int rac_frames_gather(int n_tensors, const void *const *rings, void *const *outs, const int64_t *frame_bytes, const int32_t *slots,
                       int T, int n_slots, void *stream);
+
+/* The training step's parameter update (csrc/optimizer.hip; racformer_amd/optim.py, FusedAdamW): torch.optim.AdamW (amsgrad=False,
+ * maximize=False) after clip_grad_norm_(norm_type=2) over a list of float32 tensors, in three launches on `stream` -- no atomics, no
+ * grid-wide barrier, no read-back, no allocation: capturable, and bitwise reproducible wherever the tensors lie.
+ *
+ * A CHUNK is RAC_OPT_CHUNK consecutive elements of one tensor (a tensor's last chunk is short; no chunk spans two tensors).  The
+ * constant is part of the definition of the norm's summation order: per chunk a fixed tree in float64 (squares of float32 are exact
+ * there), then the chunks' partial sums in index order in a fixed tree.  Neither depends on the grid, the device or the alignment.
+ *   tensors  : DEVICE [n_tensors] rac_opt_tensor -- the tensors that take part in this step: p (updated), g (read only, left
+ *              unclipped), m / v (exp_avg / exp_avg_sq, updated), numel >= 1, and `row`, the tensor's row in hyper / steps / scalars
+ *              (rows are distinct; a tensor keeps its row from step to step whether or not it takes part).  Pointers are 4-byte
+ *              aligned; accesses are 16 bytes wide where a pointer is 16-byte aligned, scalar otherwise and at a tensor's tail
+ *   chunks   : DEVICE [n_chunks] rac_opt_chunk -- tensor index and start element (a multiple of RAC_OPT_CHUNK, below numel) of
+ *              every chunk, tensors in table order, chunks of a tensor in ascending order
+ *   hyper    : DEVICE double [rows, RAC_OPT_HYPER] -- lr, weight_decay, beta1, beta2, eps, 0 per row; read by the finish launch of
+ *              every step, so a scheduler changes a learning rate by writing here
+ *   steps    : DEVICE float [rows] -- per-tensor step counters (torch keeps them as float32 too); + 1 for the present tensors
+ *              unless the step is skipped
+ *   scalars  : DEVICE float [rows, RAC_OPT_SCALARS] -- written by the finish launch for the present tensors, each computed in
+ *              float64 and rounded once: 1 - lr wd, lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - beta1, beta2, 1 - beta2, eps, 0
+ *   partials : DEVICE double [n_chunks] scratch
+ *   record   : DEVICE rac_opt_record -- total_sq (sum of the squares of all gradients), total_norm (its root), clip_coef =
+ *              min(1, max_norm / (total_norm + 1e-6)) (1 when max_norm < 0: no clipping), skip = the total is not finite.  When
+ *              skip is set nothing else is written: no counter, no scalar, no element of p, m or v
+ *   phases   : mask of RAC_OPT_NORM | RAC_OPT_FINISH | RAC_OPT_UPDATE, the launches to enqueue (a step is RAC_OPT_ALL; single
+ *              phases are for timing)
+ * Per element (every operation rounded once, division and square root correctly rounded), with the row's scalars:
+ *     g' = g clip_coef;  p = p (1 - lr wd);  m = m + (g' - m)(1 - beta1);  v = beta2 v + ((1 - beta2) g') g'
+ *     p = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ * Departure from torch: the clip is folded into the update, g itself is not written.
+ * Refused with RAC_E_ARG before any HIP call: a null or misaligned table pointer, n_tensors < 1, n_chunks < n_tensors, phases out
+ * of range, max_norm nan.  The tables' CONTENTS are the caller's responsibility (device memory is not inspected). */
+#define RAC_OPT_CHUNK 16384
+#define RAC_OPT_HYPER 6
+#define RAC_OPT_SCALARS 8
+enum { RAC_OPT_NORM = 1, RAC_OPT_FINISH = 2, RAC_OPT_UPDATE = 4, RAC_OPT_ALL = 7 };
+typedef struct {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    int64_t numel;
+    int32_t row;
+    int32_t reserved;
+} rac_opt_tensor;
+typedef struct {
+    int64_t start;
+    int32_t tensor;
+    int32_t reserved;
+} rac_opt_chunk;
+typedef struct {
+    double total_sq;
+    double total_norm;
+    float clip_coef;
+    int32_t skip;
+} rac_opt_record;
+int rac_adamw_step(const rac_opt_tensor *tensors, int n_tensors, const rac_opt_chunk *chunks, int n_chunks, const double *hyper,
+                   float *steps, float *scalars, double *partials, rac_opt_record *record, float max_norm, int phases, void *stream);
 
 #ifdef __cplusplus
 }

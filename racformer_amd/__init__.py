@@ -15,3 +15,4 @@ from .depth_net import DepthNet  # noqa: E402,F401
 from .necks import FPN, CustomFPN  # noqa: E402,F401
 from .resnet import ResNet  # noqa: E402,F401
 from .detector import RaCFormer  # noqa: E402,F401
+from .optim import CosineAnnealingLr, FusedAdamW, build_optimizer, parse_losses, train_step  # noqa: E402,F401

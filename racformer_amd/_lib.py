@@ -125,6 +125,7 @@ SIGNATURES = {
     "rac_resnet_conv_wgrad": (_i, [_vp] * 5 + [_i] * 10 + [_vp]),
     "rac_resnet_relu_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
     "rac_frames_gather": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "rac_adamw_step": (_i, [_vp, _i, _vp, _i] + [_vp] * 5 + [_f, _i, _vp]),
 }
 
 
@@ -194,6 +195,12 @@ class ResnetDgrad(ctypes.Structure):
 
 
 RESNET_AMAX_PARTS = 64
+
+
+# rac_adamw_step (include/racformer_hip.h): RAC_OPT_CHUNK, RAC_OPT_HYPER, RAC_OPT_SCALARS and the phase mask; the device tables'
+# layouts (rac_opt_tensor, rac_opt_chunk, rac_opt_record) are numpy dtypes in racformer_amd/optim.py
+OPT_CHUNK, OPT_HYPER, OPT_SCALARS = 16384, 6, 8
+OPT_NORM, OPT_FINISH, OPT_UPDATE, OPT_ALL = 1, 2, 4, 7
 
 
 def lib():

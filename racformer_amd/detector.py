@@ -46,7 +46,8 @@ ground truth into the metas, runs the head in training mode and returns ``loss_d
 part takes its torch route up to the decoder, which has none: the loss half is device-only, as inference is.  A training step empties
 the streaming memory (its frames were computed on other weights); after ``train()`` or ``load_state_dict`` the next streaming call
 compares the head's weights with those its captured plan was made on, once, and drops the plan if they differ (a steady streaming
-step does not look at the weights; after editing weights in place in eval mode, call ``reset_memory()``).  ``with_cp`` is accepted and without effect; data-parallel training and an optimiser loop are not here."""
+step does not look at the weights; after editing weights in place in eval mode, call ``reset_memory()``).  ``with_cp`` is accepted and without effect.  The optimiser side of a step -- AdamW with the recipe's per-parameter learning rates, the gradient clip, the
+schedule, ``train_step`` -- is ``racformer_amd/optim.py`` (its update moves every parameter's ``_version``, so no pack cached here goes stale); data-parallel training is not here."""
 import contextlib
 from collections import OrderedDict
 

@@ -1057,7 +1057,9 @@ int rac_image_aug_fwd(const float *img, const float *table, float *out, int n, i
  *   distance) + PointPillarsScatter in one launch per destination set.  Per pillar: mean = sum of the rows' xyz / num_points;
  *   features [C raw | xyz - mean | x - (c_x vs_x + center_x), y and z alike] (C + 6); y = relu(wt^T f + shift) per row, wt f32 [C+6][64]
  *   and shift [64] holding the Linear with the BatchNorm1d folded in; max over the max_num_points rows, rows >= num_points taking
- *   part with relu(shift) (the reference zeroes their features and still runs them through Linear / BN / ReLU / max).
+ *   part with relu(shift) (the reference zeroes their features and still runs them through Linear / BN / ReLU / max).  A NaN among
+ *   a pillar's candidates wins the maximum, as torch.relu and torch.max have it: a NaN point feature gives NaN in that pillar's
+ *   channels (feats, canvas and image), and no other pillar changes.
  *     canvas  f32 [n_clouds][64][H][W] (PointPillarsScatter's result: canvas[cloud, :, c_y, c_x]) or NULL
  *     image   f16 [n_clouds][H+2][W+2][2][hi 32 | lo 32] activation image of rac_conv_direct_fwd or NULL, with the scale
  *             act_scale(bound_mul * (*amax) + bound_add) (amax may be NULL)
@@ -1096,7 +1098,8 @@ int rac_pillar_encode_fwd(const float *voxels, const int32_t *coors, const int32
  *     feats       f32 [n_rows][64], slots int32 [n_rows][64]: the winning value and its slot -- the FIRST maximum in slot order, -1 for a
  *                 padded slot (it comes after the real ones); 0 / -1 in rows without a pillar.  torch may pick another of several tied
  *                 slots: tied rows are identical inputs (duplicate radar returns), all padded, or both at the ReLU's zero, and in each
- *                 case every parameter gradient is the same.
+ *                 case every parameter gradient is the same.  A NaN among the candidates wins (torch.max); the slot saved for it is
+ *                 unspecified.
  *     canvas      f32 [n_clouds][64][H][W], 16-byte aligned
  *   Sums: a pillar's rows in slot order, the pillars of each of 16 contiguous row ranges (ceil(n_rows / 16) rows) ascending, the ranges
  *   ascending.  No pillar at all: canvas 0, stat 0, n_total 0, the running statistics untouched.
@@ -1156,18 +1159,21 @@ int rac_bn_train_bwd(const float *g, const float *x, const float *y, const float
  *   epilogue, in this order, each part optional (NULL):  + bias[co]  + img_bias[n][co]  + bins_table[bins[pix]][co] for
  *                  0 <= bins[pix] < n_bins (table [n_bins][Cout]: a one-hot input's 1x1 term as a column lookup)
  *                  + cls_table[cls[pix] + 1][co], row 0 for a class outside 0 .. n_cls - 1 (table [n_cls + 1][Cout])
- *                  + residual[pix][co] (channel-last rows of ld_res floats)   then ReLU if relu != 0
+ *                  + residual[pix][co] (channel-last rows of ld_res floats)   then ReLU if relu != 0; a NaN stays a NaN
+ *                  (as torch.relu keeps it)
  *   out            RAC_CS_CHANNEL_LAST: rows of ld_out floats, channels c_off .. c_off + Cout - 1 (the next layer's operand: a
  *                  concatenation is written in place, never copied);  RAC_CS_CHANNEL_FIRST: [BN][ld_out][hw], channels from c_off
  *   Any violation is RAC_E_ARG before any launch.
  *
  * rac_depthnet_gates_fwd: gates [branches][BN][C] = sigmoid(We relu(Wr (W2 relu(W1 x + b1) + b2) + br) + be) for x = mlp_input[n]
  *   (f32 [BN][9]; the BatchNorm1d in front folded into W1, b1): Mlp and the SE tail of one DepthNet branch per params block
+ *   (a NaN passes both ReLUs: a NaN in mlp_input[n] makes every gate of map n NaN)
  *   w1t [9][C] | b1 [C] | w2t [C][C] | b2 [C] | wrt [C][C] | br [C] | wet [C][C] | be [C], matrices [in][out]; C <= 1024.
  *
  * rac_depthnet_pool_bias_fwd: ASPP's image-pool branch as a per-image bias of ASPP.conv1: m = mean over the hw rows of map n of x
  *   (channel-last rows of ld floats, C channels; up to 1024 / C pixel segments summed in ascending order, then added in ascending
- *   order), y = relu(wpool_t^T m + bpool), img_bias[n][co] = sum_k wbias_t[k][co] y[k].  wpool_t [C][C], wbias_t [C][Cout], [in][out]. */
+ *   order), y = relu(wpool_t^T m + bpool) (a NaN stays a NaN), img_bias[n][co] = sum_k wbias_t[k][co] y[k].  wpool_t [C][C],
+ *   wbias_t [C][Cout], [in][out]; C <= 1024. */
 enum { RAC_CS_CHANNEL_LAST = 0, RAC_CS_CHANNEL_FIRST = 1 };
 typedef struct {
     const float *in;

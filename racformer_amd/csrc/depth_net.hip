@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void cs_conv_kernel(const rac_conv_small d, in
         if (d.residual)
             v += d.residual[pix * d.ld_res + co];
         if (d.relu)
-            v = fmaxf(v, 0.f);
+            v = rac_relu(v);
         if (d.out_layout == RAC_CS_CHANNEL_FIRST)
             d.out[((size_t)n * d.ld_out + d.c_off + co) * hw + p] = v;
         else
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void dn_gates_kernel(const float *__restrict__
         float s = b1[c];
         for (int k = 0; k < 9; ++k)
             s = fmaf(w1[k * C + c], x[k], s);
-        u[c] = fmaxf(s, 0.f);
+        u[c] = rac_relu(s);
     }
     __syncthreads();
     auto layer = [&](const float *w, const float *b, const float *src, float *dst, int act) {
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void dn_gates_kernel(const float *__restrict__
 #pragma unroll 8
             for (int k = 0; k < C; ++k)
                 s = fmaf(w[(size_t)k * C + c], src[k], s);
-            dst[c] = act == 1 ? fmaxf(s, 0.f) : s;
+            dst[c] = act == 1 ? rac_relu(s) : s;
         }
         __syncthreads();
     };
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(1024) void dn_pool_bias_kernel(const float *__restr
 #pragma unroll 8
         for (int k = 0; k < C; ++k)
             s = fmaf(wpool_t[(size_t)k * C + cc], m[k], s);
-        y[cc] = fmaxf(s, 0.f);
+        y[cc] = rac_relu(s);
     }
     __syncthreads();
     for (int co = threadIdx.x; co < Cout; co += 1024) {

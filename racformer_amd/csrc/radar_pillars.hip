@@ -296,10 +296,12 @@ __global__ __launch_bounds__(256) void rp_encode_kernel(const RpEncode a)
     const float *vox = a.voxels + (size_t)r * a.P * C;
     float mean[3], centre[3];
     rp_pillar_centres(vox, a.P, C, np, co, a.vs, a.center0, mean, centre);
-    float best = np < a.P ? fmaxf(shift, 0.f) : 0.f;       // (every candidate is >= 0: 0 is neutral for the max)
+    // (every candidate is >= 0: 0 is neutral for the max; a NaN among the candidates wins, as torch.max has it)
+    float best = np < a.P ? rac_relu(shift) : 0.f;
     for (int s = 0; s < min(np, a.P); ++s) {
-        const float acc = rp_row_dot(vox + s * C, C, w, wc, mean, centre);
-        best = fmaxf(best, fmaxf(acc + shift, 0.f));
+        const float y = rac_relu(rp_row_dot(vox + s * C, C, w, wc, mean, centre) + shift);
+        if (y > best || y != y)
+            best = y;
     }
     if (a.feats)
         a.feats[(size_t)r * RP_FEAT + ch] = best;
@@ -541,14 +543,14 @@ __global__ __launch_bounds__(256) void rp_train_apply_kernel(const RpTrain a)
         slot = 0;
         for (int s = 1; s < np; ++s) {
             const float y = rp_bn_relu(x[s * RP_FEAT], m, is, g, b);
-            if (y > best) {
+            if (y > best || y != y) {     // (a NaN wins, as torch.max has it; which slot it leaves is unspecified)
                 best = y;
                 slot = s;
             }
         }
         if (np < a.P) {
             const float y = rp_bn_relu(0.f, m, is, g, b);
-            if (y > best) {
+            if (y > best || y != y) {
                 best = y;
                 slot = -1;
             }

@@ -68,9 +68,10 @@ select cost about 1 us a launch, 0.75 % of the branch; recorded, and the fix is 
 the parent's instructions (device assembly of both sources compared kernel by kernel: only the three ReLU instantiations
 differ), and bench.py, which launches none of the three, measures the same with either library (305.7 / 308.2 against 307.2 /
 307.6 samples/s, taking turns on one machine).
-Open, seen while reading and not part of this module: depth_net.hip:177,202,211,258 (fmaxf(v, 0) ReLUs) and the pillar maximum of
-radar_pillars.hip:251,269 (fmaxf drops a NaN point feature) still turn a NaN into a number; the backbone's ReLU (resnet.hip:197,
-v < 0 ? 0 : v) keeps a NaN already.
+Closed since (tests/test_depth_net_fwd_f64_gpu.py, tests/test_radar_pillars_gpu.py::test_2b_*): what this paragraph listed as open --
+the fmaxf(v, 0) ReLUs of depth_net.hip (the convolution's epilogue, both ReLUs of the gates, the image-pool branch) and the pillar
+maximum of radar_pillars.hip, which dropped a NaN point feature -- now keep a NaN (rac_relu; `y > best || y != y`).  The backbone's
+ReLU (resnet.hip, v < 0 ? 0 : v) kept one already.
 """
 import json
 import os

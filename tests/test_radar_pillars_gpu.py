@@ -14,7 +14,7 @@ from racformer_amd import _lib
 from racformer_amd import radar_pillars as RP
 from racformer_amd import synthetic as syn
 from test_conv_direct_gpu import act_scale, image_values
-from test_radar_pillars_ref import edge_points, encoder, hand_points
+from test_radar_pillars_ref import edge_points, encoder, hand_points, poisoned_pillar
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -149,6 +149,45 @@ def test_2_canvas_and_image(name):
     vals2, border2, cv2, bound2 = image_of(fewer)
     assert border2 == 0.0 and float((vals2 - cv2).abs().max()) <= IMAGE_RES * bound2
     assert int((cv2 != 0).sum()) < int((cv != 0).sum()) and bool((vals2[cv2 == 0] == 0).all())      # no stale cell
+
+
+@pytest.mark.parametrize("slot", ["first", "last"])
+def test_2b_nan_point_feature_poisons_its_pillar_alone(slot):
+    """A NaN in a non-coordinate feature of one in-range point (the pillar's first point, finite candidates and the padded rows'
+    behind it, or its last real one): NaN in all 64 channels of that pillar in feats, canvas and image -- a NaN among the candidates
+    wins the maximum, as torch.max has it -- and every other pillar, empty cell and the image's border equal the clean run bit for
+    bit.  Both runs pack the image at the clean cloud's amax: the voxelizer's own amax takes a NaN's bits for the largest, and a NaN
+    bound means scale 1 by design (rac_act_scale)."""
+    from racformer_amd.fused import act_image
+    v, bad, c, n, m = poisoned_pillar(slot)
+    cfg = R.SMALL
+    enc = encoder(cfg, R.make_state_dict(2)).to(DEV)
+    gx, gy, _ = enc.radar_voxel_layer.geom.grid
+    amax = torch.tensor([float(v.abs().max())], device=DEV)
+
+    def run(vox):
+        img = act_image("t_radar_pfn", 4, gy, gx, 64, torch.device(DEV))
+        cv = torch.full((4, 64, gy, gx), float("nan"), device=DEV)
+        feats = torch.full((v.shape[0], 64), float("nan"), device=DEV)
+        enc.radar_voxel_encoder.encode(vox.to(DEV), c.to(DEV), n.to(DEV), 4, gy, gx, amax=amax, canvas=cv, image=img, feats=feats)
+        torch.cuda.synchronize()
+        return feats.cpu(), cv.cpu(), img.cpu().clone().reshape(4, gy + 2, gx + 2, 2, 2, 32)
+
+    f0, c0, i0 = run(v)
+    f1, c1, i1 = run(bad)
+    assert not bool(torch.isnan(f0).any()) and not bool(torch.isnan(c0).any()) and not bool(torch.isnan(i0.float()).any())
+    others = torch.arange(v.shape[0]) != m
+    assert bool(torch.isnan(f1[m]).all()) and torch.equal(f1[others].view(torch.int32), f0[others].view(torch.int32))
+    b, cy, cx = int(c[m, 0]), int(c[m, 2]), int(c[m, 3])
+    cell = torch.zeros(c0.shape, dtype=torch.bool)
+    cell[b, :, cy, cx] = True
+    assert torch.equal(torch.isnan(c1), cell) and torch.equal(c1[~cell].view(torch.int32), c0[~cell].view(torch.int32))
+    pix = torch.zeros(i0.shape, dtype=torch.bool)
+    pix[b, cy + 1, cx + 1] = True
+    assert torch.equal(torch.isnan(i1), pix) and torch.equal(i1[~pix].view(torch.int16), i0[~pix].view(torch.int16))
+    # the routes agree on the poisoned pillar too: the module's torch route on the same voxels
+    want = encoder(cfg, R.make_state_dict(2)).radar_voxel_encoder(bad, n, c).detach()
+    assert torch.equal(torch.isnan(want), torch.isnan(f1))
 
 
 # ------------------------------------------------------------------------------------------------ convolution layers

@@ -87,6 +87,36 @@ def test_padded_rows_take_part_in_the_max():
     assert int(n[0]) == 10 and torch.allclose(st.pillar_features(v, c, n)[0], alone, rtol=0, atol=1e-12)
 
 
+def poisoned_pillar(slot):
+    """SMALL's clouds voxelized, and the same with a NaN in a non-coordinate feature of one in-range point: the first (slot "first")
+    or the last real point of a pillar that holds several and has padded rows behind them -> (clean voxels, poisoned voxels, coors,
+    num, the pillar's row)"""
+    clouds = syn.make_radar_points(4, [0, 1, 40, 300], seed=6, grid=16, edge_fraction=0.2)
+    v, c, n = R.voxelize_batch(clouds, zero_z=True, **R.SMALL)
+    m = int(torch.nonzero((n >= 3) & (n < R.SMALL["max_num_points"]))[0])
+    bad = v.clone()
+    bad[m, 0 if slot == "first" else int(n[m]) - 1, 4] = float("nan")
+    return v, bad, c, n, m
+
+
+@pytest.mark.parametrize("slot", ["first", "last"])
+def test_nan_point_feature_poisons_its_pillar_alone(slot):
+    """torch.max keeps a NaN among a pillar's candidates: all 64 channels of that pillar are NaN, in the features and on the canvas,
+    and every other pillar keeps the clean run's bits (the restatement, and the module's torch route)"""
+    v, bad, c, n, m = poisoned_pillar(slot)
+    st = R.Stages(R.make_state_dict(2), torch.float32, **R.SMALL)
+    enc = encoder(R.SMALL, R.make_state_dict(2))
+    for feats in (lambda x: st.pillar_features(x, c, n), lambda x: enc.radar_voxel_encoder(x, n, c).detach()):
+        clean, got = feats(v), feats(bad)
+        assert not bool(torch.isnan(clean).any()) and bool(torch.isnan(got[m]).all())
+        others = torch.arange(v.shape[0]) != m
+        assert torch.equal(got[others].view(torch.int32), clean[others].view(torch.int32))
+    canvas, clean = st.canvas(bad, c, n, 4), st.canvas(v, c, n, 4)
+    cell = torch.zeros(clean.shape, dtype=torch.bool)
+    cell[int(c[m, 0]), :, int(c[m, 2]), int(c[m, 3])] = True
+    assert torch.equal(torch.isnan(canvas), cell) and torch.equal(canvas[~cell], clean[~cell])
+
+
 RIGS = {
     "hand": (R.HAND, lambda: [hand_points()]),
     "edges": (R.F8, lambda: [edge_points()]),

@@ -83,6 +83,8 @@
  *                        and GridMask (models/utils.py:8-45, :104-120, :219-305; models/racformer.py:108-109, :198-224)
  *   rac_adamw_step    <- the optimizer and grad_clip of the training recipe (AdamW through mmcv's optimizer hook,
  *                        configs/racformer_r50_nuimg_704x256_f8.py:282-296): clip_grad_norm_ + torch.optim.AdamW.step
+ *   rac_point_maps_radar_fwd / rac_point_maps_lidar_fwd <- RadarPointToMultiViewDepth and PointToMultiViewDepth of the data pipeline
+ *                        (loaders/pipelines/loading.py:470-600): the radar_depth / radar_rcs maps and gt_depth from the clouds
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -93,7 +95,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 34
+#define RAC_ABI_VERSION 35
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1362,6 +1364,37 @@ typedef struct {
 } rac_opt_record;
 int rac_adamw_step(const rac_opt_tensor *tensors, int n_tensors, const rac_opt_chunk *chunks, int n_chunks, const double *hyper,
                    float *steps, float *scalars, double *partials, rac_opt_record *record, float max_norm, int phases, void *stream);
+
+/* Point clouds to per-view maps (csrc/point_maps.hip; racformer_amd/point_maps.py): what the reference's data pipeline
+ * makes on the CPU -- radar_depth / radar_rcs from the radar clouds, gt_depth from the lidar cloud -- made on the device from the
+ * packed clouds of the radar pillar ABI.  Nothing is read back, launches are sized by the shapes alone, no allocation: capturable;
+ * winners are chosen by 64-bit integer atomic min / max, so two runs give the same bits.
+ *   points        : DEVICE float [n_points, C], C >= 3: x, y, z and further columns
+ *   cloud_offsets : DEVICE int32 [n_clouds + 1], ascending from 0 to n_points (rac_pillar_voxelize_fwd's table)
+ *   mats          : DEVICE float [n_clouds * n_views, 12]: rows 0..2 of the 4x4 lidar2img of map m = cloud * n_views + view
+ *   H, W, ds      : the image size and the downsample; the map is hm x wm = H / ds x W / ds (integer division)
+ *   Hp, Wp        : the outputs' row count and row length, Hp >= hm, Wp >= wm; outputs are [n_clouds * n_views, Hp, Wp], every element
+ *                   is written, rows >= hm and columns >= wm as +0.0.  Outputs are 4-byte aligned; stores are 16 bytes wide where
+ *                   the address allows it, scalar otherwise
+ *   scratch       : DEVICE uint64 [scratch_words], 8-byte aligned, contents arbitrary before and after.  Needed: radar
+ *                   2 * n_clouds * n_views * wm words, lidar n_clouds * n_views * hm * wm words
+ * Per cloud and view (float32, every operation rounded once, left to right, IEEE division):
+ *   p_i = x M[i][0] + y M[i][1] + z M[i][2] + M[i][3];  u = p_0 / p_2, v = p_1 / p_2, d = p_2;  cx = rint(u / ds), cy = rint(v / ds)
+ *   kept: 0 <= cx < wm, 0 <= cy < hm, lo <= d < hi (NaN, inf and p_2 = 0 fail);  key k = (cx + cy wm) + d / 100
+ *   a pixel's winner is the kept point with the smallest (k, index in the cloud)
+ *   lidar: gt_depth[cy][cx] = d of the pixel's winner, 0 elsewhere
+ *   radar: every row of column cx = the value of the column's pixel winner with the largest cy, 0 for a column without one;
+ *          radar_depth gets the winner's d, radar_rcs gets points[s][rcs_col] where s is the winner's POSITION AMONG THE CLOUD'S KEPT
+ *          POINTS for this view in input order (the reference's indexing, kept as it is); either output may be NULL
+ * RAC_E_ARG before any HIP call: a null or misaligned pointer, C < 3, ds < 1, H < ds or W < ds, Hp < hm or Wp < wm, rcs_col outside
+ * [0, C), a scratch that is too small, more than 65535 maps.  RAC_E_UNSUPPORTED before any HIP call: hm * wm > 2^18, hi > 99 or
+ * lo <= 0 (the key's rounding could reach the next pixel's rank, or a key could be negative), n_points >= 2^20, hm > 4096. */
+int rac_point_maps_radar_fwd(const float *points, const int32_t *cloud_offsets, const float *mats, float *radar_depth, float *radar_rcs,
+                             uint64_t *scratch, int64_t scratch_words, int n_points, int n_clouds, int n_views, int C, int rcs_col, int H,
+                             int W, int Hp, int Wp, int ds, float lo, float hi, void *stream);
+int rac_point_maps_lidar_fwd(const float *points, const int32_t *cloud_offsets, const float *mats, float *gt_depth, uint64_t *scratch,
+                             int64_t scratch_words, int n_points, int n_clouds, int n_views, int C, int H, int W, int Hp, int Wp, int ds,
+                             float lo, float hi, void *stream);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,8 @@ SIGNATURES = {
     "rac_resnet_relu_bwd": (_i, [_vp] * 4 + [ctypes.c_int64, _vp]),
     "rac_frames_gather": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rac_adamw_step": (_i, [_vp, _i, _vp, _i] + [_vp] * 5 + [_f, _i, _vp]),
+    "rac_point_maps_radar_fwd": (_i, [_vp] * 6 + [ctypes.c_int64] + [_i] * 10 + [_f, _f, _vp]),
+    "rac_point_maps_lidar_fwd": (_i, [_vp] * 5 + [ctypes.c_int64] + [_i] * 9 + [_f, _f, _vp]),
 }
 
 

@@ -1,5 +1,5 @@
 """The detector that joins the parts: ``RaCFormer`` of the reference's models/racformer.py -- images, radar clouds and the
-radar depth / RCS maps to boxes, offline (``simple_test_offline``: all T frames of a sample through the front end) and streaming
+radar depth / RCS maps (given, or made here from the radar clouds: ``radar_depth=None, radar_rcs=None``, racformer_amd/point_maps.py) to boxes, offline (``simple_test_offline``: all T frames of a sample through the front end) and streaming
 (``simple_test_online``: only the frames the memory does not hold yet).
 
 Constructor arguments are the ``model`` dict entries of configs/racformer_r50_nuimg_704x256_f8.py:108-201; every sub-config is a dict
@@ -59,7 +59,8 @@ from .head import RaCFormer_head
 from .image_aug import GpuPhotoMetricDistortion, GridMask, prepare_images
 from .lss_depth import LSSViewTransformerBEVDepth_racformer
 from .necks import FPN, CustomFPN
-from .radar_pillars import RadarPillarEncoder
+from .point_maps import lidar_depth_map, meta_view_table, radar_maps
+from .radar_pillars import RadarPillarEncoder, pack_clouds
 from .resnet import ResNet, apply_input_norm
 
 MEMORY_KEYS = 16        # the reference evicts while its queue holds this many keys (:551)
@@ -298,10 +299,32 @@ class RaCFormer(nn.Module):
         """:153-177 -> (voxels, num_points, coors [M, 4])"""
         return self.radar_encoder.radar_voxelize(points)
 
-    def extract_feat(self, img, radar_points, radar_depth, radar_rcs, img_metas):
+    def point_maps(self, img, radar_points, img_metas):
+        """The radar maps the reference's loader would hand over (RadarPointToMultiViewDepth, downsample 1): radar_points, a list
+        over T of lists over B of [n, >= 4] clouds, and ``img_metas[b]['lidar2img']`` -> (radar_depth, radar_rcs) [B, T*N, H, W] on the
+        images' device, map t*N + view from frame t's cloud (``point_maps.radar_maps``: HIP on the device, the restatement on CPU)."""
+        first = img[0] if isinstance(img, list) else img
+        H, W = first.shape[-2:]
+        B, T, N = len(img_metas), len(radar_points), self.num_cams
+        clouds = [radar_points[t][b].detach().to(first.device, torch.float32) for b in range(B) for t in range(T)]
+        points, offsets = pack_clouds(clouds)
+        mats = meta_view_table(img_metas, N, frames=T, device=first.device)
+        depth, rcs = radar_maps(points, offsets, mats, (H, W), self.img_lss_view_transformer.grid_config)
+        return depth.view(B, T * N, H, W), rcs.view(B, T * N, H, W)
+
+    def _maps_or_built(self, img, radar_points, radar_depth, radar_rcs, img_metas):
+        if (radar_depth is None) != (radar_rcs is None):
+            raise ValueError("RaCFormer: radar_depth and radar_rcs go together: pass both, or neither to have them made from radar_points")
+        if radar_depth is None:
+            return self.point_maps(img, radar_points, img_metas)
+        return radar_depth, radar_rcs
+
+    def extract_feat(self, img, radar_points, radar_depth=None, radar_rcs=None, img_metas=None):
         """The eval branch of :179-348.  img [B, T*N, 3, H, W], radar_points a list over T of lists over B of [n, 7], radar_depth /
-        radar_rcs [B, T*N, (1,) H, W] -> (img_feats: per level [B, T*N, C, H_i, W_i] -- or [B*T*G, N, H_i, W_i, 64], pregrouped --,
+        radar_rcs [B, T*N, (1,) H, W] -- or both None: made from radar_points and the metas' lidar2img (``point_maps``) -> (img_feats:
+        per level [B, T*N, C, H_i, W_i] -- or [B*T*G, N, H_i, W_i, 64], pregrouped --,
         all_bev_feats [B, T, C, Y, X], radar_bev_feats [B, T, 256, Y, X], depth of frame 0 [B*N, D, h, w])."""
+        radar_depth, radar_rcs = self._maps_or_built(img, radar_points, radar_depth, radar_rcs, img_metas)
         if self.training:
             if not self.fused_grad:
                 raise NotImplementedError(TRAINING_MESSAGE)
@@ -492,16 +515,34 @@ class RaCFormer(nn.Module):
         losses.update(self.pts_bbox_head.loss(gt_bboxes_3d, gt_labels_3d, outs))
         return losses
 
+    def lidar_gt_depth(self, points, img, img_metas, pad_hw=None):
+        """``gt_depth`` as the reference's loader makes it (PointToMultiViewDepth, downsample 1): points, a list over B of [n, >= 3]
+        lidar clouds, and frame 0's views -> [B, N, Hp, Wp] on the images' device (``point_maps.lidar_depth_map``)."""
+        first = img[0] if isinstance(img, list) else img
+        H, W = first.shape[-2:]
+        B, N = len(img_metas), self.num_cams
+        pts, offsets = pack_clouds([p.detach().to(first.device, torch.float32) for p in points])
+        mats = meta_view_table(img_metas, N, frames=1, device=first.device)
+        out = lidar_depth_map(pts, offsets, mats, (H, W), self.img_lss_view_transformer.grid_config, pad_hw=pad_hw)
+        return out.view(B, N, *out.shape[-2:])
+
     def forward_train(self, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_depth=None, img=None, radar_points=None,
-                      radar_depth=None, radar_rcs=None, gt_bboxes_ignore=None):
+                      radar_depth=None, radar_rcs=None, gt_bboxes_ignore=None, points=None):
         """:400-441: one training forward -> the dict of losses (``loss_depth``, ``loss_cls``, ``loss_bbox``, ``d{i}.*`` and, with
-        denoising queries, the ``*_dn`` keys), each a 0-dim tensor with its graph.  Needs ``fused_grad`` and ``train()``."""
+        denoising queries, the ``*_dn`` keys), each a 0-dim tensor with its graph.  Needs ``fused_grad`` and ``train()``.
+        ``radar_depth`` / ``radar_rcs`` None: made from ``radar_points``; ``gt_depth`` None: made from ``points``, a list over B of
+        lidar clouds, at the padded size the depth logits stand for."""
         if not self.fused_grad:
             raise NotImplementedError(TRAINING_MESSAGE)
         if not self.training:
             raise RuntimeError("RaCFormer.forward_train: the detector is in eval mode; call train() first")
         self.reset_memory()         # (frames held by the streaming memory, and a captured plan, belong to the weights before this step)
+        if gt_depth is None and points is None:
+            raise ValueError("RaCFormer.forward_train: gt_depth, or the lidar clouds `points` to make it from, is needed")
         img_feats, bev_feats, radar_bev_feats, depth = self.extract_feat(img, radar_points, radar_depth, radar_rcs, img_metas)
+        if gt_depth is None:
+            ds = self.img_lss_view_transformer.downsample
+            gt_depth = self.lidar_gt_depth(points, img, img_metas, pad_hw=(depth.shape[2] * ds, depth.shape[3] * ds))
         for i in range(len(img_metas)):
             img_metas[i]['gt_bboxes_3d'] = gt_bboxes_3d[i]
             img_metas[i]['gt_labels_3d'] = gt_labels_3d[i]
@@ -522,7 +563,10 @@ class RaCFormer(nn.Module):
         return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
 
     def simple_test(self, img_metas, img=None, rescale=False, radar_points=None, radar_depth=None, radar_rcs=None, **kwargs):
-        return self.simple_test_offline(img_metas, img, rescale, radar_points[0], radar_depth[0], radar_rcs[0])
+        if (radar_depth is None) != (radar_rcs is None):
+            raise ValueError("RaCFormer: radar_depth and radar_rcs go together: pass both, or neither to have them made from radar_points")
+        return self.simple_test_offline(img_metas, img, rescale, radar_points[0], None if radar_depth is None else radar_depth[0],
+                                        None if radar_rcs is None else radar_rcs[0])
 
     def simple_test_offline(self, img_metas, img=None, rescale=False, radar_points=None, radar_depth=None, radar_rcs=None):
         img_feats, bev_feats, radar_bev_feats, _ = self.extract_feat(img=img, radar_points=radar_points, radar_depth=radar_depth,
@@ -588,8 +632,12 @@ class RaCFormer(nn.Module):
         B, NT, C, H, W = img.shape
         N = self.num_cams
         img = img.reshape(B, NT // N, N, C, H, W)
-        radar_depth = radar_depth.reshape(B, NT // N, N, 1, H, W)
-        radar_rcs = radar_rcs.reshape(B, NT // N, N, 1, H, W)
+        if (radar_depth is None) != (radar_rcs is None):
+            raise ValueError("RaCFormer: radar_depth and radar_rcs go together: pass both, or neither to have them made from radar_points")
+        built = radar_depth is None         # (then a frame's maps are made when the frame is computed, from its cloud and its metas)
+        if not built:
+            radar_depth = radar_depth.reshape(B, NT // N, N, 1, H, W)
+            radar_rcs = radar_rcs.reshape(B, NT // N, N, 1, H, W)
         img_filenames = img_metas[0]['filename']
         num_frames = len(img_filenames) // N
         img_shape = (H, W, C)
@@ -607,7 +655,8 @@ class RaCFormer(nn.Module):
             metas_curr = [{k: [v[m] for m in idx] for k, v in img_metas[0].items() if isinstance(v, list)}]
             key = img_filenames[i * N]
             if self.memory is None or key not in self.memory.slots:
-                feats, bev, radar, _ = self.extract_feat(img[:, i], [radar_points[i]], radar_depth[:, i], radar_rcs[:, i], metas_curr)
+                feats, bev, radar, _ = self.extract_feat(img[:, i], [radar_points[i]], None if built else radar_depth[:, i],
+                                                         None if built else radar_rcs[:, i], metas_curr)
                 tensors = self._frame_tensors(feats, bev, radar)
                 pregrouped = self.pts_bbox_head.transformer.decoder.pregrouped
                 if self.memory is None or not self.memory.fits(tensors, n_slots, pregrouped):

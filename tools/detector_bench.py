@@ -10,7 +10,9 @@ repetition after a warm-up (tools/resnet_bench.py's scheme).  Three groups:
               (``FPN.forward_pregrouped`` + ``CustomFPN``), the per-frame view-transformer loop, the per-frame radar loop, decoder +
               decode (``pts_bbox_head`` + ``get_bboxes``); and the whole call
   streaming   the steady-state step of ``simple_test_online``: the front end on one frame (``extract_feat``, T = 1), the slot copy,
-              the gather launch, ``CapturedStep.replay`` + ``get_bboxes``; and the whole call with one new frame per step
+              the gather launch, ``CapturedStep.replay`` + ``get_bboxes``; and the whole call with one new frame per step; the
+              ``*_built_maps`` entries are the same front end and the same whole call with ``radar_depth=None, radar_rcs=None`` (the
+              maps made on the device from the frame's cloud, racformer_amd/point_maps.py)
   gather      ``rac_frames_gather`` of the window beside ``Tensor.copy_`` of the same bytes (T consecutive slots per kind, six calls)
 Nothing is asserted.  Every figure in the record is measured by this run; ``expectation`` repeats what DESIGN.md derived beforehand."""
 import argparse
@@ -152,9 +154,11 @@ def main():
     det.reset_memory()
     step = [0]
 
-    def online():
+    def online(built_maps=False):
         s = step[0] = step[0] + 1
         w = window(frames, [max(s - t, 0) for t in range(T)])                             # one new key per step
+        if built_maps:                          # the radar maps made on the device from the new frame's cloud
+            return det.simple_test_online(w[4], w[0], False, w[1], None, None)
         return det.simple_test_online(w[4], w[0], False, w[1], w[2], w[3])
 
     for _ in range(T + 2):
@@ -178,7 +182,9 @@ def main():
             slot_copy=lambda: [r[spare].copy_(t) for r, t in zip(mem.rings, tensors)],
             gather=lambda: fused.frames_gather(mem.rings, win, slots),
             replay_and_decode=replay,
-            whole=online), args.reps)
+            whole=online,
+            front_end_one_frame_built_maps=lambda: det.extract_feat(one[0], one[1], None, None, metas_of([3])),
+            whole_built_maps=lambda: online(True)), args.reps)
         rec["streaming"]["memory"] = dict(slots=mem.n_slots, ring_bytes=sum(r.numel() * 4 for r in mem.rings),
                                           window_bytes=sum(w.numel() * 4 for w in win))
 

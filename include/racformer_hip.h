@@ -85,6 +85,8 @@
  *                        configs/racformer_r50_nuimg_704x256_f8.py:282-296): clip_grad_norm_ + torch.optim.AdamW.step
  *   rac_point_maps_radar_fwd / rac_point_maps_lidar_fwd <- RadarPointToMultiViewDepth and PointToMultiViewDepth of the data pipeline
  *                        (loaders/pipelines/loading.py:470-600): the radar_depth / radar_rcs maps and gt_depth from the clouds
+ *   rac_image_geom_fwd <- RandomTransformImage of the data pipeline (loaders/pipelines/transforms.py:219-342): Pillow's bicubic
+ *                        Image.resize, crop and left-right flip of the raw camera frames
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -95,7 +97,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 35
+#define RAC_ABI_VERSION 36
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1395,6 +1397,32 @@ int rac_point_maps_radar_fwd(const float *points, const int32_t *cloud_offsets, 
 int rac_point_maps_lidar_fwd(const float *points, const int32_t *cloud_offsets, const float *mats, float *gt_depth, uint64_t *scratch,
                              int64_t scratch_words, int n_points, int n_clouds, int n_views, int C, int H, int W, int Hp, int Wp, int ds,
                              float lo, float hi, void *stream);
+
+/* Raw camera frames to the detector's images (csrc/image_geom.hip; racformer_amd/image_geom.py): the resize, crop and
+ * left-right flip of the reference's RandomTransformImage as Pillow's 8-bit bicubic resampler computes them, for all images of all
+ * samples in ONE launch.  Integer arithmetic only, nothing read back, sized by the shapes, no atomics, no allocation: capturable, the
+ * same bits on every run.  raw is only read; every output element is written exactly once.
+ *   raw         : DEVICE uint8 [n_images, Hr, Wr, 3], any byte alignment
+ *   group       : consecutive images that share one table (one sample's draw); n_images is a multiple of it
+ *   tables      : DEVICE int32 [n_images / group, words], 4-byte aligned; tables_host: the same words in HOST memory, read before the
+ *                 call returns (every bound is checked there, so the kernel cannot read outside raw).  With ntx = ceil(fW / 64) and
+ *                 nty = ceil(fH / 16), one group's words are, in this order:
+ *                   column bounds [fW][2]   : output column ox reads raw columns [first, first + count); count = 0: it is 0
+ *                   row bounds    [fH][2]   : the same for output row oy and raw rows
+ *                   column spans  [ntx][2]  : [lo, hi) covers the reads of output columns 64 i .. 64 i + 63 (0, 0 for none)
+ *                   row spans     [nty][2]  : the same for output rows 16 i .. 16 i + 15
+ *                   column weights [fW][ksize], row weights [fH][ksize] : 22-bit fixed point, entries past the count unused
+ *   out         : DEVICE, out_kind RAC_IG_F32_CHW: float [n_images, 3, fH, fW], the integers 0 .. 255; RAC_IG_U8_HWC: uint8
+ *                 [n_images, fH, fW, 3].  The channel order is raw's.
+ * Per channel: h(r, ox) = clip8((2^21 + sum_t raw[r][first_x + t] * wx[ox][t]) >> 22) for the raw rows r an output row reads, then
+ * out(oy, ox) = clip8((2^21 + sum_t h(first_y + t, ox) * wy[oy][t]) >> 22); int32 sums (the caller's weights keep them below 2^31).
+ * RAC_E_ARG before any HIP call: a null pointer, a misaligned table or float output, a size <= 0, n_images > 65535 or not a multiple of
+ * group, a bound outside raw or outside its tile's span, a count above ksize.  RAC_E_UNSUPPORTED before any HIP call, nothing is
+ * launched: ksize > 16, a column span above 212 raw columns or a row span above 64 raw rows (the LDS tile chosen at compile time; a
+ * down-scale by more than about 3). */
+enum { RAC_IG_F32_CHW = 0, RAC_IG_U8_HWC = 1 };
+int rac_image_geom_fwd(const uint8_t *raw, const int32_t *tables, const int32_t *tables_host, void *out, int n_images, int group, int Hr,
+                       int Wr, int fH, int fW, int ksize, int out_kind, void *stream);
 
 #ifdef __cplusplus
 }

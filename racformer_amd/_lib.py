@@ -128,6 +128,7 @@ SIGNATURES = {
     "rac_adamw_step": (_i, [_vp, _i, _vp, _i] + [_vp] * 5 + [_f, _i, _vp]),
     "rac_point_maps_radar_fwd": (_i, [_vp] * 6 + [ctypes.c_int64] + [_i] * 10 + [_f, _f, _vp]),
     "rac_point_maps_lidar_fwd": (_i, [_vp] * 5 + [ctypes.c_int64] + [_i] * 9 + [_f, _f, _vp]),
+    "rac_image_geom_fwd": (_i, [_vp] * 4 + [_i] * 8 + [_vp]),
 }
 
 

@@ -18,6 +18,10 @@ itself has no CPU route: ``pts_bbox_head`` raises there).  Departure, attribute 
 ``FPN.forward_pregrouped`` -- instead of ``[B, T*N, C, H, W]``, and sets ``pts_bbox_head.transformer.decoder.pregrouped`` to match what
 it returned; the regroup copy then never runs.
 
+Raw frames: ``prepare_raw`` takes what the cameras deliver -- uint8 frames and their metas -- through the loader's
+``RandomTransformImage`` on the device (racformer_amd/image_geom.py: one launch for all frames of all samples) and returns the ``img``
+and ``img_metas`` every entry point below takes as it is.
+
 Streaming (``simple_test_online``, :476-557, quirks included): batch size 1; a frame's key is its first camera's file name; a frame not
 in the memory goes through ``extract_feat`` alone (T = 1, the metas of this call), so a cached BEV map stays in the ego frame of the
 call that first saw it; a key repeated inside a window is computed once; after the call the oldest keys leave while the memory holds
@@ -57,6 +61,7 @@ import torch.nn.functional as F
 
 from .head import RaCFormer_head
 from .image_aug import GpuPhotoMetricDistortion, GridMask, prepare_images
+from .image_geom import ida_mat, transform_images
 from .lss_depth import LSSViewTransformerBEVDepth_racformer
 from .necks import FPN, CustomFPN
 from .point_maps import lidar_depth_map, meta_view_table, radar_maps
@@ -311,6 +316,32 @@ class RaCFormer(nn.Module):
         mats = meta_view_table(img_metas, N, frames=T, device=first.device)
         depth, rcs = radar_maps(points, offsets, mats, (H, W), self.img_lss_view_transformer.grid_config)
         return depth.view(B, T * N, H, W), rcs.view(B, T * N, H, W)
+
+    def prepare_raw(self, raw, img_metas, transform, draws=None):
+        """What the reference's loader does to the camera frames before the detector sees them (``RandomTransformImage``,
+        loaders/pipelines/transforms.py:219-342): raw uint8 [B, T*N, Hr, Wr, 3] (the loader's channel order) and the metas of the raw
+        frames -> (img float32 [B, T*N, 3, fH, fW] with values 0..255, img_metas), ready for ``forward_train``, ``simple_test_offline``
+        and ``simple_test_online``.  ``transform``: an ``image_geom.RandomTransformImage``; ``draws``: one ``IdaDraw`` per sample, by
+        default drawn here in the order of the samples, as the pipeline runs once per sample.  All images go through one launch
+        (``image_geom.transform_images``; the numpy route on CPU tensors).  The returned metas are copies whose ``lidar2img`` are
+        ``ida_mat @ lidar2img`` (float32 @ the meta's matrix) and whose ``ori_shape`` / ``img_shape`` / ``pad_shape`` are the new
+        shape; the caller's metas stay as they are."""
+        if raw.dim() != 5 or raw.shape[-1] != 3 or raw.dtype != torch.uint8:
+            raise ValueError(f"RaCFormer.prepare_raw: uint8 [B, T*N, H, W, 3] frames expected, got {raw.dtype} {tuple(raw.shape)}")
+        B, TN = raw.shape[:2]
+        if len(img_metas) != B:
+            raise ValueError(f"RaCFormer.prepare_raw: {len(img_metas)} metas for {B} samples")
+        draws = [transform.draw() for _ in range(B)] if draws is None else list(draws)
+        if len(draws) != B:
+            raise ValueError(f"RaCFormer.prepare_raw: {len(draws)} draws for {B} samples")
+        img = transform_images(raw.reshape(B * TN, *raw.shape[2:]).contiguous(), draws, out="f32_chw")
+        metas = []
+        for meta, draw in zip(img_metas, draws):
+            mat = ida_mat(draw)
+            shape = [tuple(img.shape[-2:]) + (3,)] * TN
+            metas.append(dict(meta, lidar2img=[mat @ m for m in meta['lidar2img']], ori_shape=shape, img_shape=list(shape),
+                              pad_shape=list(shape)))
+        return img.view(B, TN, *img.shape[1:]), metas
 
     def _maps_or_built(self, img, radar_points, radar_depth, radar_rcs, img_metas):
         if (radar_depth is None) != (radar_rcs is None):

@@ -87,6 +87,8 @@
  *                        (loaders/pipelines/loading.py:470-600): the radar_depth / radar_rcs maps and gt_depth from the clouds
  *   rac_image_geom_fwd <- RandomTransformImage of the data pipeline (loaders/pipelines/transforms.py:219-342): Pillow's bicubic
  *                        Image.resize, crop and left-right flip of the raw camera frames
+ *   rac_bev_aug_fwd   <- RaCGlobalRotScaleTransImage of the data pipeline (loaders/pipelines/transforms.py:398-464): the rotation about
+ *                        z and the isotropic scaling of the lidar cloud, the radar clouds and the ground-truth boxes
  */
 #ifndef RACFORMER_HIP_H
 #define RACFORMER_HIP_H
@@ -97,7 +99,7 @@
 extern "C" {
 #endif
 
-#define RAC_ABI_VERSION 36
+#define RAC_ABI_VERSION 37
 #define RAC_MAX_LEVELS 8
 #define RAC_MAX_POINTS 128 /* same limit as the reference, msmv_sampling_forward.cu:21 */
 
@@ -1423,6 +1425,45 @@ int rac_point_maps_lidar_fwd(const float *points, const int32_t *cloud_offsets, 
 enum { RAC_IG_F32_CHW = 0, RAC_IG_U8_HWC = 1 };
 int rac_image_geom_fwd(const uint8_t *raw, const int32_t *tables, const int32_t *tables_host, void *out, int n_images, int group, int Hr,
                        int Wr, int fH, int fW, int ksize, int out_kind, void *stream);
+
+/* The scene's rotation about z and isotropic scaling (csrc/bev_aug.hip; racformer_amd/bev_aug.py): what the reference's
+ * RaCGlobalRotScaleTransImage does to the lidar cloud, the radar clouds and the ground-truth boxes through mmdet3d's rotate / scale,
+ * for all samples of a step in ONE launch.  No trigonometric function on the device, nothing read back, the grid sized by the chunk
+ * table, no atomics, no allocation: capturable, the same bits on every run and at every address.
+ *   segs    : DEVICE [n_segs] rac_bev_seg -- src (read) and dst (written) float [rows, cols], rows back to back, 4-byte aligned; kind
+ *             RAC_BEV_POINTS (3 <= cols <= RAC_BEV_MAX_COLS) or RAC_BEV_BOXES (cols 7 or 9: x, y, z of the bottom centre, w, l, h, yaw
+ *             and, with 9, vx, vy); sample: the row of `draws` the segment uses.  rows may be 0.  dst == src is allowed (a lane reads its
+ *             row whole before it writes it); any other overlap of a dst with a src or with another dst is refused
+ *   chunks  : DEVICE [n_chunks] rac_bev_chunk -- segment and first row of every RAC_BEV_CHUNK rows of every segment, segments in
+ *             table order, a segment's chunks ascending (the last one short); one workgroup per chunk, one row per lane
+ *   segs_host, chunks_host : the same tables in HOST memory, read before the call returns: everything below is checked there, so the
+ *             kernel cannot touch a row no segment names
+ *   draws   : DEVICE float [n_samples, 4] -- c, s, a, r per sample: cos and sin of the angle as the host computed them, the angle and
+ *             the scale ratio, all float32.  Read by the launch, so a captured launch takes new draws from a rewritten table
+ * Per row, float32, every operation rounded once, nothing contracted into a fused multiply-add, left to right:
+ *   points: x' = ((x c + y (-s)) + z 0) r;  y' = ((x s + y c) + z 0) r;  z' = ((x 0 + y 0) + z 1) r;  columns >= 3 copied bit for bit
+ *           (the products by 0 stay: they carry a NaN or inf coordinate into the other two, as the reference's matmul does)
+ *   boxes : the centre as a point; w, l, h times r; yaw' = yaw + a (not re-limited); vx' = (vx c + vy (-s)) r, vy' = (vx s + vy c) r
+ * n_chunks == 0 (every segment empty) launches nothing.  RAC_E_ARG before any HIP call: a null or misaligned pointer, n_segs outside
+ * [1, 1024], n_samples < 1, rows < 0, rows * cols >= 2^31, cols or kind or sample out of range, overlapping segments, a chunk table that
+ * is not the one described above. */
+enum { RAC_BEV_POINTS = 0, RAC_BEV_BOXES = 1 };
+#define RAC_BEV_CHUNK 256
+#define RAC_BEV_MAX_COLS 16
+typedef struct {
+    const float *src;
+    float *dst;
+    int32_t rows;
+    int32_t cols;
+    int32_t kind;
+    int32_t sample;
+} rac_bev_seg;
+typedef struct {
+    int32_t seg;
+    int32_t row0;
+} rac_bev_chunk;
+int rac_bev_aug_fwd(const rac_bev_seg *segs, const rac_bev_chunk *chunks, const rac_bev_seg *segs_host, const rac_bev_chunk *chunks_host,
+                    const float *draws, int n_segs, int n_chunks, int n_samples, void *stream);
 
 #ifdef __cplusplus
 }

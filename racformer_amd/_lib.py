@@ -129,6 +129,7 @@ SIGNATURES = {
     "rac_point_maps_radar_fwd": (_i, [_vp] * 6 + [ctypes.c_int64] + [_i] * 10 + [_f, _f, _vp]),
     "rac_point_maps_lidar_fwd": (_i, [_vp] * 5 + [ctypes.c_int64] + [_i] * 9 + [_f, _f, _vp]),
     "rac_image_geom_fwd": (_i, [_vp] * 4 + [_i] * 8 + [_vp]),
+    "rac_bev_aug_fwd": (_i, [_vp] * 5 + [_i] * 3 + [_vp]),
 }
 
 
@@ -204,6 +205,12 @@ RESNET_AMAX_PARTS = 64
 # layouts (rac_opt_tensor, rac_opt_chunk, rac_opt_record) are numpy dtypes in racformer_amd/optim.py
 OPT_CHUNK, OPT_HYPER, OPT_SCALARS = 16384, 6, 8
 OPT_NORM, OPT_FINISH, OPT_UPDATE, OPT_ALL = 1, 2, 4, 7
+
+
+# rac_bev_aug_fwd (include/racformer_hip.h): RAC_BEV_CHUNK, RAC_BEV_MAX_COLS and the segment kinds; the tables' layouts (rac_bev_seg,
+# rac_bev_chunk) are numpy dtypes in racformer_amd/bev_aug.py
+BEV_CHUNK, BEV_MAX_COLS = 256, 16
+BEV_POINTS, BEV_BOXES = 0, 1
 
 
 def lib():

@@ -20,7 +20,8 @@ it returned; the regroup copy then never runs.
 
 Raw frames: ``prepare_raw`` takes what the cameras deliver -- uint8 frames and their metas -- through the loader's
 ``RandomTransformImage`` on the device (racformer_amd/image_geom.py: one launch for all frames of all samples) and returns the ``img``
-and ``img_metas`` every entry point below takes as it is.
+and ``img_metas`` every entry point below takes as it is.  ``prepare_bev_aug`` is the loader's next geometric stage,
+``RaCGlobalRotScaleTransImage`` (racformer_amd/bev_aug.py: the scene's rotation and scaling of all clouds and boxes in one launch).
 
 Streaming (``simple_test_online``, :476-557, quirks included): batch size 1; a frame's key is its first camera's file name; a frame not
 in the memory goes through ``extract_feat`` alone (T = 1, the metas of this call), so a cached BEV map stays in the ego frame of the
@@ -59,6 +60,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .bev_aug import RaCGlobalRotScaleTransImage, transform_batch, view_mats
 from .head import RaCFormer_head
 from .image_aug import GpuPhotoMetricDistortion, GridMask, prepare_images
 from .image_geom import ida_mat, transform_images
@@ -342,6 +344,26 @@ class RaCFormer(nn.Module):
             metas.append(dict(meta, lidar2img=[mat @ m for m in meta['lidar2img']], ori_shape=shape, img_shape=list(shape),
                               pad_shape=list(shape)))
         return img.view(B, TN, *img.shape[1:]), metas
+
+    def prepare_bev_aug(self, img_metas, radar_points, points=None, gt_bboxes_3d=None, transform=None, draws=None):
+        """The loader's stage between ``prepare_raw`` and the point maps (``RaCGlobalRotScaleTransImage``,
+        loaders/pipelines/transforms.py:398-464): one rotation about z and one scaling of the whole scene per sample.  ``radar_points``:
+        a list over T of lists over B of [n, 7]; ``points``: a list over B of lidar clouds; ``gt_bboxes_3d``: a list over B of [n, 9]
+        (or [n, 7]) boxes, tensors or objects with ``.tensor`` -> (img_metas, radar_points, points, gt_bboxes_3d), ready for
+        ``forward_train(radar_depth=None, radar_rcs=None, gt_depth=None, points=...)``.  ``transform``: a
+        ``bev_aug.RaCGlobalRotScaleTransImage`` (by default the recipe's); ``draws``: one ``BevDraw`` per sample, by default drawn here
+        in the order of the samples.  All clouds and boxes go through one launch (``bev_aug.transform_batch``; the torch route on CPU
+        tensors) and come back as views into packed tensors, the clouds in the nesting they came in, the boxes as plain tensors.  The
+        returned metas are copies whose ``lidar2img`` are ``bev_aug.view_mats``'; the caller's metas, clouds and boxes stay as they are."""
+        B = len(img_metas)
+        transform = RaCGlobalRotScaleTransImage() if transform is None else transform
+        draws = [transform.draw() for _ in range(B)] if draws is None else list(draws)
+        if len(draws) != B:
+            raise ValueError(f"RaCFormer.prepare_bev_aug: {len(draws)} draws for {B} samples")
+        boxes = None if gt_bboxes_3d is None else [b if isinstance(b, torch.Tensor) else b.tensor for b in gt_bboxes_3d]
+        radar, points, boxes = transform_batch(radar_points, points, boxes, draws)
+        metas = [dict(meta, lidar2img=view_mats(meta['lidar2img'], draw)) for meta, draw in zip(img_metas, draws)]
+        return metas, radar, points, boxes
 
     def _maps_or_built(self, img, radar_points, radar_depth, radar_rcs, img_metas):
         if (radar_depth is None) != (radar_rcs is None):
